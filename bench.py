@@ -22,7 +22,13 @@ for SMN_BENCH_STALL_S (120) seconds or the run exceeds SMN_BENCH_RANK_TIMEOUT_S 
 and its phase and the run exits non-zero.  When the RCCL communicator cannot be brought up the run exits non-zero too
 (`"comm": {"fallback": reason}`) unless --allow-replica-fallback asks for independent replicas.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and
+prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, with the workload's `config`
+and `result`); nothing else runs on the GPU or the host.  --full adds everything else the line used to carry: the
+hipEvents around the dominant kernel in the timed region, the untimed detail pass (`phases_ms`), `roofline` and its
+probes, `cpu_baseline`, the other workloads of BASELINE.json (`other_workloads`) and the sharded line's one-GPU build
+reference.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; the inputs are
+seeded, so two builds can be compared output for output).
 """
 import argparse
 import ctypes as C
@@ -77,11 +83,18 @@ def parse():
     p.add_argument("--no-exclusive-probe", action="store_true", help="skip the look-ahead-off pass that fills frac_exclusive")
     p.add_argument("--with-ntk", action="store_true", help="sharded path: build NNGP + NTK jointly and pipeline both (default for --config c5)")
     p.add_argument("--no-other-workloads", action="store_true",
-                   help="skip C2 / C5 / C3 / fp64 / predictive-path measurements appended to the default line")
+                   help="skip C2 / C5 / C3 / fp64 / predictive-path measurements appended to the --full line")
     p.add_argument("--sharded-path", action="store_true",
                    help="run the P>1 step (sharded build + column-first exchange + LML) even with one rank (rehearsal on one GPU)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: detail pass, roofline and its probes, CPU baseline, "
+                        "the other workloads, the sharded line's one-GPU build reference (the --no-* options apply here)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
     p.add_argument("--rendezvous-file", default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     for k, v in CONFIGS[a.config].items():
         if getattr(a, k) is None:
             setattr(a, k, v)
@@ -419,6 +432,36 @@ def cpu_baseline(args, np_dtype, eps, gpu_logpdf=None):
     return out
 
 
+DUMP_ROWS = 64          # rows of an N x N output that --dump-outputs keeps (a fixed, seeded sample)
+
+
+def lower_rows_sample(ctx, ptr, n, ld, np_dtype, rows=DUMP_ROWS, seed=0):
+    """A fixed, seeded sample of an N x N device matrix whose lower triangle is defined: `rows` whole rows, read one by one,
+    with the entries above the diagonal set to 0.  Returns (row indices as float64, rows x N values as float64)."""
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=min(rows, n), replace=False))
+    isz = np.dtype(np_dtype).itemsize
+    vals = np.empty((len(idx), n), np_dtype)
+    for k, i in enumerate(idx):
+        ctx.call("smn_memcpy_d2h", vals[k].ctypes.data_as(C.c_void_p), C.c_void_p(ptr.value + isz * int(i) * ld), isz * n)
+    vals[np.arange(n)[None, :] > idx[:, None]] = 0
+    return idx.astype(np.float64), vals.astype(np.float64)
+
+
+def lml_outputs(lp, quad, logdet, info):
+    """What one SPR.loss step hands its caller (smn_spr_loss / smn_lml): four host scalars, as 1-element arrays."""
+    return {name: np.array([v], np.float64) for name, v in (("logpdf", lp), ("quad", quad), ("logdet", logdet), ("info", info))}
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 class _JsonOut:
     """The contract is ONE JSON line on stdout.  RCCL prints a version banner to stdout when a communicator comes up, so
     file descriptor 1 is pointed at stderr for the whole run and the JSON line is written to a saved copy of the real one."""
@@ -450,10 +493,11 @@ def read_profile(ctx, per_steps):
 
 
 # ----------------------------------------------------------------------------- C3: conv-NNGP + Student-t, fp64
-def measure_conv(L, ctx, n, nl, act, eps, steps, warmup, cpu_sample_n=0):
+def measure_conv(L, ctx, n, nl, act, eps, steps, warmup, cpu_sample_n=0, outputs=None):
     """BASELINE configs[2]: 4-layer conv-NNGP kernel of N CIFAR-shaped images (32x32x3) + Student-t (inverse-gamma scale
     mixture, alpha = beta = 2) log-marginal likelihood, fp64, one GPU.  SURVEY 8(d): VALU-bound, reported as
-    pair-pixel-layers per second with the VALU-busy share of the committed PMC pass."""
+    pair-pixel-layers per second with the VALU-busy share of the committed PMC pass.  `outputs` (a dict): filled with what
+    the last timed step computed (the likelihood's scalars and a seeded row sample of the kernel matrix)."""
     h = w = 32; c = 3
     rng = np.random.default_rng(0)
     xh = rng.standard_normal((n, h, w, c))
@@ -482,6 +526,9 @@ def measure_conv(L, ctx, n, nl, act, eps, steps, warmup, cpu_sample_n=0):
     dt = time.perf_counter() - t0
     ms_per_step = dt / steps * 1e3
     build_ms = tb[0] / steps * 1e3
+    if outputs is not None:
+        outputs.update(lml_outputs(lp.value, quad.value, logdet.value, info.value))
+        outputs["kernel_row_index"], outputs["kernel_rows"] = lower_rows_sample(ctx, k.ptr, n, n, np.float64)
     ppl = n * (n + 1) / 2.0 * h * w * nl                       # pair-pixel-layers of the lower triangle (what is computed)
     valu = None
     for name in ("r03_pmc_cnn.json", "r02_pmc_cnn.json"):
@@ -524,10 +571,13 @@ def measure_conv(L, ctx, n, nl, act, eps, steps, warmup, cpu_sample_n=0):
 
 
 def bench_conv(args, out_fd, L, ctx, sync, rank, world):
+    outputs = {} if args.dump_outputs else None
     out = measure_conv(L, ctx, args.n, args.layers, args.act, args.eps if args.eps is not None else 1e-4, args.steps, args.warmup,
-                       cpu_sample_n=0 if args.no_cpu_baseline else (args.cpu_sample_n or 160))
+                       cpu_sample_n=0 if (args.no_cpu_baseline or not args.full) else (args.cpu_sample_n or 160), outputs=outputs)
     out.update({"n_gpus": world, "scaling": "strong", "vs_baseline": None})
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         out_fd.emit(json.dumps(out))
 
 
@@ -888,12 +938,13 @@ def main():
     y = ctx.to_device(rng.standard_normal(n).astype(np_dtype))
     lp, quad, logdet, info = C.c_double(), C.c_double(), C.c_double(), C.c_int()
     res = {}
+    ntk = None
 
     if not sharded:
         def step():
             ctx.call("smn_spr_loss", code, L.NET_MLP, act, nl, 1.0, 1e-8, 1.0, x.ptr, n, d, d, y.ptr, eps, 0.0, 1.0,
                      C.byref(lp), C.byref(quad), C.byref(logdet), C.byref(info))
-            res["v"] = (lp.value, logdet.value, info.value)
+            res["v"] = (lp.value, quad.value, logdet.value, info.value)
         parts = 0
     else:
         # Cyclic column-first shard (sharding.py): rank r builds every lower tile of its tile rows in ONE launch into its own
@@ -909,7 +960,6 @@ def main():
         spec = (L.NET_MLP, act, nl, 1.0, 1e-8, 1.0)
         # BASELINE config 5 ("erf NNGP + NTK ... shard + single-GPU Cholesky on assembled kernel"): the build launch is the
         # joint NNGP + NTK one and the NTK's pieces ride the same streams into a full matrix of the caller's
-        ntk = None
         if args.config == "c5" or args.with_ntk:
             ntk_arrays = (ctx.empty((lay["elems"],), np_dtype), ctx.empty((world * lay["elems"],), np_dtype), ctx.empty((n, n), np_dtype))
             res["ntk_arrays"] = ntk_arrays                  # owners stay alive for the run
@@ -921,23 +971,62 @@ def main():
             k = res["k"]
             v = sharding.lml_sharded_cols(backend, code, spec, x.ptr, n, d, d, y.ptr, rank, world, mine.ptr, stage.ptr,
                                           eps, 0.0, 1.0, cols=cols, ntk=ntk, progress=lambda ph: say("step %d: %s" % (k, ph)))
-            res["v"] = (v[0], v[2], v[3])
+            res["v"] = tuple(v)
+
+    def finish():
+        if sharded:
+            say("final barrier")
+            sync.barrier()
+            ctx.call("smn_comm_destroy")
+        if wd is not None:
+            wd.done()
 
     say("warm-up")
     for _ in range(args.warmup):
         step()
     say("barrier before the timed region")
     sync.barrier()
-    # Timed region: hipEvent pairs around the launches of the DOMINANT kernel only (category 5, the Cholesky trailing
-    # update: 79 launches per step).  Pairs around all ~280 launches of a step cost ~2 ms of queue time per step
+    # Timed region.  --full: hipEvent pairs around the launches of the DOMINANT kernel only (category 5, the Cholesky
+    # trailing update: 79 launches per step).  Pairs around all ~280 launches of a step cost ~2 ms of queue time per step
     # (profiles/r01e_event_overhead.txt), so the other categories are timed in a separate, untimed pass below.
-    ctx.call("smn_profile_enable", 2 << 5)
+    if args.full:
+        ctx.call("smn_profile_enable", 2 << 5)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     say("barrier after the timed region")
     sync.barrier()
     dt = time.perf_counter() - t0
+    last = res["v"]                                # (logpdf, quad, logdet, info) of the last timed step
+    if args.dump_outputs and rank == 0:
+        outputs = lml_outputs(*last)
+        if ntk is not None:                        # the NTK the sharded C5 step assembles in the caller's matrix
+            outputs["ntk_row_index"], outputs["ntk_rows"] = lower_rows_sample(ctx, ntk[2], n, n, np_dtype)
+        dump_outputs(args.dump_outputs, outputs)
+
+    def headline(ms_per_step):
+        flops_counted = 2.0 * n * n * d + n ** 3 / 3.0                 # SURVEY.md 8(d): Gram 2N^2 d + Cholesky N^3/3
+        return {
+            "metric": "kernel-build + Cholesky wallclock (ms) and GFLOP/s at N=%d, %d-layer %s NNGP" % (n, nl, args.act),
+            "value": flops_counted / (ms_per_step * 1e-3) / 1e9, "unit": "GFLOP/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong" if (sharded or world == 1) else "replicas", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic", "comm": comm,
+            "config": {"workload": "%s: SPR.loss = NNGP kernel build + jittered Cholesky + Gaussian LML, N=%d d=%d L=%d %s"
+                                   % (args.config.upper(), n, d, nl, args.act),
+                       "N": n, "d": d, "layers": nl, "act": args.act, "w_std": 1.0, "b_std": 1e-8, "last_w_std": 1.0,
+                       "eps_abs": eps, "flops_counted": flops_counted,
+                       "parallelism": ("single GPU" if world == 1 else "%d independent replicas (--allow-replica-fallback; no RCCL communicator: %s)" % (world, comm["fallback"])) if not sharded else
+                       "cyclic tile-row shards x%d (one build launch per rank), column-first exchange in %d ranges (RCCL all-gather + scatter per range on side streams, consumed by the factorisation range by range), replicated Cholesky" % (world, parts)},
+            "result": {"logpdf": last[0], "logdet": last[2], "info": last[3]},
+        }
+
+    if not args.full:
+        dt = sync.max(dt)
+        if rank == 0:
+            out_fd.emit(json.dumps(headline(dt / args.steps * 1e3)))
+        finish()
+        return
     say("detail pass")
     ms, cnt = C.c_double(), C.c_int()
     ctx.call("smn_profile_read", 5, C.byref(ms), C.byref(cnt))
@@ -961,7 +1050,6 @@ def main():
 
     if rank == 0:
         n_total = n + TILE
-        flops_counted = 2.0 * n * n * d + n ** 3 / 3.0                 # SURVEY.md 8(d): Gram 2N^2 d + Cholesky N^3/3
         trail_fl, strip_fl = fl[5], fl[4]
         peak = PEAK_F32_MFMA_TFLOPS if args.dtype == "f32" else PEAK_F64_MFMA_TFLOPS
         per = prof                                 # per step: `trail` from the timed region, the rest from the detail pass
@@ -1050,25 +1138,14 @@ def main():
         # what the step EXECUTED on the MFMA (lower-triangle Gram tiles, whole update tiles) over its wall time, beside the
         # SURVEY-sanctioned counted rate in `value`
         executed = build_fl + trail_fl + strip_fl
-        out = {
-            "metric": "kernel-build + Cholesky wallclock (ms) and GFLOP/s at N=%d, %d-layer %s NNGP" % (n, nl, args.act),
-            "value": flops_counted / (ms_per_step * 1e-3) / 1e9, "unit": "GFLOP/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong" if (sharded or world == 1) else "replicas", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic", "comm": comm,
-            "config": {"workload": "%s: SPR.loss = NNGP kernel build + jittered Cholesky + Gaussian LML, N=%d d=%d L=%d %s"
-                                   % (args.config.upper(), n, d, nl, args.act),
-                       "N": n, "d": d, "layers": nl, "act": args.act, "w_std": 1.0, "b_std": 1e-8, "last_w_std": 1.0,
-                       "eps_abs": eps, "flops_counted": flops_counted,
-                       "parallelism": ("single GPU" if world == 1 else "%d independent replicas (--allow-replica-fallback; no RCCL communicator: %s)" % (world, comm["fallback"])) if not sharded else
-                       "cyclic tile-row shards x%d (one build launch per rank), column-first exchange in %d ranges (RCCL all-gather + scatter per range on side streams, consumed by the factorisation range by range), replicated Cholesky" % (world, parts)},
+        out = headline(ms_per_step)
+        out.update({
             "executed_tflops": executed / (ms_per_step * 1e-3) / 1e12,
             "executed_note": "MFMA flops actually issued per step (lower-triangle Gram tiles + whole update tiles; rank 0's share of the build when sharded) / step time; `value` counts 2N^2 d + N^3/3",
             "phases_ms": {k: round(v[0], 4) for k, v in per.items()},
             "phases_ms_source": "trail: hipEvents in the timed region; others: separate untimed pass with events on every launch",
-            "result": {"logpdf": res["v"][0], "logdet": res["v"][1], "info": res["v"][2]},
             "roofline": roof,
-        }
+        })
         if sharded:
             # The north-star's "kernel-build speed-up at N GPUs", stated with and without the exchange.  The rank's build is ONE
             # launch on every CU (`kernel_build_ms`).  The all-gathers (`exchange_ms`, summed over the column ranges) and the
@@ -1150,16 +1227,11 @@ def main():
             del x, y                                   # the headline's inputs: the extra workloads bring their own
             out["other_workloads"] = other_workloads(L, ctx)
         if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args, np_dtype, eps, res["v"][0])
+            out["cpu_baseline"] = cpu_baseline(args, np_dtype, eps, last[0])
         elif world == 1:
             out["cpu_baseline"] = None
         out_fd.emit(json.dumps(out))
-    if sharded:
-        say("final barrier")
-        sync.barrier()
-        ctx.call("smn_comm_destroy")
-    if wd is not None:
-        wd.done()
+    finish()
 
 
 if __name__ == "__main__":

@@ -9,16 +9,16 @@ rm -rf $O/stats $O/pmc
 cd $R
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $O/gpu_tests.log 2>&1
 echo "pytest rc=$?"; tail -4 $O/gpu_tests.log
-timeout -k 10 500 python3 bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 500 python3 bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-recursion-probe --no-exclusive-probe --no-other-workloads > $O/stats.json 2> $O/stats.err; echo "stats rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-recursion-probe --no-exclusive-probe --no-other-workloads > $O/stats.json 2> $O/stats.err; echo "stats rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc/$c -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-recursion-probe --no-exclusive-probe --no-other-workloads > $O/pmc_$c.json 2> $O/pmc_$c.err; echo "pmc $c rc=$?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc/$c -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-recursion-probe --no-exclusive-probe --no-other-workloads > $O/pmc_$c.json 2> $O/pmc_$c.err; echo "pmc $c rc=$?"
 done
 cd $R
 SMNNGP_LIB=$R/scale-mixtures-of-neural-network-gaussian-processes_amd/libsmnngp_timing.so timeout -k 10 120 python3 scratch/r03/panel_timing.py > $O/panel_timeline.txt 2>&1; echo "timeline rc=$?"
 timeout -k 10 300 bash scratch/rec_table.sh > $O/recursion_table.txt 2>&1; echo "rec table rc=$?"
-timeout -k 10 200 python3 bench.py --sharded-path --no-cpu-baseline > $O/bench_sharded_one_rank.json 2> $O/bench_sharded.err; echo "sharded rc=$?"
+timeout -k 10 200 python3 bench.py --full --sharded-path --no-cpu-baseline > $O/bench_sharded_one_rank.json 2> $O/bench_sharded.err; echo "sharded rc=$?"
 python3 - <<PY
 import csv, glob, json, collections
 d = json.load(open("$O/bench.json"))

@@ -208,3 +208,31 @@ def test_watchdog_overall_limit_and_a_rank_that_never_started(tmp_path):
     (d / "hb_1").write_text(json.dumps({"phase": "done", "t_phase": time.time() - 9, "t": time.time()}))
     got = bench.diagnose(str(d), 2, "test")
     assert got["stuck_rank"] == 0 and got["phase"] == "smn_comm_init"        # a finished rank is never the stuck one
+
+
+def test_full_is_off_by_default_and_steps_is_checked(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dumped_outputs_are_float_npy_files(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    out = bench.lml_outputs(-1.5, 2.0, 3.25, 0)
+    out["rows"] = np.arange(6, dtype=np.float32).reshape(2, 3)
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    got = {p.name[:-4]: np.load(str(p)) for p in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["info", "logdet", "logpdf", "quad", "rows"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["logpdf"].tolist() == [-1.5] and got["quad"].tolist() == [2.0] and got["info"].tolist() == [0.0]
+    assert np.array_equal(got["rows"], out["rows"])

@@ -59,7 +59,7 @@ def test_replica_fallback_only_on_request_and_labelled():
 
 def test_sharded_path_on_a_one_rank_communicator_equals_the_fused_step():
     r1, l1 = _run([])
-    r2, l2 = _run(["--sharded-path"])
+    r2, l2 = _run(["--sharded-path", "--full"])                        # the exchange / build figures come from the detail pass
     assert r1.returncode == 0 and r2.returncode == 0, (r1.stderr[-1500:], r2.stderr[-1500:])
     a, b = json.loads(l1[0]), json.loads(l2[0])
     assert b["comm"] == {"rccl_ranks": 1, "fallback": None} and a["comm"]["rccl_ranks"] == 0
@@ -75,7 +75,7 @@ def test_one_gpu_build_reference_of_the_sharded_line_is_one_launch():
     the sharded line's reference for `build_only_speedup` must be the one-launch build with the chip to itself, not the average of
     the two launches: with one rank the ratio is about 1."""
     big = ["--n", "14400", "--d", "256", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-recursion-probe",
-           "--no-exclusive-probe", "--no-other-workloads", "--sharded-path"]
+           "--no-exclusive-probe", "--no-other-workloads", "--sharded-path", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + big, capture_output=True, text=True, timeout=420, env=env)
     assert r.returncode == 0, r.stderr[-1500:]
