@@ -80,7 +80,10 @@ def relu_map(k, q1, q2, theta=None):
     c = np.clip(c, -1.0, 1.0)
     ang = np.arccos(c)
     kdot = (np.pi - ang) / (2.0 * np.pi)
-    k_new = (np.sqrt(np.maximum(p - k * k, 0.0)) + (np.pi - ang) * k) / (2.0 * np.pi)
+    # J from the clipped c alone: sqrt(p - k^2) and acos(k / sqrt(p)) from differently rounded quantities do not cancel
+    # at |c| -> 1 (3e-9 on K, amplified to ~1e-5 by the next layer's Kdot; tests/test_mp_golden.py)
+    # ((1 - c)(1 + c): 1 - c^2 would lose the last digits of the square root at c -> -1, where J -> 0)
+    k_new = sp * (np.sqrt(np.maximum((1.0 - c) * (1.0 + c), 0.0)) + (np.pi - ang) * c) / (2.0 * np.pi)
     th = None if theta is None else (theta * kdot).astype(dt)
     return k_new.astype(dt), (q1 / 2.0).astype(dt), (q2 / 2.0).astype(dt), th
 
@@ -89,8 +92,12 @@ def erf_map(k, q1, q2, theta=None):
     """neural_tangents stax.Erf kernel transform (Williams 1997). Appendix A.2."""
     dt = k.dtype
     p = np.outer(1.0 + 2.0 * q1, 1.0 + 2.0 * q2)
-    kdot = 4.0 / (np.pi * np.sqrt(np.maximum(p - 4.0 * k * k, 0.0)))
-    k_new = (2.0 / np.pi) * np.arcsin(np.clip(2.0 * k / np.sqrt(p), -1.0, 1.0))
+    sp = np.sqrt(p)
+    c = np.clip(2.0 * k / sp, -1.0, 1.0)
+    # p - 4 k^2 = p (1 - c)(1 + c): the factored form keeps its digits at |c| -> 1
+    with np.errstate(divide="ignore"):
+        kdot = 4.0 / (np.pi * sp * np.sqrt(np.maximum((1.0 - c) * (1.0 + c), 0.0)))
+    k_new = (2.0 / np.pi) * np.arcsin(c)
     q1n = (2.0 / np.pi) * np.arcsin(2.0 * q1 / (1.0 + 2.0 * q1))
     q2n = (2.0 / np.pi) * np.arcsin(2.0 * q2 / (1.0 + 2.0 * q2))
     th = None if theta is None else (theta * kdot).astype(dt)
@@ -228,8 +235,9 @@ def cnn_kernel(x1, x2=None, num_hiddens=1, act="relu", w_std=1.0, b_std=0.0,
             sp = np.sqrt(p)
             with np.errstate(divide="ignore", invalid="ignore"):
                 cc = np.where(sp > 0, k / sp, 0.0)
-            ang = np.arccos(np.clip(cc, -1.0, 1.0))
-            k = (np.sqrt(np.maximum(p - k * k, 0.0)) + (np.pi - ang) * k) / (2 * np.pi)
+            cc = np.clip(cc, -1.0, 1.0)
+            ang = np.arccos(cc)
+            k = sp * (np.sqrt(np.maximum((1.0 - cc) * (1.0 + cc), 0.0)) + (np.pi - ang) * cc) / (2 * np.pi)   # (relu_map)
             q1, q2 = q1 / 2.0, q2 / 2.0
         elif act == "erf":
             p = (1 + 2 * q1)[:, None] * (1 + 2 * q2)[None, :]
@@ -405,8 +413,10 @@ def _act_maps(k, q1, q2, act):
         sp = np.sqrt(p)
         with np.errstate(divide="ignore", invalid="ignore"):
             cc = np.where(sp > 0, k / sp, 0.0)
-        ang = np.arccos(np.clip(cc, -1.0, 1.0))
-        return (np.sqrt(np.maximum(p - k * k, 0.0)) + (np.pi - ang) * k) / (2 * np.pi), q1 / 2.0, q2 / 2.0
+        cc = np.clip(cc, -1.0, 1.0)
+        ang = np.arccos(cc)
+        return (sp * (np.sqrt(np.maximum((1.0 - cc) * (1.0 + cc), 0.0)) + (np.pi - ang) * cc) / (2 * np.pi),   # (relu_map)
+                q1 / 2.0, q2 / 2.0)
     if act == "erf":
         p = (1 + 2 * q1)[:, None] * (1 + 2 * q2)[None, :]
         kk = (2 / np.pi) * np.arcsin(np.clip(2 * k / np.sqrt(p), -1.0, 1.0))
