@@ -1099,32 +1099,31 @@ __global__ void init_scalars_kernel(double* logdet, int* info) {
 }
 
 template <typename T>
-int launch_update(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t r0, int64_t c0, int64_t k0, int64_t K,
-                  int64_t tiles_m, int64_t tiles_n, int lower, int tag = -1) {
+int launch_update(smn_ctx* ctx, const FactorCall& f, hipStream_t st, T* a, int64_t lda, int64_t r0, int64_t c0, int64_t k0,
+                  int64_t K, int64_t tiles_m, int64_t tiles_n, int lower, int tag = -1) {
   if (tiles_m <= 0 || tiles_n <= 0 || K <= 0) return SMN_OK;
   if (tag < 0) tag = lower ? 1 : 0;   // 0: strip update, 1: trailing update (separate symbols / profile categories)
-  if (ctx->chol_id0 >= 0) {
+  if (f.id0 >= 0) {
     // Identity rows [id0, id1) (analytic gradients): row id0 + i of the panel is zero left of column i, so the rows from
     // id0 + k0 + K on multiply zeros in this update -- as row operand AND as column operand.  What is left is the
     // contiguous rows [r0, act) in the caller's shape plus the rows below the identity block (the right-hand sides)
     // against the live columns; launched as such (the same tiles, the same arithmetic), not as one grid whose dead
     // workgroups leave at once: the XCD-aware tile order hands every XCD one contiguous eighth of the grid, and the dead
     // tiles are the last 70 % of it (profiles/r03_grad_identity_skip.txt: 3 of 8 XCDs were doing all the work).
-    const int64_t id0 = ctx->chol_id0, id1 = ctx->chol_id1, r_end = r0 + tiles_m * kTile;
+    const int64_t id0 = f.id0, id1 = f.id1, r_end = r0 + tiles_m * kTile;
     const int64_t act = std::min(id1, id0 + (k0 + K + kTile - 1) / kTile * kTile);
     if (act < id1 && r_end > act) {
-      ctx->chol_id0 = -1;
-      int rc = SMN_OK;
-      if (r0 < act) rc = launch_update<T>(ctx, st, a, lda, r0, c0, k0, K, (act - r0) / kTile, tiles_n, lower, tag);
-      if (rc == SMN_OK && r_end > id1) {
+      FactorCall live = f;   // the pieces below are launched as plain updates
+      live.id0 = live.id1 = -1;
+      if (r0 < act) SMN_TRY(launch_update<T>(ctx, live, st, a, lda, r0, c0, k0, K, (act - r0) / kTile, tiles_n, lower, tag));
+      if (r_end > id1) {
         const int64_t tb = (r_end - id1) / kTile;
         // live columns of those rows: the caller's own (strip, trapezoid: all left of id0) or, for a triangle, [c0, act)
         const int64_t nb = lower == 1 ? (act - c0) / kTile : tiles_n;
-        rc = launch_update<T>(ctx, st, a, lda, id1, c0, k0, K, tb, nb, 0, tag);
-        if (rc == SMN_OK && lower == 1) rc = launch_update<T>(ctx, st, a, lda, id1, id1, k0, K, tb, tb, 1, tag);
+        SMN_TRY(launch_update<T>(ctx, live, st, a, lda, id1, c0, k0, K, tb, nb, 0, tag));
+        if (lower == 1) SMN_TRY(launch_update<T>(ctx, live, st, a, lda, id1, id1, k0, K, tb, tb, 1, tag));
       }
-      ctx->chol_id0 = id0;
-      return rc;
+      return SMN_OK;
     }
   }
   if (lower == 2 && tiles_n >= tiles_m) {   // a trapezoid as wide as it is tall is the triangle
@@ -1132,8 +1131,8 @@ int launch_update(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t r0, i
     tiles_n = tiles_m;
   }
   UpdArgs<T> u{a, lda, r0, c0, k0, (int)K, (int)tiles_n, lower, 0, TileMap::make(tiles_m, tiles_n, lower == 1),
-               ctx->batch_logdet ? ctx->batch_stride : 0};
-  const unsigned gy = (unsigned)(ctx->batch_logdet ? ctx->batch : 1);
+               f.batch_logdet ? f.batch_stride : 0};
+  const unsigned gy = (unsigned)(f.batch_logdet ? f.batch : 1);
   int64_t nt = lower == 1   ? tiles_m * (tiles_m + 1) / 2
                : lower == 2 ? tiles_n * (tiles_n + 1) / 2 + (tiles_m - tiles_n) * tiles_n
                             : tiles_m * tiles_n;
@@ -1201,15 +1200,17 @@ int launch_update(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t r0, i
 }
 
 template <typename T, int XRV>
-int launch_panel_x(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t j0, int64_t n_total, int prefactored) {
+int launch_panel_x(smn_ctx* ctx, const FactorCall& f, hipStream_t st, T* a, int64_t lda, int64_t j0, int64_t n_total,
+                   int prefactored) {
   const int64_t rbeg = j0 + PB;
   const int64_t below = n_total - rbeg;
   const unsigned grid = below > 0 ? (unsigned)((below + XRV - 1) / XRV) : 1u;
-  const bool batched = ctx->batch_logdet != nullptr;   // (a batch of ONE problem still keeps its scalars in the batch arrays)
-  const unsigned gy = (unsigned)(batched ? ctx->batch : 1);
-  const int64_t bs = batched ? ctx->batch_stride : 0, ls = batched ? ctx->batch_ldiag_stride : 0;
-  double* logdet = batched ? ctx->batch_logdet : ctx->d_scal;
-  int* info = batched ? ctx->batch_info : ctx->d_info;
+  const bool batched = f.batch_logdet != nullptr;   // (a batch of ONE problem still keeps its scalars in the batch arrays)
+  const unsigned gy = (unsigned)(batched ? f.batch : 1);
+  // problem g's factored diagonal blocks: workspace slot 3 (cholesky_t) at g * n_factor * PB elements
+  const int64_t bs = batched ? f.batch_stride : 0, ls = batched ? f.n_factor * PB : 0;
+  double* logdet = batched ? f.batch_logdet : ctx->d_scal;
+  int* info = batched ? f.batch_info : ctx->d_info;
   if (ctx->panel_leaf && !prefactored) {
     ProfScope ps(ctx, PROF_PANEL, st);
     T* ldiag = reinterpret_cast<T*>(ctx->ws[3]) + (j0 / PB) * (int64_t)(PB * PB);
@@ -1219,17 +1220,17 @@ int launch_panel_x(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t j0, 
     // N = 16384 32.6 -> 31.1 ms; more passes than groups / CUs lose (even under the look-ahead's contention), and the f32
     // 128-row form gains nothing at N = 36864 (its workgroups already carry 128 rows): f64 only.
     int passes = 1;
-    if (sizeof(T) == 8 && !batched && ctx->chol_id0 < 0 && (int64_t)grid > (int64_t)ctx->num_cu)
+    if (sizeof(T) == 8 && !batched && f.id0 < 0 && (int64_t)grid > (int64_t)ctx->num_cu)
       passes = (int)std::min<int64_t>(((int64_t)grid + ctx->num_cu - 1) / ctx->num_cu, (int64_t)ctx->panel_max_passes);
     // a batch that fills the chip is throughput-bound: fewer workgroups per problem, each factoring the diagonal block once
     // for up to four groups of rows, is less work in all (the grid search's two batches 13.3 -> 12.9 ms, 256 problems of
     // N = 245 1.43 -> 1.34 us each)
-    if (batched && ctx->chol_id0 < 0 && (int64_t)gy * grid > 2 * (int64_t)ctx->num_cu && grid > 1)
+    if (batched && f.id0 < 0 && (int64_t)gy * grid > 2 * (int64_t)ctx->num_cu && grid > 1)
       passes = (int)std::min<int64_t>((int64_t)grid, (int64_t)ctx->panel_max_passes);
     const unsigned gridp = (grid + (unsigned)passes - 1) / (unsigned)passes;
     auto kernr = panelr_kernel<T, XRV>;
     hipLaunchKernelGGL(kernr, dim3(gridp, gy), dim3(2 * panel_threads(XRV)), panelr_lds_bytes<T>(XRV), st, a, lda, j0, rbeg, n_total,
-                       logdet, info, ldiag, ctx->chol_id0, ctx->chol_id1, bs, ls, passes);
+                       logdet, info, ldiag, f.id0, f.id1, bs, ls, passes);
     SMN_CHECK_LAUNCH(ctx);
     return SMN_OK;
   }
@@ -1238,27 +1239,28 @@ int launch_panel_x(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t j0, 
     ProfScope ps(ctx, PROF_PANEL, st);
     T* ldiag = reinterpret_cast<T*>(ctx->ws[3]) + (j0 / PB) * (int64_t)(PB * PB);
     hipLaunchKernelGGL(kern, dim3(grid, gy), dim3(panel_threads(XRV)), panel_lds_bytes<T>(XRV), st, a, lda, j0, rbeg, n_total,
-                       prefactored, logdet, info, ldiag, ctx->chol_id0, ctx->chol_id1, bs, ls);
+                       prefactored, logdet, info, ldiag, f.id0, f.id1, bs, ls);
   }
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
 
 template <typename T>
-int launch_panel(smn_ctx* ctx, hipStream_t st, T* a, int64_t lda, int64_t j0, int64_t n_total, int prefactored) {
+int launch_panel(smn_ctx* ctx, const FactorCall& f, hipStream_t st, T* a, int64_t lda, int64_t j0, int64_t n_total,
+                 int prefactored) {
   if constexpr (sizeof(T) == 4 && PanelCfg<T>::XR == 128) {
     // few rows left: 16-row workgroups (eight times as many, each with half the block-update work)
     const int64_t below = n_total - (j0 + PB);
     if (below <= (int64_t)kPanelSmallRows) {
       // latency-bound (one problem, or a batch that does not fill the chip anyway): 16-row workgroups; a batch that does fill
       // it is throughput-bound, and every workgroup redoes the diagonal block: 64-row ones, a quarter as many
-      const int64_t gy = ctx->batch_logdet ? ctx->batch : 1;
+      const int64_t gy = f.batch_logdet ? f.batch : 1;
       if (gy * ((below + kPanelSmallXR - 1) / kPanelSmallXR) <= 2 * (int64_t)ctx->num_cu)
-        return launch_panel_x<T, kPanelSmallXR>(ctx, st, a, lda, j0, n_total, prefactored);
-      return launch_panel_x<T, 64>(ctx, st, a, lda, j0, n_total, prefactored);
+        return launch_panel_x<T, kPanelSmallXR>(ctx, f, st, a, lda, j0, n_total, prefactored);
+      return launch_panel_x<T, 64>(ctx, f, st, a, lda, j0, n_total, prefactored);
     }
   }
-  return launch_panel_x<T, PanelCfg<T>::XR>(ctx, st, a, lda, j0, n_total, prefactored);
+  return launch_panel_x<T, PanelCfg<T>::XR>(ctx, f, st, a, lda, j0, n_total, prefactored);
 }
 
 template <typename T>
@@ -1304,19 +1306,23 @@ int set_lds_attrs(smn_ctx* ctx) {
 }
 
 template <typename T>
-int cholesky_t(smn_ctx* ctx, T* a, int64_t n_total, int64_t n_factor, int64_t lda, int64_t n_shift, double jitter_abs,
-               double ridge_rel, bool keep_factor) {
+int cholesky_t(smn_ctx* ctx, const FactorCall& f) {
+  T* a = static_cast<T*>(f.a);
+  const int64_t n_total = f.n_total, n_factor = f.n_factor, lda = f.lda;
+  // Every way out leaves the caller's stream behind each arrival it was handed and behind F1 (the far update on the bulk
+  // stream, below): the caller may free or reuse the workspace at once
+  SideJoin pieces{ctx, f.n_arrivals ? f.arrivals_on : nullptr, nullptr};
+  SideJoin bulk{ctx, nullptr, ctx->ev_b};   // armed by the first F1 launch
   SMN_TRY(set_lds_attrs<T>(ctx));
   void* side = nullptr;   // factored diagonal blocks, [n_factor/128][128*128]
-  SMN_TRY(smn_workspace(ctx, 3, sizeof(T) * (size_t)n_factor * PB * (size_t)(ctx->batch_logdet ? ctx->batch : 1), &side));
-  ctx->batch_ldiag_stride = n_factor * PB;
+  SMN_TRY(smn_workspace(ctx, 3, sizeof(T) * (size_t)n_factor * PB * (size_t)(f.batch_logdet ? f.batch : 1), &side));
   hipStream_t st = ctx->stream;
-  if (!ctx->chol_prepped) hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(1), 0, st, ctx->d_scal, ctx->d_info);
-  if (!ctx->chol_prepped && n_shift > 0 && (jitter_abs != 0.0 || ridge_rel != 0.0)) {
-    if (ridge_rel != 0.0)
-      hipLaunchKernelGGL(diag_trace_kernel<T>, dim3(1), dim3(256), 0, st, a, lda, n_shift, ctx->d_scal + 1);
-    hipLaunchKernelGGL(diag_shift_kernel<T>, dim3((unsigned)((n_shift + 255) / 256)), dim3(256), 0, st, a, lda,
-                       n_shift, jitter_abs, ridge_rel, ctx->d_scal + 1);
+  if (!f.prepped) hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(1), 0, st, ctx->d_scal, ctx->d_info);
+  if (!f.prepped && f.n_shift > 0 && (f.jitter_abs != 0.0 || f.ridge_rel != 0.0)) {
+    if (f.ridge_rel != 0.0)
+      hipLaunchKernelGGL(diag_trace_kernel<T>, dim3(1), dim3(256), 0, st, a, lda, f.n_shift, ctx->d_scal + 1);
+    hipLaunchKernelGGL(diag_shift_kernel<T>, dim3((unsigned)((f.n_shift + 255) / 256)), dim3(256), 0, st, a, lda,
+                       f.n_shift, f.jitter_abs, f.ridge_rel, ctx->d_scal + 1);
   }
   SMN_CHECK_LAUNCH(ctx);
   // Two-level, right-looking.  Inside a super-panel of S columns the K = 256 updates touch only the super-panel's
@@ -1339,133 +1345,112 @@ int cholesky_t(smn_ctx* ctx, T* a, int64_t n_total, int64_t n_factor, int64_t ld
   if (S < W) S = W;
   int64_t Swide = kSuperWide;
   if (Swide < S) Swide = S;
-  bool bulk_busy = false;
-  // ctx->chol_noschur: the trailing block of the appended rows (rows and columns >= n_factor) is neither read nor written
+  // f.noschur: the trailing block of the appended rows (rows and columns >= n_factor) is neither read nor written
   // -- the caller wants B L^-T only (grad.hip: X = L^-T from B = I, then K~^-1 = X X^T as one full-rate launch), and the
   // matrix need not even have those columns (lda >= n_factor suffices)
-  const bool noschur = ctx->chol_noschur && n_factor < n_total;
-  int rc = SMN_OK;
-  auto hip_ok = [&](hipError_t e) {
-    if (e != hipSuccess && rc == SMN_OK)
-      rc = smn_fail(ctx, SMN_EHIP, "cholesky: %s", hipGetErrorString(e));
-  };
+  const bool noschur = f.noschur && n_factor < n_total;
   // Column-first multi-GPU exchange (heads.hip smn_lml_from_shards): the kernel's columns land in this workspace piece by
   // piece while the factorisation is already being issued.  A stream about to touch columns [.., col_hi) waits for the
   // pieces that hold them, once each: a sub-panel for its own 128 columns, the near updates for their super-panel's, F0 for the next super-panel's,
   // the bulk update F1 for everything.  The first wait (super-panel 0) is what of the exchange is exposed; later ones are
   // stalls the first panel chain did not cover (separate profile categories).
-  const bool arriving = ctx->consume_arrivals && !ctx->arrivals.empty();
+  const bool arriving = f.n_arrivals > 0;
   std::vector<char> seen_main, seen_bulk;
   if (arriving) {
-    seen_main.assign(ctx->arrivals.size(), 0);
-    seen_bulk.assign(ctx->arrivals.size(), 0);
+    seen_main.assign(f.n_arrivals, 0);
+    seen_bulk.assign(f.n_arrivals, 0);
   }
   bool first_need = true;
   auto need_columns = [&](hipStream_t s, int64_t col_hi) -> int {
     if (!arriving) return SMN_OK;
     std::vector<char>& seen = (s == st) ? seen_main : seen_bulk;
     bool any = false;
-    for (size_t i = 0; i < ctx->arrivals.size(); ++i)
-      if (!seen[i] && ctx->arrivals[i].col_begin < col_hi) any = true;
+    for (size_t i = 0; i < f.n_arrivals; ++i)
+      if (!seen[i] && f.arrivals[i].col_begin < col_hi) any = true;
     if (!any) return SMN_OK;
     ProfScope ps(ctx, first_need ? PROF_EXPOSED : PROF_STALL, s);
     first_need = false;
-    for (size_t i = 0; i < ctx->arrivals.size(); ++i)
-      if (!seen[i] && ctx->arrivals[i].col_begin < col_hi) {
-        SMN_HIP(ctx, hipStreamWaitEvent(s, ctx->arrivals[i].ev, 0));
+    for (size_t i = 0; i < f.n_arrivals; ++i)
+      if (!seen[i] && f.arrivals[i].col_begin < col_hi) {
+        SMN_HIP(ctx, hipStreamWaitEvent(s, f.arrivals[i].ev, 0));
         seen[i] = 1;
       }
     return SMN_OK;
   };
-  auto body = [&]() -> int {
-    // Super-panels are wider while many rows are left (the update-bound phase: a K = 2048 far update runs closer to the
-    // tile engine's rate and halves the launches and their tails) and S wide in the chain-bound rest.
-    auto width = [&](int64_t c0) { return (sb && n_total - c0 >= ctx->super_wide_rows) ? Swide : S; };
-    for (int64_t s0 = 0, s_stop = 0; s0 < n_factor; s0 = s_stop) {
-      const int64_t Sc = width(s0);
-      const int64_t s_end = (n_factor - s0 < Sc) ? n_factor : s0 + Sc;
-      s_stop = s_end;
-      for (int64_t j0 = s0; j0 < s_end; j0 += W) {
-        const int64_t w = (s_end - j0 < W) ? s_end - j0 : W;
-        for (int64_t js = j0; js < j0 + w; js += PB) {
-          SMN_TRY(need_columns(st, js + PB));   // (arrivals: a sub-panel and its strip touch their own 128 columns only)
-          if (js > j0)   // strip: this sub-panel's 128 columns, K = the outer panel's finished columns
-            SMN_TRY(launch_update<T>(ctx, st, a, lda, js, js, j0, js - j0, (n_total - js) / kTile, 1, 0));
-          SMN_TRY(launch_panel<T>(ctx, st, a, lda, js, n_total, 0));
-        }
-        const int64_t j1 = j0 + w;
-        if (j1 < s_end) SMN_TRY(need_columns(st, s_end));
-        if (j1 < s_end)   // near update: columns [j1, s_end), all rows from the diagonal down
-          SMN_TRY(launch_update<T>(ctx, st, a, lda, j1, j1, j0, w, (n_total - j1) / kTile, (s_end - j1) / kTile, 2));
+  // Super-panels are wider while many rows are left (the update-bound phase: a K = 2048 far update runs closer to the
+  // tile engine's rate and halves the launches and their tails) and S wide in the chain-bound rest.
+  auto width = [&](int64_t c0) { return (sb && n_total - c0 >= ctx->super_wide_rows) ? Swide : S; };
+  for (int64_t s0 = 0, s_stop = 0; s0 < n_factor; s0 = s_stop) {
+    const int64_t Sc = width(s0);
+    const int64_t s_end = (n_factor - s0 < Sc) ? n_factor : s0 + Sc;
+    s_stop = s_end;
+    for (int64_t j0 = s0; j0 < s_end; j0 += W) {
+      const int64_t w = (s_end - j0 < W) ? s_end - j0 : W;
+      for (int64_t js = j0; js < j0 + w; js += PB) {
+        SMN_TRY(need_columns(st, js + PB));   // (arrivals: a sub-panel and its strip touch their own 128 columns only)
+        if (js > j0)   // strip: this sub-panel's 128 columns, K = the outer panel's finished columns
+          SMN_TRY(launch_update<T>(ctx, f, st, a, lda, js, js, j0, js - j0, (n_total - js) / kTile, 1, 0));
+        SMN_TRY(launch_panel<T>(ctx, f, st, a, lda, js, n_total, 0));
       }
-      if (s_end >= n_total) break;
-      const int64_t K = s_end - s0;
-      if (!sb) {   // far update, one launch
-        SMN_TRY(need_columns(st, n_total));
-        const int64_t tm = (n_total - s_end) / kTile;
-        if (!noschur) SMN_TRY(launch_update<T>(ctx, st, a, lda, s_end, s_end, s0, K, tm, tm, 1));
-        else if (n_factor > s_end) SMN_TRY(launch_update<T>(ctx, st, a, lda, s_end, s_end, s0, K, tm, (n_factor - s_end) / kTile, 2));
-        continue;
-      }
-      const int64_t Sn = width(s_end);   // the next super-panel's width decides where F0 ends and F1 begins
-      const int64_t s_next = s_end >= n_factor ? s_end : ((n_factor - s_end < Sn) ? n_factor : s_end + Sn);
-      // Once F1 is small (the chain-bound tail) it starts BEHIND F0 instead of beside it: F0 is on the chain's critical path
-      // and, sharing the chip with an F1 that nobody waits for, takes three times as long (profiles/r02_tail_chain_timeline.txt).
-      const int64_t tm1 = n_total > s_next ? (n_total - s_next) / kTile : 0;
-      const int64_t tn1 = noschur ? (n_factor > s_next ? (n_factor - s_next) / kTile : 0) : tm1;   // F1's tile columns
-      const bool f0_first = tn1 * (tn1 + 1) / 2 + (tm1 - tn1) * tn1 <= kF0FirstTiles;
-      if (!f0_first) {
-        SMN_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-        SMN_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_a, 0));
-      }
-      if (bulk_busy) SMN_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_b, 0));
-      if (s_next > s_end) SMN_TRY(need_columns(st, s_next));
-      if (s_next > s_end)   // F0
-        SMN_TRY(launch_update<T>(ctx, st, a, lda, s_end, s_end, s0, K, (n_total - s_end) / kTile, (s_next - s_end) / kTile, 2));
-      if (f0_first) {
-        SMN_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-        SMN_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_a, 0));
-      }
-      if (n_total > s_next && tn1 > 0) {   // F1
-        const int64_t tm = (n_total - s_next) / kTile;
-        bulk_busy = true;       // set first: an error below must still join the bulk stream
-        SMN_TRY(need_columns(sb, n_total));
-        if (!noschur) {
-          SMN_TRY(launch_update<T>(ctx, sb, a, lda, s_next, s_next, s0, K, tm, tm, 1));
-        } else {
-          // no Schur block: the triangle of the columns left, then the rectangle of the appended rows under it (two
-          // launches, so that each takes the XCD patch order a trapezoid does not have)
-          SMN_TRY(launch_update<T>(ctx, sb, a, lda, s_next, s_next, s0, K, tn1, tn1, 1));
-          if (tm > tn1) SMN_TRY(launch_update<T>(ctx, sb, a, lda, s_next + tn1 * kTile, s_next, s0, K, tm - tn1, tn1, 0, 1));
-        }
-        SMN_HIP(ctx, hipEventRecord(ctx->ev_b, sb));
-      }
+      const int64_t j1 = j0 + w;
+      if (j1 < s_end) SMN_TRY(need_columns(st, s_end));
+      if (j1 < s_end)   // near update: columns [j1, s_end), all rows from the diagonal down
+        SMN_TRY(launch_update<T>(ctx, f, st, a, lda, j1, j1, j0, w, (n_total - j1) / kTile, (s_end - j1) / kTile, 2));
     }
-    return SMN_OK;
-  };
-  rc = body();
-  if (arriving) {   // the caller's stream ends up behind every piece, whatever the column structure above consumed
-    const int rc2 = need_columns(st, INT64_MAX);
-    if (rc == SMN_OK) rc = rc2;
-    if (rc != SMN_OK) (void)hipStreamSynchronize(ctx->stream_scatter);
-  }
-  // The caller's stream continues after the bulk stream whatever happened above: an error exit must not leave F1 work
-  // running behind a workspace the caller is about to free or reuse.
-  if (bulk_busy) {
-    if (rc != SMN_OK) {
-      (void)hipStreamSynchronize(sb);
-    } else {
-      hip_ok(hipEventRecord(ctx->ev_b, sb));
-      hip_ok(hipStreamWaitEvent(st, ctx->ev_b, 0));
+    if (s_end >= n_total) break;
+    const int64_t K = s_end - s0;
+    if (!sb) {   // far update, one launch
+      SMN_TRY(need_columns(st, n_total));
+      const int64_t tm = (n_total - s_end) / kTile;
+      if (!noschur) SMN_TRY(launch_update<T>(ctx, f, st, a, lda, s_end, s_end, s0, K, tm, tm, 1));
+      else if (n_factor > s_end) SMN_TRY(launch_update<T>(ctx, f, st, a, lda, s_end, s_end, s0, K, tm, (n_factor - s_end) / kTile, 2));
+      continue;
+    }
+    const int64_t Sn = width(s_end);   // the next super-panel's width decides where F0 ends and F1 begins
+    const int64_t s_next = s_end >= n_factor ? s_end : ((n_factor - s_end < Sn) ? n_factor : s_end + Sn);
+    // Once F1 is small (the chain-bound tail) it starts BEHIND F0 instead of beside it: F0 is on the chain's critical path
+    // and, sharing the chip with an F1 that nobody waits for, takes three times as long (profiles/r02_tail_chain_timeline.txt).
+    const int64_t tm1 = n_total > s_next ? (n_total - s_next) / kTile : 0;
+    const int64_t tn1 = noschur ? (n_factor > s_next ? (n_factor - s_next) / kTile : 0) : tm1;   // F1's tile columns
+    const bool f0_first = tn1 * (tn1 + 1) / 2 + (tm1 - tn1) * tn1 <= kF0FirstTiles;
+    if (!f0_first) {
+      SMN_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+      SMN_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_a, 0));
+    }
+    if (bulk.side) SMN_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_b, 0));
+    if (s_next > s_end) SMN_TRY(need_columns(st, s_next));
+    if (s_next > s_end)   // F0
+      SMN_TRY(launch_update<T>(ctx, f, st, a, lda, s_end, s_end, s0, K, (n_total - s_end) / kTile, (s_next - s_end) / kTile, 2));
+    if (f0_first) {
+      SMN_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+      SMN_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_a, 0));
+    }
+    if (n_total > s_next && tn1 > 0) {   // F1
+      const int64_t tm = (n_total - s_next) / kTile;
+      bulk.side = sb;   // armed first: an error below must still join the bulk stream
+      SMN_TRY(need_columns(sb, n_total));
+      if (!noschur) {
+        SMN_TRY(launch_update<T>(ctx, f, sb, a, lda, s_next, s_next, s0, K, tm, tm, 1));
+      } else {
+        // no Schur block: the triangle of the columns left, then the rectangle of the appended rows under it (two
+        // launches, so that each takes the XCD patch order a trapezoid does not have)
+        SMN_TRY(launch_update<T>(ctx, f, sb, a, lda, s_next, s_next, s0, K, tn1, tn1, 1));
+        if (tm > tn1) SMN_TRY(launch_update<T>(ctx, f, sb, a, lda, s_next + tn1 * kTile, s_next, s0, K, tm - tn1, tn1, 0, 1));
+      }
+      SMN_HIP(ctx, hipEventRecord(ctx->ev_b, sb));
     }
   }
-  if (rc == SMN_OK && keep_factor && ctx->batch_logdet) rc = smn_fail(ctx, SMN_ENOTSUP, "cholesky: keep_factor in a batched factorisation");
-  if (rc == SMN_OK && keep_factor) {
+  // the caller's stream ends up behind every piece, whatever the column structure above consumed
+  SMN_TRY(need_columns(st, INT64_MAX));
+  pieces.release();
+  SMN_TRY(bulk.join());
+  if (f.keep_factor && f.batch_logdet) return smn_fail(ctx, SMN_ENOTSUP, "cholesky: keep_factor in a batched factorisation");
+  if (f.keep_factor) {
     hipLaunchKernelGGL(copy_diag_kernel<T>, dim3((unsigned)(n_factor / PB)), dim3(1024), 0, st, a, lda,
                        static_cast<const T*>(side));
-    hip_ok(hipGetLastError());
+    SMN_CHECK_LAUNCH(ctx);
   }
-  return rc;
+  return SMN_OK;
 }
 
 }  // namespace
@@ -1500,24 +1485,15 @@ int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const
   return SMN_OK;
 }
 
-int cholesky_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda, int64_t n_shift,
-                    double jitter_abs, double ridge_rel, bool keep_factor, int64_t id0, int64_t id1) {
-  if (n_total % kTile || n_factor % kTile || n_factor > n_total || n_factor <= 0)
+int cholesky_padded(smn_ctx* ctx, const FactorCall& f) {
+  if (f.n_total % kTile || f.n_factor % kTile || f.n_factor > f.n_total || f.n_factor <= 0)
     return smn_fail(ctx, SMN_EINVAL, "cholesky_padded: n_total=%lld n_factor=%lld must be multiples of %d",
-                    (long long)n_total, (long long)n_factor, kTile);
-  if (lda % (16 / (int)dtype_size(dtype)) || (reinterpret_cast<uintptr_t>(a) & 15))
+                    (long long)f.n_total, (long long)f.n_factor, kTile);
+  if (f.lda % (16 / (int)dtype_size(f.dtype)) || (reinterpret_cast<uintptr_t>(f.a) & 15))
     return smn_fail(ctx, SMN_EINVAL, "cholesky_padded: matrix must be 16-byte aligned");
-  if (id0 >= 0 && (id0 < n_factor || id0 % kTile || id1 < id0 || id1 > n_total))
+  if (f.id0 >= 0 && (f.id0 < f.n_factor || f.id0 % kTile || f.id1 < f.id0 || f.id1 > f.n_total))
     return smn_fail(ctx, SMN_EINVAL, "cholesky_padded: bad identity-row hint");
-  ctx->chol_id0 = id0;
-  ctx->chol_id1 = id0 >= 0 ? id1 : -1;
-  const int rc = dtype == SMN_F64
-                     ? cholesky_t<double>(ctx, static_cast<double*>(a), n_total, n_factor, lda, n_shift, jitter_abs,
-                                          ridge_rel, keep_factor)
-                     : cholesky_t<float>(ctx, static_cast<float*>(a), n_total, n_factor, lda, n_shift, jitter_abs, ridge_rel,
-                                         keep_factor);
-  ctx->chol_id0 = ctx->chol_id1 = -1;
-  return rc;
+  return f.dtype == SMN_F64 ? cholesky_t<double>(ctx, f) : cholesky_t<float>(ctx, f);
 }
 
 // Solve-only sweep: rows [n_factor, n_total) of `a` <- rows * L^-T with L = the (already factored)
@@ -1532,10 +1508,11 @@ int solve_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t
   // where the purely left-looking sweep issued n_factor / 128 launches of tm tiles with K up to n_factor).
   int64_t S = ctx->super_panel / PB * PB;
   if (S < PB) S = PB;
+  const FactorCall plain{};   // one problem, no identity rows
   auto upd = [&](int64_t c0, int64_t k0, int64_t K, int64_t tiles_n) -> int {
     const int tag = K >= 256 ? 1 : 0;   // the pipelined K loop from K = 256 on (profile category: trailing update)
-    if (dtype == SMN_F64) return launch_update<double>(ctx, st, static_cast<double*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
-    return launch_update<float>(ctx, st, static_cast<float*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
+    if (dtype == SMN_F64) return launch_update<double>(ctx, plain, st, static_cast<double*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
+    return launch_update<float>(ctx, plain, st, static_cast<float*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
   };
   if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx));
   else SMN_TRY(set_lds_attrs<float>(ctx));

@@ -30,8 +30,7 @@ struct smn_ctx {
   // (cholesky.hip need_columns): the panel chain of a super-panel for its own columns only, the far update for the rest.
   void* shard_a = nullptr; int64_t shard_lda = 0, shard_n = 0; int shard_dtype = -1; double shard_eps = 0.0;
   struct Arrival { int64_t col_begin, col_end; hipEvent_t ev; };
-  std::vector<Arrival> arrivals;          // in issue order; cleared by smn_shard_begin and by the factorisation that consumed them
-  bool consume_arrivals = false;          // set by smn_lml_from_shards around its factorisation
+  std::vector<Arrival> arrivals;          // in issue order; cleared by smn_shard_begin and by smn_lml_from_shards
   std::vector<hipEvent_t> ev_pool;        // events of the pieces (gathered / arrived), reused from pipeline to pipeline
   size_t ev_pool_used = 0;
   std::string err;
@@ -59,24 +58,14 @@ struct smn_ctx {
   int64_t super_panel = 1024;        // columns per super-panel of the two-level Cholesky (env SMN_SUPER)
   int64_t super_wide_rows = 18432;   // super-panels are kSuperWide columns while at least this many rows are left (env SMN_SUPER_WIDE_ROWS;
                                      // measured: wide pays from ~18k rows left on, profiles/r02_wide_super_panel_sweep.txt; 0 rows = always wide)
-  // structural-zero hint for the factorisation in flight: appended rows [id0, id1) hold an identity block
-  // (row id0 + i is zero left of column i), set by cholesky_padded, -1 = none
-  int64_t chol_id0 = -1, chol_id1 = -1;
-  // batched factorisation (heads.hip spr_batch): `batch` problems of identical shape, problem g at a + g * batch_stride
-  // elements, its logdet / info in batch_logdet[g] / batch_info[g]; every panel / update launch gets grid.y = batch
   size_t batch_bytes = (size_t)48 << 30;   // workspace budget of one batched pass (smn_debug_batch_bytes)
-  int batch = 1; int64_t batch_stride = 0, batch_ldiag_stride = 0; double* batch_logdet = nullptr; int* batch_info = nullptr;
   // Split build of the headline path (heads.hip aug_build, smn_spr_loss with the look-ahead): the bottom-right corner of the
   // kernel matrix (tile rows and columns >= corner_tile) is built on the bulk stream BESIDE the first super-panel's panel
   // chain, which needs none of it; the factorisation takes it as one Arrival.  The two tile orders live in tile_list.
   int* tile_list = nullptr; int64_t tile_list_cap = 0; int tile_list_tm = 0, tile_list_tb = 0, tile_list_na = 0, tile_list_nb = 0;
   hipEvent_t ev_s0 = nullptr, ev_corner = nullptr;   // main -> bulk (the first launch is done); bulk -> main (the corner has landed)
-  bool trace_ready = false;          // the build in front left the trace of the kernel's diagonal in d_scal[1] (BuildCall::want_trace)
   bool split_build = true;           // smn_debug_split_build
   int panel_max_passes = 4;          // row groups one panel workgroup may carry (smn_debug_panel_passes; 1: one group each, as before round 4)
-  int64_t corner_col = 0;            // first column of the corner of the split build in flight (0: none)
-  bool chol_noschur = false;         // the factorisation in flight leaves the appended rows' trailing block alone (cholesky.hip)
-  bool chol_prepped = false;         // the caller has shifted the diagonal and reset logdet / info already (aug_prep)
   std::unordered_map<const void*, size_t> max_lds;   // largest dynamic-LDS size already allowed per kernel (smn_allow_lds)
   bool lds_attrs_done[2] = {false, false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) issued for f32 / f64 kernels
   bool panel_leaf = true;            // panelr_kernel (register-resident 16x16 leaf) in the factorisation; env SMN_PANEL_LEAF=0: panel_kernel
@@ -153,6 +142,29 @@ struct SmnDeviceGuard {
   SmnDeviceGuard& operator=(const SmnDeviceGuard&) = delete;
 };
 #define SMN_ENTER(ctx) SmnDeviceGuard smn_device_guard_((ctx)->device)
+
+// Work of this call on a side stream, joined back into the main stream on every way out of a scope.  join() -- the success
+// path -- makes the main stream wait for `ev`, recorded on the side stream behind that work (no host wait).  Leaving the
+// scope without join() -- an error return -- synchronises the side stream on the host instead: nothing a failed call issued
+// may still run behind a workspace its caller frees or reuses.  release(): a later call takes the work over and joins it.
+// side == nullptr: nothing in flight.
+struct SideJoin {
+  smn_ctx* ctx;
+  hipStream_t side;
+  hipEvent_t ev;
+  ~SideJoin() {
+    if (side) (void)hipStreamSynchronize(side);
+  }
+  int join() {
+    if (side) {
+      SMN_HIP(ctx, hipEventRecord(ev, side));
+      SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
+    }
+    side = nullptr;
+    return SMN_OK;
+  }
+  void release() { side = nullptr; }
+};
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 

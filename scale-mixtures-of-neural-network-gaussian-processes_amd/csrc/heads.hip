@@ -53,11 +53,12 @@ double logpdf_from(double quad, double logdet, int64_t n, double df, double scal
 }
 
 // Fused build of the augmented matrix straight from the inputs.
-// allow_split: the caller goes on to aug_finish with an absolute jitter only (smn_spr_loss): under the look-ahead the
-// bottom-right corner of the matrix is then built on the bulk stream beside the first super-panel's panel chain (run_build).
+// out: the caller goes on to aug_finish with it.  Under the look-ahead the bottom-right corner of the matrix is then built
+// on the bulk stream beside the first super-panel's panel chain (run_build); want_trace leaves the trace of the kernel's
+// diagonal for a relative ridge.
 int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, int64_t ldx, const void* xt,
               int64_t ldxt, int64_t d, int nbatch = 0, const double* bw = nullptr, const double* bb = nullptr,
-              const double* blw = nullptr, bool allow_split = false, bool want_trace = false) {
+              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false) {
   const int64_t kp = k_pad(spec.dtype, d);
   void* xs = nullptr;
   SMN_TRY(smn_workspace(ctx, 0, g.es * (size_t)kp * (size_t)g.n_total + sizeof(double) * (size_t)g.n_total, &xs));
@@ -75,59 +76,58 @@ int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, 
   c.get_mask = SMN_GET_NNGP;
   c.out_k = g.a; c.ldo = g.lda;
   c.nbatch = nbatch; c.bw = bw; c.bb = bb; c.blw = blw; c.out_bs = g.n_total * g.lda;   // batched: problem b at a + b * n_total^2
-  // (not while pieces of a column-first exchange are pending on this context: the Arrival list is theirs)
-  c.split_corner = (allow_split && nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
+  // (not while pieces of a column-first exchange are still landing in this workspace)
+  c.split_corner = (out && nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
   c.want_trace = (want_trace && nbatch == 0) ? 1 : 0;   // (relative ridge: the prep launch then carries the shift, aug_finish)
-  return run_build(ctx, c);
+  return run_build(ctx, c, out);
 }
 
-int aug_finish(smn_ctx* ctx, int dtype, const Aug& g, const void* y, int64_t ldy, int64_t n_shift, double jitter_abs,
-               double ridge_rel, void* mean, void* cov, int64_t ldcov, double* quad_h, double* logdet_h, int* info_h,
-               bool td_identity = false) {
+// built: what the build in front left behind (none: {}).  shards: the pieces of a column-first exchange still landing in
+// the workspace (smn_lml_from_shards).
+int aug_finish(smn_ctx* ctx, int dtype, const Aug& g, const BuildOut& built, const void* y, int64_t ldy, int64_t n_shift,
+               double jitter_abs, double ridge_rel, void* mean, void* cov, int64_t ldcov, double* quad_h, double* logdet_h,
+               int* info_h, bool td_identity = false, const std::vector<smn_ctx::Arrival>* shards = nullptr) {
+  // a split build (aug_build): the corner is still being built on the bulk stream; joined on every way out until the
+  // factorisation takes it over
+  const int64_t corner = built.corner_col;
+  SideJoin corner_join{ctx, corner > 0 ? ctx->stream_bulk : nullptr, nullptr};
   if (g.c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");   // the mailbox holds 62 doubles
   // the right-hand-side rows, the diagonal shift and the scalar reset are one launch: with an absolute jitter only, or with the
   // relative ridge when the build in front left the trace of the kernel's diagonal (aug_build want_trace)
-  const bool traced = ctx->trace_ready;
-  ctx->trace_ready = false;
-  const bool prepped = g.c > 0 && (ridge_rel == 0.0 || traced);
+  const bool prepped = g.c > 0 && (ridge_rel == 0.0 || built.trace);
   const int64_t n_sh = (jitter_abs != 0.0 || ridge_rel != 0.0) ? n_shift : 0;
-  // a split build (aug_build): the corner's columns are prepped behind the corner's own launch, on the bulk stream, and the
-  // factorisation takes them as ONE arrival (cholesky.hip need_columns: whoever first touches those columns waits for it)
-  const int64_t corner = ctx->corner_col;
-  ctx->corner_col = 0;
+  // the corner's columns are prepped behind the corner's own launch, on the bulk stream, and the factorisation takes them as
+  // ONE arrival (cholesky.hip need_columns: whoever first touches those columns waits for it)
   if (corner > 0 && !prepped) SMN_HIP(ctx, hipStreamSynchronize(ctx->stream_bulk));   // (no caller does this: the trace needs every column)
-  const bool split = corner > 0 && prepped && !ctx->consume_arrivals;
+  const bool split = corner > 0 && prepped;
+  const smn_ctx::Arrival corner_arrival{corner, g.n_total, ctx->ev_corner};
   if (split) {
     const int64_t sh = n_sh;
     SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, corner, y, g.n, g.c, ldy, std::min(sh, corner), jitter_abs, 0, nullptr, ridge_rel, n_shift));
-    const int prc = aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy, sh, jitter_abs, corner, ctx->stream_bulk, ridge_rel, n_shift);
-    if (prc != SMN_OK) {
-      (void)hipStreamSynchronize(ctx->stream_bulk);
-      return prc;
-    }
+    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy, sh, jitter_abs, corner, ctx->stream_bulk, ridge_rel, n_shift));
     SMN_HIP(ctx, hipEventRecord(ctx->ev_corner, ctx->stream_bulk));
-    ctx->arrivals.clear();
-    ctx->arrivals.push_back({corner, g.n_total, ctx->ev_corner});
-    ctx->consume_arrivals = true;
   } else if (prepped) {
     if (corner > 0) SMN_HIP(ctx, hipStreamSynchronize(ctx->stream_bulk));
     SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy, n_sh, jitter_abs, 0, nullptr, ridge_rel, n_shift));
   } else {
     SMN_TRY(set_aug_rows(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy));
   }
-  ctx->chol_prepped = prepped;
-  // identity test rows (the small-N gradient route): whole 128-row tiles of them are skipped where they are structurally zero
-  const int64_t id0 = td_identity ? g.n_pad : -1, id1 = td_identity ? g.n_pad + g.t / kTile * kTile : -1;
-  const int crc = cholesky_padded(ctx, dtype, g.a, g.n_total, g.n_pad, g.lda, n_shift, jitter_abs, ridge_rel, false, id0, id1);
-  ctx->chol_prepped = false;
-  if (split) {   // (the factorisation has made the caller's stream wait for the corner, whatever its return code)
-    ctx->arrivals.clear();
-    ctx->consume_arrivals = false;
+  FactorCall f{dtype, g.a, g.n_total, g.n_pad, g.lda, n_shift, jitter_abs, ridge_rel, false};
+  f.prepped = prepped;
+  if (td_identity) {   // identity test rows (the small-N gradient route): whole 128-row tiles of them are skipped where they are structurally zero
+    f.id0 = g.n_pad;
+    f.id1 = g.n_pad + g.t / kTile * kTile;
   }
-  SMN_TRY(crc);
+  if (split) {
+    f.arrivals = &corner_arrival; f.n_arrivals = 1; f.arrivals_on = ctx->stream_bulk;
+  } else if (shards) {
+    f.arrivals = shards->data(); f.n_arrivals = shards->size(); f.arrivals_on = ctx->stream_scatter;
+  }
+  SMN_TRY(cholesky_padded(ctx, f));
+  corner_join.release();   // the factorisation has left the caller's stream behind the corner
   // a column-first exchange: the factorisation has waited for the pieces of the workspace; pieces scattered elsewhere (the NTK
   // of config 5, smn_shard_exchange_cols_to) ride the same scatter stream -- the call returns behind all of them
-  if (ctx->consume_arrivals) SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
+  if (shards) SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
   double* quad_dev = ctx->d_scal + 8;
   SMN_TRY(extract_posterior(ctx, dtype, g.a, g.lda, g.n_pad, g.t, g.c, mean, cov, ldcov, quad_dev, true));
   double ld = 0.0;
@@ -156,7 +156,7 @@ extern "C" int smn_cholesky(smn_ctx* ctx, int dtype, void* a_d, int64_t n_total,
   const bool inplace = n_total % kTile == 0 && n_factor % kTile == 0 && lda % (16 / (int64_t)es) == 0 &&
                        (reinterpret_cast<uintptr_t>(a_d) & 15) == 0;
   if (inplace) {
-    SMN_TRY(cholesky_padded(ctx, dtype, a_d, n_total, n_factor, lda, n_shift, jitter_abs, ridge_rel, true));
+    SMN_TRY(cholesky_padded(ctx, FactorCall{dtype, a_d, n_total, n_factor, lda, n_shift, jitter_abs, ridge_rel, true}));
   } else {
     const int64_t m = n_total - n_factor, nfp = round_up(n_factor, kTile), ntp = nfp + round_up(m, kTile);
     void* w = nullptr;
@@ -168,7 +168,7 @@ extern "C" int smn_cholesky(smn_ctx* ctx, int dtype, void* a_d, int64_t n_total,
     SMN_TRY(copy_matrix(ctx, dtype, wb + es * (size_t)(nfp * ntp), ntp, ab + es * (size_t)(n_factor * lda), lda, m, n_factor, 0));
     SMN_TRY(copy_matrix(ctx, dtype, wb + es * (size_t)(nfp * ntp + nfp), ntp, ab + es * (size_t)(n_factor * lda + n_factor), lda, m, m, 1));
     SMN_TRY(fill_identity_pad(ctx, dtype, w, ntp, nfp, n_factor));
-    SMN_TRY(cholesky_padded(ctx, dtype, w, ntp, nfp, ntp, n_shift, jitter_abs, ridge_rel, true));
+    SMN_TRY(cholesky_padded(ctx, FactorCall{dtype, w, ntp, nfp, ntp, n_shift, jitter_abs, ridge_rel, true}));
     char* ao = static_cast<char*>(a_d);
     SMN_TRY(copy_matrix(ctx, dtype, ao, lda, wb, ntp, n_factor, n_factor, 1));
     SMN_TRY(copy_matrix(ctx, dtype, ao + es * (size_t)(n_factor * lda), lda, wb + es * (size_t)(nfp * ntp), ntp, m, n_factor, 0));
@@ -237,7 +237,7 @@ extern "C" int smn_lml(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ld
   SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
   double quad = 0.0, ld = 0.0;
   int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
+  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
   if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
@@ -262,7 +262,7 @@ extern "C" int smn_lml_from_blocks(smn_ctx* ctx, int dtype, const void* stage_d,
   SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
   double quad = 0.0, ld = 0.0;
   int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
+  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
   if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
@@ -458,9 +458,7 @@ extern "C" int smn_lml_from_shards(smn_ctx* ctx, int dtype, int64_t n, const voi
   int info = 0;
   // jitter_abs = 0: the scatter added it already.  The factorisation consumes the Arrivals and leaves the main stream behind
   // all of them.
-  ctx->consume_arrivals = true;
-  const int rc = aug_finish(ctx, dtype, g, y_d, 1, n, 0.0, 0.0, nullptr, nullptr, 0, &quad, &ld, &info);
-  ctx->consume_arrivals = false;
+  const int rc = aug_finish(ctx, dtype, g, {}, y_d, 1, n, 0.0, 0.0, nullptr, nullptr, 0, &quad, &ld, &info, false, &ctx->arrivals);
   ctx->arrivals.clear();
   ctx->shard_a = nullptr;
   SMN_TRY(rc);
@@ -516,7 +514,7 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
                          reinterpret_cast<float*>(g.at(g.n_pad, 0)), g.lda, n);
     SMN_CHECK_LAUNCH(ctx);
     SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-    return aug_finish(ctx, dtype, g, y_d, 1, n, eps_abs, 0.0, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, true);
+    return aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, true);
   }
   const size_t es = dtype_size(dtype);
   const int64_t n_pad = round_up(n, kTile), n_app = round_up(n + 1, kTile), n_total = n_pad + n_app, lda = n_pad;
@@ -537,12 +535,11 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
   SMN_TRY(fill_identity_pad(ctx, dtype, a, lda, n_pad, n));
   // y^T in the row behind the identity block, the absolute jitter on the diagonal, logdet / info reset: one launch
   SMN_TRY(aug_prep(ctx, dtype, a, lda, n_pad + n, n_pad, y_d, n, 1, 1, eps_abs != 0.0 ? n : 0, eps_abs));
-  ctx->chol_prepped = true;
-  ctx->chol_noschur = true;
-  const int crc = cholesky_padded(ctx, dtype, a, n_total, n_pad, lda, n, eps_abs, 0.0, false, n_pad, n_pad + n / kTile * kTile);
-  ctx->chol_prepped = false;
-  ctx->chol_noschur = false;
-  SMN_TRY(crc);
+  FactorCall f{dtype, a, n_total, n_pad, lda, n, eps_abs, 0.0, false};
+  f.id0 = n_pad;
+  f.id1 = n_pad + n / kTile * kTile;
+  f.prepped = f.noschur = true;
+  SMN_TRY(cholesky_padded(ctx, f));
   double* quad_dev = ctx->d_scal + 8;
   SMN_TRY(inverse_from_rows(ctx, dtype, xrows, lda, xrows + es * (size_t)n * (size_t)lda, n_pad, n, ninv_d, ldinv, alpha_d, quad_dev));
   double ld = 0.0, quad = 0.0;
@@ -570,7 +567,7 @@ int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int
   SMN_TRY(copy_matrix(ctx, dtype, g.at(g.n_pad, 0), g.lda, kb + g.es * (size_t)(n * ldk), ldk, t, n, 0));
   SMN_TRY(copy_matrix(ctx, dtype, g.at(g.n_pad, g.n_pad), g.lda, kb + g.es * (size_t)(n * ldk + n), ldk, t, t, 1));
   SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-  return aug_finish(ctx, dtype, g, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
+  return aug_finish(ctx, dtype, g, {}, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
 }
 
 extern "C" int smn_predict(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d,
@@ -594,10 +591,11 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, true));
+  BuildOut built;
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built));
   double quad = 0.0, ld = 0.0;
   int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
+  SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
   if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
@@ -733,12 +731,10 @@ int spr_batch(smn_ctx* ctx, const char* who, int dtype, int net, int act, int nu
                            static_cast<const float*>(y_d), n, c, c, n, sh_d, ridge_rel ? rel_d : nullptr, tr_d, ld_d, info_d);
     }
     SMN_CHECK_LAUNCH(ctx);
-    ctx->batch = nb; ctx->batch_stride = bstride; ctx->batch_logdet = ld_d; ctx->batch_info = info_d;
-    ctx->chol_prepped = true;
-    const int crc = cholesky_padded(ctx, dtype, g.a, g.n_total, g.n_pad, g.lda, n, 0.0, 0.0, false);
-    ctx->chol_prepped = false;
-    ctx->batch = 1; ctx->batch_stride = 0; ctx->batch_logdet = nullptr; ctx->batch_info = nullptr;
-    SMN_TRY(crc);
+    FactorCall f{dtype, g.a, g.n_total, g.n_pad, g.lda, n, 0.0, 0.0, false};
+    f.prepped = true;
+    f.batch = nb; f.batch_stride = bstride; f.batch_logdet = ld_d; f.batch_info = info_d;
+    SMN_TRY(cholesky_padded(ctx, f));
     {
       const int64_t w = std::max<int64_t>(std::max(t, c), 1);
       dim3 ge((unsigned)((w + 255) / 256), (unsigned)std::min<int64_t>(t + 1, 4096), (unsigned)nb);
@@ -839,6 +835,7 @@ extern "C" int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int nu
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, 0, nullptr, nullptr, nullptr, true, ridge_rel != 0.0));
-  return aug_finish(ctx, dtype, g, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
+  BuildOut built;
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, 0, nullptr, nullptr, nullptr, &built, ridge_rel != 0.0));
+  return aug_finish(ctx, dtype, g, built, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
 }

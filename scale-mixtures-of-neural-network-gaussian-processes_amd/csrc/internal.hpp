@@ -58,12 +58,17 @@ struct BuildCall {
   // only -- host arrays bw / bb / blw --, problem g written at out_k + g * out_bs elements
   int nbatch; const double* bw; const double* bb; const double* blw; int64_t out_bs;
   // split_corner = TB > 0 (symmetric, un-sharded, one problem): the tiles with row AND column >= T - TB go out as a second
-  // launch on the bulk stream; ctx->corner_col / ev_corner tell the factorisation (cholesky.hip need_columns) when they landed
+  // launch on the bulk stream, still in flight when run_build returns (BuildOut::corner_col)
   int split_corner;
-  // want_trace: leave sum_i<nv0 K_ii (from the exact-diagonal table) in ctx->d_scal[1] and set ctx->trace_ready
+  // want_trace: leave sum_i<nv0 K_ii (from the exact-diagonal table) in ctx->d_scal[1] (BuildOut::trace)
   int want_trace;
 };
-int run_build(smn_ctx* ctx, const BuildCall& c);
+// What a build leaves behind for the factorisation after it (heads.hip aug_finish).
+struct BuildOut {
+  int64_t corner_col = 0;   // first column of the corner of a split build, still being built on the bulk stream (0: none)
+  bool trace = false;       // the trace of the kernel's diagonal is in ctx->d_scal[1]
+};
+int run_build(smn_ctx* ctx, const BuildCall& c, BuildOut* out = nullptr);   // out: needed by split_corner
 // TB for a split build of T tile rows on this context (0: do not split)
 int split_corner_tiles(const smn_ctx* ctx, int64_t tiles);
 
@@ -76,11 +81,23 @@ int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, i
 
 inline int64_t k_pad(int dtype, int64_t d) { return round_up(d, dtype == SMN_F64 ? 16 : 32); }
 
-// Partial Cholesky on a padded matrix (n_total, n_factor multiples of 128).  Device-side results:
-// logdet (double) and info (int) are left in ctx->d_scal[0] / ctx->d_info[0]; no host sync.
-int cholesky_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda,
-                    int64_t n_shift, double jitter_abs, double ridge_rel, bool keep_factor,
-                    int64_t id0 = -1, int64_t id1 = -1);   // id0/id1: appended rows [id0, id1) are an identity block
+// One partial Cholesky on a padded matrix (n_total, n_factor multiples of 128).  Device-side results: logdet (double) and
+// info (int) are left in ctx->d_scal[0] / ctx->d_info[0] (batched: batch_logdet[g] / batch_info[g]); no host sync.
+struct FactorCall {
+  int dtype; void* a; int64_t n_total, n_factor, lda;
+  int64_t n_shift; double jitter_abs, ridge_rel;
+  bool keep_factor;
+  int64_t id0 = -1, id1 = -1;   // appended rows [id0, id1) hold an identity block (row id0 + i is zero left of column i)
+  bool prepped = false;         // the caller has shifted the diagonal and reset logdet / info already (aug_prep)
+  bool noschur = false;         // the appended rows' trailing block is neither read nor written (cholesky.hip)
+  // batched (batch_logdet != nullptr, a batch of one included): `batch` problems of identical shape, problem g at
+  // a + g * batch_stride elements; every panel / update launch gets grid.y = batch
+  int batch = 1; int64_t batch_stride = 0; double* batch_logdet = nullptr; int* batch_info = nullptr;
+  // pieces of the matrix still landing (cholesky.hip need_columns), their events recorded on stream arrivals_on; the
+  // caller's stream is behind all of them when the factorisation returns
+  const smn_ctx::Arrival* arrivals = nullptr; size_t n_arrivals = 0; hipStream_t arrivals_on = nullptr;
+};
+int cholesky_padded(smn_ctx* ctx, const FactorCall& f);
 int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,
                   double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov, double* quad_h,
                   double* logdet_h, int* info_h);
@@ -110,7 +127,7 @@ int set_aug_rows(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, in
 int extract_posterior(smn_ctx* ctx, int dtype, const void* a, int64_t lda, int64_t aug0, int64_t t, int64_t c,
                       void* mean, void* cov, int64_t ldcov, double* quad_dev, bool publish = false);
 // set_aug_rows + absolute diagonal shift + reset of logdet / info in one launch (cholesky_padded then runs with
-// ctx->chol_prepped set and skips its own two)
+// FactorCall::prepped set and skips its own two)
 // (columns [col0, ncols) only, on stream st: the corner of a split build is prepped behind its own launch)
 // ridge_rel != 0: the shift is jitter_abs + ridge_rel * d_scal[1] / n_trace (the trace left there by the build: want_trace)
 int aug_prep(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, int64_t ncols, const void* y, int64_t n,

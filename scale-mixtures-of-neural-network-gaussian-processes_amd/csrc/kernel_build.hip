@@ -616,7 +616,7 @@ int split_tile_lists(smn_ctx* ctx, int T, int TB) {
 }
 
 template <typename T>
-int run_build_t(smn_ctx* ctx, const BuildCall& c) {
+int run_build_t(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
   LayerProg prog;
   SMN_TRY(make_prog(ctx, c.spec, &prog));
   if (c.rows1 % kTile || c.rows2 % kTile || c.kp % Mfma<T>::BK)
@@ -654,11 +654,10 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c) {
   hipLaunchKernelGGL(diag_tables_kernel<T>, dim3((unsigned)((c.rows1 + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
                      c.q1, c.rows1, prog, tab1, tlen, dg1, dgt1, progs_d, tab_bs);
   SMN_CHECK_LAUNCH(ctx);
-  ctx->trace_ready = false;
   if (c.want_trace && c.symmetric && c.exact_diag && c.nbatch == 0 && !c.shard && c.nv0 > 0) {
     hipLaunchKernelGGL(table_trace_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, dg1, c.nv0, ctx->d_scal + 1);
     SMN_CHECK_LAUNCH(ctx);
-    ctx->trace_ready = true;
+    if (out) out->trace = true;
   }
   T* tab2 = tab1;
   if (!c.symmetric) {
@@ -725,7 +724,6 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c) {
   size_t lds = MainTile<T>::LDS_BYTES;
   const size_t tab_lds = (size_t)(prog.nsets * 2 + 1) * 2 * kTile * sizeof(T);
   if (tab_lds > lds) lds = tab_lds;
-  ctx->corner_col = 0;
   if (c.split_corner > 0 && c.symmetric && !c.shard && c.nbatch == 0 && !c.mirror && ctx->stream_bulk && c.split_corner < tm) {
     // Two launches: everything but the bottom-right corner on the caller's stream, the corner on the bulk stream (CU-masked,
     // like the far updates it will be followed by) -- beside whatever the caller issues next on its own stream.
@@ -739,13 +737,11 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c) {
     // the corner starts BEHIND the first launch (it is meant to share the chip with the panel chain, not with the build)
     SMN_HIP(ctx, hipEventRecord(ctx->ev_s0, ctx->stream));
     SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream_bulk, ctx->ev_s0, 0));
+    SideJoin corner{ctx, ctx->stream_bulk, nullptr};   // (an error drains the first launch too: the bulk stream waits for it)
     a.tlist = ctx->tile_list + ctx->tile_list_na; a.tlist_n = ctx->tile_list_nb;
-    const int rc = launch_build<T>(ctx, a, (a.tlist_n + 7) / 8 * 8, lds, ntk, ctx->stream_bulk);
-    if (rc != SMN_OK) {   // the corner did not go out: nothing on the bulk stream to wait for, but the matrix is incomplete
-      (void)hipStreamSynchronize(ctx->stream);
-      return rc;
-    }
-    ctx->corner_col = (tm - TB) * kTile;
+    SMN_TRY(launch_build<T>(ctx, a, (a.tlist_n + 7) / 8 * 8, lds, ntk, ctx->stream_bulk));
+    corner.release();   // in flight: the caller's factorisation takes it as an arrival
+    out->corner_col = (tm - TB) * kTile;
     return SMN_OK;
   }
   return launch_build<T>(ctx, a, ntiles, lds, ntk);
@@ -846,8 +842,8 @@ int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, i
   return SMN_OK;
 }
 
-int run_build(smn_ctx* ctx, const BuildCall& c) {
-  return c.spec.dtype == SMN_F64 ? run_build_t<double>(ctx, c) : run_build_t<float>(ctx, c);
+int run_build(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
+  return c.spec.dtype == SMN_F64 ? run_build_t<double>(ctx, c, out) : run_build_t<float>(ctx, c, out);
 }
 
 // Size of the corner of a split build: the corner's tiles take about as long on the bulk stream's CUs as the first
