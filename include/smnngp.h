@@ -189,7 +189,18 @@ int smn_predict(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64
 
 /* ---- fused model-level calls (what the spax facade uses; nothing leaves the GPU but scalars) ----
  * smn_spr_loss: SPR.loss (spax/models.py:93-98): builds K(x,x) straight into the factorisation
- * workspace, adds eps_abs, factors, and returns the log-pdf of y (Gaussian df<=0 / Student-t). */
+ * workspace, adds eps_abs, factors, and returns the log-pdf of y (Gaussian df<=0 / Student-t).
+ *
+ * Gram cache.  The input Gram x x^T depends on x alone -- net, activation, depth, w_std, b_std, last_w_std, eps, df, scale and
+ * y all enter after it -- and a training loop calls this with the same x thousands of times.  From 2560 padded rows on the
+ * context therefore keeps its own padded copy of x and, from the second call on one x, the raw MFMA accumulators of the lower
+ * 128x128 tiles of x x^T; later calls run the layer recursion over those instead of the matrix product.  Whether x is
+ * unchanged is decided by CONTENT on every call, never by pointer: the padding pass compares all of x with the copy bit for
+ * bit (NaN and signed zeros included), so freeing and re-allocating x, or overwriting it in place, is seen.  The results are
+ * bit-identical to a call without the cache (same accumulators, same epilogue code).  The memory belongs to the context
+ * (freed by smn_ctx_destroy): copy + accumulators are 0.75 GB at n = 16384, d = 3072 in fp32 and 2.6 GB at n = 32768; above
+ * 8 GiB, or when the allocation fails, the call runs without the cache -- it never fails because of it.  Other entry points
+ * neither read nor write the cache. */
 int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
                  double w_std, double b_std, double last_w_std,
                  const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
@@ -227,6 +238,12 @@ int smn_debug_batch_bytes(smn_ctx* ctx, size_t bytes);
  * launch on the bulk stream, beside the first super-panel's panel chain (same tiles, same bits: only the order changes).
  * on = 0 switches that off (one launch, as every other entry point builds). */
 int smn_debug_split_build(smn_ctx* ctx, int on);
+/* on = 0 above also bypasses the Gram cache of smn_spr_loss (kept, not dropped): "one build launch with the chip to itself".
+ * Test hook: smn_debug_gram_cache(ctx, 0) bypasses the cache and frees it; 1 (the default) enables it again, cold.
+ * smn_gram_cache_stats: calls served from the cached accumulators (hits), calls that went through the cache and ran the
+ * matrix product (misses) since the context was created, and the bytes the cache holds now (any pointer may be NULL). */
+int smn_debug_gram_cache(smn_ctx* ctx, int on);
+int smn_gram_cache_stats(smn_ctx* ctx, int64_t* hits, int64_t* misses, size_t* bytes);
 /* Test hook: a panel workgroup of the factorisation carries up to max_passes groups of rows when there are more groups than CUs
  * (default 4; the later groups ride through the solve alone; same bits).  1 = one group per workgroup. */
 int smn_debug_panel_passes(smn_ctx* ctx, int max_passes);

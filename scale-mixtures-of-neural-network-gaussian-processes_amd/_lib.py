@@ -84,6 +84,8 @@ PROTOTYPES = {
                               _vp, _vp, _i64, _vp, _pd, _pd, _pi],
     "smn_debug_batch_bytes": [_vp, _sz],
     "smn_debug_split_build": [_vp, C.c_int],
+    "smn_debug_gram_cache": [_vp, C.c_int],
+    "smn_gram_cache_stats": [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)],
     "smn_debug_panel_passes": [_vp, C.c_int],
     "smn_mixture_nll": [_vp, _i, _i, _i64, _vp, _vp, _pd, _pd, _pi, _pd, _d, _d, _i64, _i, _i, _pd, _pd, _pd],
     "smn_comm_unique_id": [C.c_char_p],

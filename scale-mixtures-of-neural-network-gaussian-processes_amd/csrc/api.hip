@@ -311,12 +311,13 @@ extern "C" int smn_ctx_create(int device_id, smn_ctx** out) {
             hipEventCreate(&c->ev_t0) == hipSuccess && hipEventCreate(&c->ev_t1) == hipSuccess &&
             hipMalloc(reinterpret_cast<void**>(&c->d_scal), 64 * sizeof(double)) == hipSuccess &&
             hipMalloc(reinterpret_cast<void**>(&c->d_info), 16 * sizeof(int)) == hipSuccess &&
-            hipHostMalloc(reinterpret_cast<void**>(&c->h_mail), 64 * sizeof(double), hipHostMallocMapped) == hipSuccess &&
+            hipHostMalloc(reinterpret_cast<void**>(&c->h_mail), smn_ctx::kMailDoubles * sizeof(double), hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_mail), c->h_mail, 0) == hipSuccess;
   if (!ok) {
     smn_ctx_destroy(c);
     return SMN_EHIP;
   }
+  c->h_mail[smn_ctx::kMailGram] = 0.0;   // no generation reported yet
   *out = c;
   return SMN_OK;
 }
@@ -329,6 +330,8 @@ extern "C" int smn_ctx_destroy(smn_ctx* c) {
   if (c->stream_scatter) (void)hipStreamSynchronize(c->stream_scatter);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) smn_comm_destroy(c);
+  gram_cache_drop(c, true);
+  if (c->gram.word) (void)hipFree(c->gram.word);
   for (int i = 0; i < smn_ctx::kSlots; ++i)
     if (c->ws[i]) (void)hipFree(c->ws[i]);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);

@@ -43,8 +43,9 @@ struct smn_ctx {
   int* d_info = nullptr;      // 16 ints
   // pinned, device-mapped host mailbox: one tiny kernel publishes logdet / info / quadratic forms into it and the
   // host reads them after ONE stream synchronisation (three pageable device-to-host copies cost ~0.1 ms per call)
-  double* h_mail = nullptr;   // 64 doubles, host pointer
+  double* h_mail = nullptr;   // 64 doubles (results) + kMailGram.. (the Gram cache's {generation, changed}), host pointer
   double* d_mail = nullptr;   // the same memory as the device sees it
+  static constexpr int kMailGram = 64, kMailDoubles = 72;
   void* comm = nullptr;       // ncclComm_t when smn_comm_init was called
   int nranks = 1, rank = 0;
   // per-kernel timing (smn_profile_*): hipEvent pairs around launches, resolved on read
@@ -69,6 +70,21 @@ struct smn_ctx {
   std::unordered_map<const void*, size_t> max_lds;   // largest dynamic-LDS size already allowed per kernel (smn_allow_lds)
   bool lds_attrs_done[2] = {false, false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) issued for f32 / f64 kernels
   bool panel_leaf = true;            // panelr_kernel (register-resident 16x16 leaf) in the factorisation; env SMN_PANEL_LEAF=0: panel_kernel
+  // Gram cache of smn_spr_loss (kernel_build.hip gram_cache_plan / build_acc_kernel): the library's own padded copy of x and
+  // the raw MFMA accumulators of the lower tiles of x x^T, reused while x is unchanged.  Validity is decided by CONTENT (the
+  // padding pass compares every element of x with the copy, bit for bit, on every call), never by pointer.  Never handed out
+  // through smn_workspace.  kEmpty: nothing valid; kHaveCopy: xc holds the last call's x; kCached: g0 belongs to xc too.
+  struct GramCache {
+    enum { kEmpty = 0, kHaveCopy = 1, kCached = 2 };
+    int state = kEmpty;
+    int dtype = -1; int64_t n = 0, d = 0, kp = 0, n_total = 0;   // the key: no net, activation, depth or hyper-parameter in it
+    void* xc = nullptr; size_t xc_bytes = 0;
+    void* g0 = nullptr; size_t g0_bytes = 0;
+    unsigned* word = nullptr;   // device word: the generation number of the last call whose x differed from the copy
+    unsigned gen = 0;
+    bool enabled = true;        // smn_debug_gram_cache
+    int64_t hits = 0, misses = 0;
+  } gram;
   bool xcd_map = true;               // XCD-aware patch tile order of launches of 512 tiles and more (env SMN_XCD_MAP=0: linear order)
 };
 

@@ -58,13 +58,18 @@ double logpdf_from(double quad, double logdet, int64_t n, double df, double scal
 // diagonal for a relative ridge.
 int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, int64_t ldx, const void* xt,
               int64_t ldxt, int64_t d, int nbatch = 0, const double* bw = nullptr, const double* bb = nullptr,
-              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false) {
+              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false, const GramPlan* gram = nullptr) {
   const int64_t kp = k_pad(spec.dtype, d);
+  const int gmode = gram ? gram->mode : GRAM_CALL_NONE;
   void* xs = nullptr;
-  SMN_TRY(smn_workspace(ctx, 0, g.es * (size_t)kp * (size_t)g.n_total + sizeof(double) * (size_t)g.n_total, &xs));
+  // Gram cache (smn_spr_loss): the operand is the cache's own copy, not workspace slot 0 (which every other entry point rewrites)
+  if (gmode != GRAM_CALL_NONE) xs = gram->xc;
+  else SMN_TRY(smn_workspace(ctx, 0, g.es * (size_t)kp * (size_t)g.n_total + sizeof(double) * (size_t)g.n_total, &xs));
   double* q = static_cast<double*>(xs);
   char* xp = reinterpret_cast<char*>(q + g.n_total);
-  SMN_TRY(pad_rows(ctx, spec.dtype, x, g.n, ldx, d, xp, g.n_total, kp, q, g.n_pad, xt, g.t, ldxt));   // both blocks in one launch
+  const bool cmp = gmode == GRAM_CALL_STORE || gmode == GRAM_CALL_BOTH;   // the copy is an earlier call's: compare while padding
+  SMN_TRY(pad_rows(ctx, spec.dtype, x, g.n, ldx, d, xp, g.n_total, kp, q, g.n_pad, xt, g.t, ldxt,   // both blocks in one launch
+                   cmp ? ctx->gram.word : nullptr, cmp ? gram->gen : 0u));
   BuildCall c{};
   c.spec = spec;
   c.x1p = xp; c.ld1 = kp; c.rows1 = g.n_total; c.q1 = q;
@@ -79,6 +84,7 @@ int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, 
   // (not while pieces of a column-first exchange are still landing in this workspace)
   c.split_corner = (out && nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
   c.want_trace = (want_trace && nbatch == 0) ? 1 : 0;   // (relative ridge: the prep launch then carries the shift, aug_finish)
+  c.gram_mode = gmode; c.gram_gen = gram ? gram->gen : 0u;
   return run_build(ctx, c, out);
 }
 
@@ -592,10 +598,14 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built));
+  // the input Gram depends on x only: reused from the context's cache while x is unchanged (decided by content, on the device)
+  const GramPlan gram = gram_cache_plan(ctx, dtype, net, n, d, k_pad(dtype, d), g.n_total);
   double quad = 0.0, ld = 0.0;
   int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
+  int rc = aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, &gram);
+  if (rc == SMN_OK) rc = aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info);
+  gram_cache_settle(ctx, gram, rc);
+  if (rc != SMN_OK) return rc;
   if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
@@ -775,6 +785,22 @@ extern "C" int smn_debug_panel_passes(smn_ctx* ctx, int max_passes) {
 extern "C" int smn_debug_split_build(smn_ctx* ctx, int on) {
   if (!ctx) return SMN_EINVAL;
   ctx->split_build = on != 0;
+  return SMN_OK;
+}
+
+extern "C" int smn_debug_gram_cache(smn_ctx* ctx, int on) {
+  if (!ctx) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  ctx->gram.enabled = on != 0;
+  if (!ctx->gram.enabled) gram_cache_drop(ctx, true);
+  return SMN_OK;
+}
+
+extern "C" int smn_gram_cache_stats(smn_ctx* ctx, int64_t* hits, int64_t* misses, size_t* bytes) {
+  if (!ctx) return SMN_EINVAL;
+  if (hits) *hits = ctx->gram.hits;
+  if (misses) *misses = ctx->gram.misses;
+  if (bytes) *bytes = ctx->gram.xc_bytes + ctx->gram.g0_bytes;
   return SMN_OK;
 }
 

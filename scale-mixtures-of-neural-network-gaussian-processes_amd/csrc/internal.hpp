@@ -62,7 +62,23 @@ struct BuildCall {
   int split_corner;
   // want_trace: leave sum_i<nv0 K_ii (from the exact-diagonal table) in ctx->d_scal[1] (BuildOut::trace)
   int want_trace;
+  // Gram cache (smn_spr_loss; gram_cache_plan): GRAM_CALL_STORE = the fused build also leaves its raw accumulators in the
+  // context's cache when x equals the cached copy; GRAM_CALL_BOTH = the cached accumulators are valid for the cached copy: every
+  // launch goes out in both forms and the device word decides which of the two runs.  gram_gen = this call's generation number.
+  int gram_mode; unsigned gram_gen;
 };
+enum { GRAM_CALL_NONE = 0, GRAM_CALL_FIRST = 1, GRAM_CALL_STORE = 2, GRAM_CALL_BOTH = 3 };
+// What one smn_spr_loss call does with the context's Gram cache (kernel_build.hip).  plan never fails: anything in the way
+// (switched off, too small, too large, no memory, another key) ends in GRAM_CALL_NONE or a cold cache.  settle, after the
+// call's synchronisation, moves the state on what the device reported; rc != SMN_OK drops the cache.
+struct GramPlan {
+  int mode = GRAM_CALL_NONE;
+  unsigned gen = 0;
+  void* xc = nullptr;   // the cache's own padded copy ([n_total] doubles q, then [n_total, kp] elements): the build's operand
+};
+GramPlan gram_cache_plan(smn_ctx* ctx, int dtype, int net, int64_t n, int64_t d, int64_t kp, int64_t n_total);
+void gram_cache_settle(smn_ctx* ctx, const GramPlan& p, int rc);
+void gram_cache_drop(smn_ctx* ctx, bool free_memory);
 // What a build leaves behind for the factorisation after it (heads.hip aug_finish).
 struct BuildOut {
   int64_t corner_col = 0;   // first column of the corner of a split build, still being built on the bulk stream (0: none)
@@ -77,7 +93,9 @@ int split_corner_tiles(const smn_ctx* ctx, int64_t tiles);
 // augmented operand
 int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, int64_t d,
              void* dst, int64_t rows_pad, int64_t kp, double* q, int64_t rows_a = 0, const void* src2 = nullptr, int64_t n2 = 0,
-             int64_t lds2 = 0);
+             int64_t lds2 = 0, unsigned* changed = nullptr, unsigned gen = 0);
+// (changed != nullptr: the compare form -- dst holds an earlier call's copy; elements that differ bitwise are rewritten and
+// *changed = gen is stored by every lane that saw one)
 
 inline int64_t k_pad(int dtype, int64_t d) { return round_up(d, dtype == SMN_F64 ? 16 : 32); }
 

@@ -20,11 +20,18 @@ namespace {
 constexpr int64_t kHalfTileBuildMax = 600;   // f32 build launches of at most this many 128x128 tiles use 64-row half tiles
 
 // ------------------------------------------------------------------ prep kernels
-template <typename T>
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+// CMP (the Gram cache's change detection, smn_spr_loss): dst holds the copy an earlier call left.  Every element is compared
+// with it by BIT PATTERN (NaN, -0 and +0 are told apart like any other values) and only the elements that differ are written;
+// a lane that finds one stores this call's generation number into *changed (every writer stores the same value, and a word
+// left by an earlier call never equals this call's number: no reset pass).  q comes from the same summation either way.
+template <typename T, bool CMP = false>
 __global__ void pad_rows_kernel(const T* __restrict__ src, int64_t n, int64_t lds, int64_t d,
                                 T* __restrict__ dst, int64_t rows_pad, int64_t kp, double inv_d,
                                 double* __restrict__ q, int64_t rows_a = 0, const T* __restrict__ src2 = nullptr,
-                                int64_t n2 = 0, int64_t lds2 = 0) {
+                                int64_t n2 = 0, int64_t lds2 = 0, unsigned* __restrict__ changed = nullptr, unsigned gen = 0) {
   // one wave per padded row; rows_a > 0: the rows from rows_a on come from a second matrix (the appended block of an
   // augmented operand: one launch instead of two)
   const int lane = threadIdx.x & 63;
@@ -38,7 +45,14 @@ __global__ void pad_rows_kernel(const T* __restrict__ src, int64_t n, int64_t ld
   double s = 0.0;
   for (int64_t c = lane; c < kp; c += 64) {
     T v = (row < n && c < d) ? src[row * lds + c] : T(0);
-    dst[c] = v;
+    if (CMP) {
+      if (!same_bits(dst[c], v)) {
+        dst[c] = v;
+        *changed = gen;
+      }
+    } else {
+      dst[c] = v;
+    }
     s += (double)v * (double)v;
   }
 #pragma unroll
@@ -157,8 +171,25 @@ struct BuildArgs {
 
 // BM = 64 (f32 launches of few tiles: a rank's share of a sharded build, small kernels): two workgroups per 128x128 tile, 64
 // rows each -- at about one tile per CU a launch ends in a tail as long as a tile; halves end in half of it.
-template <typename T, int NET, int ACT, bool NTK, int BM = kTile>
-__global__ void __launch_bounds__(256, (sizeof(T) == 8 && NTK) ? 1 : (BM == 64 && !NTK ? 3 : 2)) build_kernel(BuildArgs<T> a) {
+// The Gram cache of smn_spr_loss (common.hpp GramCache): g0 holds the RAW MFMA accumulators of the lower tiles of x x^T, tile
+// (tr, tc) at element (tr (tr + 1) / 2 + tc) * 128 * 128, in ACCUMULATOR order: per (m, n) MFMA block one acc_t per lane, the
+// 256 lanes of the workgroup contiguous (a 64-row half tile takes its half of the tile's slot), so the store and the load are
+// whole-wave contiguous 16-byte (f64: 32-byte) accesses.  The values are what mainloop leaves in t.acc -- before inv_d,
+// before prog.pre -- so they serve every net, activation, depth and hyper-parameter.
+enum { GRAM_NONE = 0, GRAM_STORE = 1, GRAM_LOAD = 2 };
+template <typename T>
+struct GramArgs {
+  T* g0;
+  const unsigned* changed; unsigned gen;   // *changed == gen: this call's x differs from the cached copy (pad_rows_kernel<T, true>)
+  int skip_unchanged;                      // GRAM_STORE launched behind a GRAM_LOAD launch: it runs only when x has changed
+  double* mail;                            // pinned slots {gen, changed} the host reads after the call's synchronisation (or null)
+};
+
+// The one body of every build kernel.  GC = GRAM_STORE: the fused build that also leaves t.acc in g0 (store_acc);
+// GC = GRAM_LOAD: t.acc comes from g0 instead of the mainloop.  The epilogue -- prog.pre, the layer loop, prog.post, the exact
+// diagonal, the identity padding -- is the same text for all three, so the stored matrix has the same bits.
+template <typename T, int NET, int ACT, bool NTK, int BM, int GC>
+__device__ __forceinline__ void build_body(const BuildArgs<T>& a, T* __restrict__ g0, bool store_acc) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Tile = TileNT<T, BM, kTile, SMN_STAGES>;
   using M = typename Tile::M;
@@ -244,9 +275,27 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 8 && NTK) ? 1 : (BM == 64 &
     return o >= a.nv0 && !(a.nv1 > 0 && o < a.aug0 + a.nv1 && o + kTile > a.aug0);
   };
   const bool dead = a.store_mode == STORE_PAD_IDENTITY && (no_valid(row0) || no_valid(col0));
-  t.mainloop(a.x1 + row0 * a.ld1, a.ld1, a.x2 + col0 * a.ld2, a.ld2, dead ? 0 : a.kp, smem);
-
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  typename Tile::acc_t* gacc = nullptr;
+  if (GC != GRAM_NONE)
+    gacc = reinterpret_cast<typename Tile::acc_t*>(g0 + ((int64_t)tr * (tr + 1) / 2 + tc) * (kTile * kTile) + half * (BM * kTile)) + tid;
+  if (GC == GRAM_LOAD) {
+    if (!dead) {
+#pragma unroll
+      for (int m = 0; m < Tile::MT; ++m)
+#pragma unroll
+        for (int n = 0; n < Tile::NT; ++n) t.acc[m][n] = gacc[(m * Tile::NT + n) * 256];
+    }
+  } else {
+    t.mainloop(a.x1 + row0 * a.ld1, a.ld1, a.x2 + col0 * a.ld2, a.ld2, dead ? 0 : a.kp, smem);
+  }
+  if (GC == GRAM_STORE && store_acc && !dead) {
+#pragma unroll
+    for (int m = 0; m < Tile::MT; ++m)
+#pragma unroll
+      for (int n = 0; n < Tile::NT; ++n) gacc[(m * Tile::NT + n) * 256] = t.acc[m][n];
+  }
+
   const int wr = wave >> 1, wc = wave & 1;
   ElemProg<T, NET, ACT, NTK> prog(a.prog);
   const int nsets = a.prog.nsets;
@@ -352,6 +401,27 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 8 && NTK) ? 1 : (BM == 64 &
           if (NTK && out_t) out_t[gc * ldo + gr] = h;
         }
       }
+}
+
+template <typename T, int NET, int ACT, bool NTK, int BM = kTile>
+__global__ void __launch_bounds__(256, (sizeof(T) == 8 && NTK) ? 1 : (BM == 64 && !NTK ? 3 : 2)) build_kernel(BuildArgs<T> a) {
+  build_body<T, NET, ACT, NTK, BM, GRAM_NONE>(a, nullptr, false);
+}
+
+// The two cache forms of the NNGP build (smn_spr_loss only: NTK == false, the 128-row tile and the 64-row half tile).
+// GRAM_LOAD has no operand stages in LDS and no MFMA: it is bound by HBM and the vector pipe, so it asks for three workgroups
+// per CU (half tiles: four; f64: two -- four of the f32 128-row tile spill 52 bytes) where the fused build gets two or three.  Both leave at once when the device word says the other
+// form has this call's work: the host launches without knowing whether x has changed.
+template <typename T, int NET, int ACT, int BM, int GC>
+__global__ void __launch_bounds__(256, GC == GRAM_LOAD ? (sizeof(T) == 8 ? 2 : (BM == 64 ? 4 : 3)) : (BM == 64 ? 3 : 2))
+build_acc_kernel(BuildArgs<T> a, GramArgs<T> gc) {
+  const bool changed = *gc.changed == gc.gen;
+  if (gc.mail && blockIdx.x == 0 && threadIdx.x == 0) {
+    gc.mail[1] = changed ? 1.0 : 0.0;
+    gc.mail[0] = (double)gc.gen;
+  }
+  if (GC == GRAM_LOAD ? changed : (gc.skip_unchanged && !changed)) return;
+  build_body<T, NET, ACT, false, BM, GC>(a, gc.g0, !changed);
 }
 
 // ------------------------------------------------------------------ standalone recursion (HBM streaming)
@@ -586,6 +656,60 @@ int launch_build(smn_ctx* ctx, const BuildArgs<T>& a, int64_t ntiles, size_t lds
   return launch_build_n<T, NET_RESNET, ACT_ERF>(ctx, a, ntiles, lds, ntk, st);
 }
 
+// The cache forms of one launch (run_build_t: the whole build, or either half of a split build).  Tile size by the rule of
+// launch_build_n, so the store and the load of one key agree on the accumulator layout.
+template <typename T, int NET, int ACT, int BM, int GC>
+int launch_acc_t(smn_ctx* ctx, const BuildArgs<T>& a, const GramArgs<T>& gc, int64_t ntiles, hipStream_t st) {
+  auto kern = build_acc_kernel<T, NET, ACT, BM, GC>;
+  const size_t tab_lds = (size_t)(a.prog.nsets * 2 + 1) * 2 * kTile * sizeof(T);
+  const size_t lds = GC == GRAM_LOAD ? tab_lds : std::max<size_t>(TileNT<T, BM, kTile, SMN_STAGES>::LDS_BYTES, tab_lds);
+  if (BM == 64) ntiles *= 2;
+  SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+  {
+    ProfScope ps(ctx, PROF_BUILD, st);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds, st, a, gc);
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
+template <typename T, int NET, int ACT>
+int launch_acc_n(smn_ctx* ctx, const BuildArgs<T>& a, GramArgs<T> gc, int mode, int64_t ntiles, hipStream_t st) {
+  bool half_tiles = false;
+  if constexpr (sizeof(T) == 4) {
+    if (ntiles <= kHalfTileBuildMax && ntiles >= 64 && !a.tlist) {
+      ntiles = (ntiles + 7) / 8 * 8;
+      half_tiles = true;
+    }
+  }
+  if (mode == GRAM_CALL_BOTH) {   // the cached accumulators first; the fused form behind it runs only if x has changed
+    gc.skip_unchanged = 1;
+    if constexpr (sizeof(T) == 4) {
+      if (half_tiles) {
+        SMN_TRY((launch_acc_t<T, NET, ACT, 64, GRAM_LOAD>(ctx, a, gc, ntiles, st)));
+        return launch_acc_t<T, NET, ACT, 64, GRAM_STORE>(ctx, a, gc, ntiles, st);
+      }
+    }
+    SMN_TRY((launch_acc_t<T, NET, ACT, kTile, GRAM_LOAD>(ctx, a, gc, ntiles, st)));
+    return launch_acc_t<T, NET, ACT, kTile, GRAM_STORE>(ctx, a, gc, ntiles, st);
+  }
+  gc.skip_unchanged = 0;
+  if constexpr (sizeof(T) == 4) {
+    if (half_tiles) return launch_acc_t<T, NET, ACT, 64, GRAM_STORE>(ctx, a, gc, ntiles, st);
+  }
+  return launch_acc_t<T, NET, ACT, kTile, GRAM_STORE>(ctx, a, gc, ntiles, st);
+}
+
+template <typename T>
+int launch_acc(smn_ctx* ctx, const BuildArgs<T>& a, const GramArgs<T>& gc, int mode, int64_t ntiles, hipStream_t st) {
+  const int net = a.prog.net, act = a.prog.act;
+  if (net == NET_MLP && act == ACT_RELU) return launch_acc_n<T, NET_MLP, ACT_RELU>(ctx, a, gc, mode, ntiles, st);
+  if (net == NET_MLP && act == ACT_ERF) return launch_acc_n<T, NET_MLP, ACT_ERF>(ctx, a, gc, mode, ntiles, st);
+  if (net == NET_RESNET && act == ACT_RELU) return launch_acc_n<T, NET_RESNET, ACT_RELU>(ctx, a, gc, mode, ntiles, st);
+  if (net == NET_RESNET && act == ACT_ERF) return launch_acc_n<T, NET_RESNET, ACT_ERF>(ctx, a, gc, mode, ntiles, st);
+  return smn_fail(ctx, SMN_EINVAL, "Gram cache: bad net/act");
+}
+
 // Tile orders of a split build of T tile rows with a corner of TB: the XCD patch order of the whole triangle, filtered into
 // "everything but the corner" (na tiles, at tile_list) and "the corner" (nb tiles, behind them).  Cached per (T, TB).
 int split_tile_lists(smn_ctx* ctx, int T, int TB) {
@@ -724,6 +848,21 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
   size_t lds = MainTile<T>::LDS_BYTES;
   const size_t tab_lds = (size_t)(prog.nsets * 2 + 1) * 2 * kTile * sizeof(T);
   if (tab_lds > lds) lds = tab_lds;
+  // Gram cache (smn_spr_loss): the same launches -- one, or the two of a split build -- in the cache forms
+  const bool gram = c.gram_mode == GRAM_CALL_STORE || c.gram_mode == GRAM_CALL_BOTH;
+  GramArgs<T> gc{};
+  if (gram) {
+    if (ntk || !c.symmetric || c.shard || c.nbatch > 0 || c.mirror || !a.out_k || !ctx->gram.g0 || !ctx->gram.word)
+      return smn_fail(ctx, SMN_EINVAL, "run_build: the Gram cache serves the plain symmetric NNGP build only");
+    gc.g0 = static_cast<T*>(ctx->gram.g0); gc.changed = ctx->gram.word; gc.gen = c.gram_gen;
+    gc.mail = ctx->d_mail + smn_ctx::kMailGram;
+  }
+  auto launch = [&](int64_t nt, hipStream_t st) -> int {
+    if (!gram) return launch_build<T>(ctx, a, nt, lds, ntk, st);
+    const int rc = launch_acc<T>(ctx, a, gc, c.gram_mode, nt, st);
+    gc.mail = nullptr;   // (the first launch of the call reports; every launch would report the same)
+    return rc;
+  };
   if (c.split_corner > 0 && c.symmetric && !c.shard && c.nbatch == 0 && !c.mirror && ctx->stream_bulk && c.split_corner < tm) {
     // Two launches: everything but the bottom-right corner on the caller's stream, the corner on the bulk stream (CU-masked,
     // like the far updates it will be followed by) -- beside whatever the caller issues next on its own stream.
@@ -733,18 +872,18 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
     if (!ctx->ev_corner) SMN_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_corner, hipEventDisableTiming));
     a.use_map = 0;
     a.tlist = ctx->tile_list; a.tlist_n = ctx->tile_list_na;
-    SMN_TRY(launch_build<T>(ctx, a, (a.tlist_n + 7) / 8 * 8, lds, ntk, ctx->stream));
+    SMN_TRY(launch((a.tlist_n + 7) / 8 * 8, ctx->stream));
     // the corner starts BEHIND the first launch (it is meant to share the chip with the panel chain, not with the build)
     SMN_HIP(ctx, hipEventRecord(ctx->ev_s0, ctx->stream));
     SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream_bulk, ctx->ev_s0, 0));
     SideJoin corner{ctx, ctx->stream_bulk, nullptr};   // (an error drains the first launch too: the bulk stream waits for it)
     a.tlist = ctx->tile_list + ctx->tile_list_na; a.tlist_n = ctx->tile_list_nb;
-    SMN_TRY(launch_build<T>(ctx, a, (a.tlist_n + 7) / 8 * 8, lds, ntk, ctx->stream_bulk));
+    SMN_TRY(launch((a.tlist_n + 7) / 8 * 8, ctx->stream_bulk));
     corner.release();   // in flight: the caller's factorisation takes it as an arrival
     out->corner_col = (tm - TB) * kTile;
     return SMN_OK;
   }
-  return launch_build<T>(ctx, a, ntiles, lds, ntk);
+  return launch(ntiles, ctx->stream);
 }
 
 
@@ -827,19 +966,164 @@ int recursion_t(smn_ctx* ctx, const BuildSpec& spec, const void* k0, int64_t n1,
 }  // namespace
 
 int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, int64_t d,
-             void* dst, int64_t rows_pad, int64_t kp, double* q, int64_t rows_a, const void* src2, int64_t n2, int64_t lds2) {
+             void* dst, int64_t rows_pad, int64_t kp, double* q, int64_t rows_a, const void* src2, int64_t n2, int64_t lds2,
+             unsigned* changed, unsigned gen) {
   const unsigned blocks = (unsigned)((rows_pad + 3) / 4);
   ProfScope ps(ctx, PROF_PREP, ctx->stream);
+  if (changed) {   // compare form (Gram cache)
+    if (dtype == SMN_F64)
+      hipLaunchKernelGGL((pad_rows_kernel<double, true>), dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const double*>(src),
+                         n, lds, d, static_cast<double*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
+                         static_cast<const double*>(src2), n2, lds2, changed, gen);
+    else
+      hipLaunchKernelGGL((pad_rows_kernel<float, true>), dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const float*>(src),
+                         n, lds, d, static_cast<float*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
+                         static_cast<const float*>(src2), n2, lds2, changed, gen);
+    SMN_CHECK_LAUNCH(ctx);
+    return SMN_OK;
+  }
   if (dtype == SMN_F64)
     hipLaunchKernelGGL(pad_rows_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const double*>(src),
                        n, lds, d, static_cast<double*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                       static_cast<const double*>(src2), n2, lds2);
+                       static_cast<const double*>(src2), n2, lds2, static_cast<unsigned*>(nullptr), 0u);
   else
     hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const float*>(src),
                        n, lds, d, static_cast<float*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                       static_cast<const float*>(src2), n2, lds2);
+                       static_cast<const float*>(src2), n2, lds2, static_cast<unsigned*>(nullptr), 0u);
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
+}
+
+// ------------------------------------------------------------------ Gram cache of smn_spr_loss (common.hpp GramCache)
+// Which problems it serves.  Measured on a build with SMN_GRAM_MIN_ROWS=128, f32, 4-layer ReLU, ms per call, cache on / off
+// (profiles/r05_gram_cache_ab.txt):
+//     n      d = 64            d = 3072
+//     245    0.100 / 0.100 (d = 6)
+//    1024    0.258 / 0.259     0.271 / 0.463
+//    2048    0.460 / 0.460     0.471 / 0.646
+//    2500    0.571 / 0.572     0.585 / 0.762
+//    4096    1.006 / 1.015     1.025 / 1.475
+//    8192    3.310 / 3.339     3.380 / 4.997
+//   16384                      14.92 / 20.68
+// A hit never measured slower than the fused build, whatever kp: at kp = 64 the 64 KB of accumulators a tile reads cost what its
+// 64-deep product does, and the calls are launch- and chain-bound anyway.  So no time is lost at any (n_total, kp), and kp does
+// not enter the rule; what the threshold keeps out is memory and bookkeeping that buy nothing: the reference's own small
+// problems (N = 245 training steps, the N = 2048 grid search, d <= 64) gain 0.00 ms, and below 2560 rows the most that was
+// measured at all is 0.19 ms at d = 3072.  Those calls keep exactly the launches they had.
+#ifndef SMN_GRAM_MIN_ROWS
+#define SMN_GRAM_MIN_ROWS 2560   // (build-time, like SMN_STAGES: the sweep above ran on a variant built with 128)
+#endif
+constexpr int64_t kGramCacheMinRows = SMN_GRAM_MIN_ROWS;   // n_total (padded rows + the appended tile row) from which the cache is used
+// copy + accumulators.  N = 16384, d = 3072 f32: 0.20 + 0.55 GB; N = 32768 (C5's shape): 0.40 + 2.17 GB in f32, twice that in f64
+constexpr size_t kGramCacheMaxBytes = (size_t)8 << 30;
+
+static bool gram_cache_pays(int64_t n_total, int64_t kp) {
+  (void)kp;   // (see above: no kp measured a loss)
+  return n_total >= kGramCacheMinRows;
+}
+
+void gram_cache_drop(smn_ctx* ctx, bool free_memory) {
+  smn_ctx::GramCache& g = ctx->gram;
+  g.state = smn_ctx::GramCache::kEmpty;
+  if (!free_memory) return;
+  if (g.xc || g.g0) {   // nothing of an earlier call may still read them
+    if (ctx->stream_bulk) (void)hipStreamSynchronize(ctx->stream_bulk);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (g.xc) (void)hipFree(g.xc);
+  if (g.g0) (void)hipFree(g.g0);
+  g.xc = g.g0 = nullptr;
+  g.xc_bytes = g.g0_bytes = 0;
+  g.dtype = -1; g.n = g.d = g.kp = g.n_total = 0;
+}
+
+GramPlan gram_cache_plan(smn_ctx* ctx, int dtype, int net, int64_t n, int64_t d, int64_t kp, int64_t n_total) {
+  using GC = smn_ctx::GramCache;
+  GC& g = ctx->gram;
+  GramPlan p;
+  // bypassed, not dropped: switched off for one-launch builds (smn_debug_split_build(0) means "one build launch with the chip to
+  // itself"), while pieces of a column-first exchange are landing, and for nets the loss does not build with a layer map
+  if (!g.enabled || !ctx->split_build || !ctx->arrivals.empty()) return p;
+  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return p;
+  if (!gram_cache_pays(n_total, kp)) return p;
+  const size_t es = dtype_size(dtype);
+  const int64_t T = n_total / kTile;
+  const size_t xc_bytes = sizeof(double) * (size_t)n_total + es * (size_t)kp * (size_t)n_total;
+  const size_t g0_bytes = es * (size_t)(T * (T + 1) / 2) * (size_t)(kTile * kTile);
+  if (xc_bytes + g0_bytes > kGramCacheMaxBytes) {
+    gram_cache_drop(ctx, true);
+    return p;
+  }
+  auto alloc = [&](void** ptr, size_t* have, size_t want) -> bool {
+    if (*ptr && *have >= want) return true;
+    if (*ptr) {
+      if (ctx->stream_bulk) (void)hipStreamSynchronize(ctx->stream_bulk);
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)hipFree(*ptr);
+      *ptr = nullptr; *have = 0;
+    }
+    if (hipMalloc(ptr, want) != hipSuccess) {
+      (void)hipGetLastError();   // (not this call's error: it goes on without the cache)
+      *ptr = nullptr;
+      return false;
+    }
+    *have = want;
+    return true;
+  };
+  if (!g.word) {
+    if (hipMalloc(reinterpret_cast<void**>(&g.word), sizeof(unsigned)) != hipSuccess ||
+        hipMemset(g.word, 0, sizeof(unsigned)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (g.word) (void)hipFree(g.word);
+      g.word = nullptr;
+      return p;
+    }
+  }
+  if (g.dtype != dtype || g.n != n || g.d != d || g.kp != kp || g.n_total != n_total) {   // another key: start cold
+    g.state = GC::kEmpty;
+    g.dtype = dtype; g.n = n; g.d = d; g.kp = kp; g.n_total = n_total;
+  }
+  if (!alloc(&g.xc, &g.xc_bytes, xc_bytes)) {
+    gram_cache_drop(ctx, true);
+    return p;
+  }
+  if (g.state != GC::kEmpty && !alloc(&g.g0, &g.g0_bytes, g0_bytes)) {   // (the accumulators only once a second call has come)
+    gram_cache_drop(ctx, true);
+    return p;
+  }
+  if (++g.gen == 0) g.gen = 1;   // (0 is the word's initial value)
+  p.gen = g.gen;
+  p.xc = g.xc;
+  p.mode = g.state == GC::kEmpty ? GRAM_CALL_FIRST : (g.state == GC::kHaveCopy ? GRAM_CALL_STORE : GRAM_CALL_BOTH);
+  return p;
+}
+
+void gram_cache_settle(smn_ctx* ctx, const GramPlan& p, int rc) {
+  using GC = smn_ctx::GramCache;
+  GC& g = ctx->gram;
+  if (p.mode == GRAM_CALL_NONE) return;
+  if (rc != SMN_OK) {   // anything may be half written
+    g.state = GC::kEmpty;
+    return;
+  }
+  if (p.mode == GRAM_CALL_FIRST) {
+    g.state = GC::kHaveCopy;
+    ++g.misses;
+    return;
+  }
+  // the call has synchronised (fetch_mail): the build's first launch left {generation, changed} in the pinned slots
+  const double* m = ctx->h_mail + smn_ctx::kMailGram;
+  if (m[0] != (double)p.gen) {
+    g.state = GC::kEmpty;
+    return;
+  }
+  const bool changed = m[1] != 0.0;
+  if (p.mode == GRAM_CALL_BOTH && !changed) {
+    ++g.hits;
+    return;
+  }
+  ++g.misses;
+  g.state = changed ? GC::kHaveCopy : GC::kCached;   // changed: the copy holds the new x, the accumulators the old one's
 }
 
 int run_build(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
