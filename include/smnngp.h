@@ -287,6 +287,32 @@ int smn_spr_loss_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens
                       double eps_abs, double df, double scale,
                       double* quad_h, double* logdet_h, int* info_h, double terms_h[4]);
 
+/* ---- the same for the conv-NNGP kernel of smn_kernel_cnn (experiments/nt_kernels.py:34-45) ----
+ * What objax.GradValues(model.loss, vars) supplies to experiments/regression/train.py:61-67 when the kernel function is
+ * get_cnn_kernel.  terms_h[0..3] as above.  For an image pair the forward-mode state is three H x W maps (K, dK/dw^2, dK/db^2)
+ * carried through L x [Conv 3x3 SAME; act] on chip, one wave per pair of the lower triangle; the N^2 H W per-pixel entries are
+ * never stored.  x_d [n,H,W,C] row-major.
+ * smn_kernel_cnn_grad_terms: the contraction alone, the counterpart of smn_lml_grad_terms: neg_kinv_d [n,n] = -K~^-1 (lower
+ *   triangle read) and alpha_d [n] as smn_predict returns them for K_td = I, K_tt = 0; coef as above.
+ * smn_spr_cnn_loss_grad: everything from x and y: the forward build of the lower triangle straight into the factorisation
+ *   workspace, the factorisation with identity, the contraction; also quad = y^T K~^-1 y, logdet K~ and info.  On a non-PD
+ *   matrix info > 0, the terms are NaN and the call returns SMN_OK.
+ * Limit: H*W <= SMN_CNN_GRAD_MAX_PIXELS (three maps of 16 pixels per lane live in registers); larger images return
+ * SMN_ENOTSUP (smn_kernel_cnn itself goes to 4096 pixels).  b_std == 0 exactly: terms_h[1] is 0 and every value is finite -- a
+ * pixel whose 3x3 neighbourhood is all zero has zero variance, where the ReLU map is not differentiable; such pixels
+ * contribute no variance-side term. */
+#define SMN_CNN_GRAD_MAX_PIXELS 1024
+int smn_kernel_cnn_grad_terms(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                              double w_std, double b_std, double last_w_std,
+                              const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                              const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d,
+                              double coef, double terms_h[4]);
+int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                          double w_std, double b_std, double last_w_std,
+                          const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d,
+                          double eps_abs, double df, double scale,
+                          double* quad_h, double* logdet_h, int* info_h, double terms_h[4]);
+
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other
  * ranks by any host channel; every rank then calls smn_comm_init.  smn_allgather is an RCCL

@@ -13,32 +13,13 @@
 // an asin per pixel, pair and layer); no MFMA: there is no GEMM here to find.
 #include <type_traits>
 
+#include "cnn_pairs.hpp"
 #include "internal.hpp"
 #include "nngp_math.hpp"
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T rsqrt_any(T x);
-template <>
-__device__ __forceinline__ float rsqrt_any<float>(float x) { return __builtin_amdgcn_rsqf(x); }
-template <>
-__device__ __forceinline__ double rsqrt_any<double>(double x) { return 1.0 / sqrt(x); }
-template <typename T>
-__device__ __forceinline__ T rcp_any(T x);
-template <>
-__device__ __forceinline__ float rcp_any<float>(float x) { return __builtin_amdgcn_rcpf(x); }
-template <>
-__device__ __forceinline__ double rcp_any<double>(double x) {   // v_rcp_f64 + two Newton steps: full double precision
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-
-struct ConvProg {
-  int act, layers, H, W, C;
-  double w2, b2, lw2;
-};
+using namespace smn_cnn;
 
 // One workgroup per image: Q[img][l][p] = pre-activation variance of layer l at pixel p,
 // diag[img] = last_w^2 * mean_p q_L (the exact K(img, img)).
@@ -119,15 +100,6 @@ __global__ void __launch_bounds__(256) conv_q_kernel(const T* __restrict__ x, in
   if (threadIdx.x == 0) diag[img] = (T)(p.lw2 * red[0] / HW);
 }
 
-template <typename T>
-struct PairArgs {
-  const T* x1; const T* x2; const T* R1; const T* R2; const T* diag;
-  int64_t n1, n2; int symmetric, mirror;
-  ConvProg prog;
-  T* out; int64_t ldo; int64_t npairs;
-  int tile_bn;   // > 0: XCD-tiled pair order (below), tiles of tile_bn x 32 image pairs; 0: plain strided order
-};
-
 constexpr int kMaxPix = 64;   // pixels per lane (H*W <= 4096)
 
 // 4 waves per workgroup, each wave walks its own list of image pairs: the map of a wave is private to it,
@@ -150,58 +122,6 @@ constexpr int KB0 = SMN_CNN_K0_BATCH;
 #ifndef SMN_CNN_OCC_F64
 #define SMN_CNN_OCC_F64 4   // workgroups per CU the f64 form is compiled for (128 VGPRs, 9 spilled doubles; 2 / 3: -6 %)
 #endif
-// The pair list of one wave: plain strided order, or the XCD-tiled order described below.  next() is wave-uniform.
-template <typename T>
-struct PairWalk {
-  const PairArgs<T>& a;
-  bool tiled; int xcd, tidx; int64_t tiles_m, tiles_n, tn, tm, pr, step;
-  __device__ __forceinline__ PairWalk(const PairArgs<T>& a_, int wave) : a(a_) {
-    tiled = a.tile_bn > 0;
-    xcd = (int)(blockIdx.x & 7);
-    tidx = (int)(blockIdx.x >> 3) * 4 + wave;   // this wave's pair inside every tile of its XCD
-    tiles_m = (a.n2 + 31) / 32;
-    tiles_n = tiled ? (a.n1 + a.tile_bn - 1) / a.tile_bn : 0;
-    tn = 0;
-    tm = xcd - 8;
-    step = (int64_t)gridDim.x * 4;
-    pr = (int64_t)blockIdx.x * 4 + wave - step;
-  }
-  __device__ __forceinline__ int64_t row_tiles(int64_t r) const {   // tiles of tile row r that hold a wanted pair
-    if (!a.symmetric) return tiles_m;
-    const int64_t c = (r * a.tile_bn + a.tile_bn - 1) / 32 + 1;
-    return c < tiles_m ? c : tiles_m;
-  }
-  __device__ __forceinline__ bool next(int64_t& n, int64_t& m) {
-    if (tiled) {
-      // XCD x walks the lower (or all) tiles with (tn + tm) % 8 == x, row by row: dealt round-robin inside a tile row
-      // with the offset rotating from row to row, so every XCD gets the same share of the triangle
-      for (;;) {
-        tm += 8;
-        while (tn < tiles_n && tm >= row_tiles(tn)) {
-          ++tn;
-          tm = (xcd - tn) & 7;
-        }
-        if (tn >= tiles_n) return false;
-        n = tn * a.tile_bn + (tidx >> 5);
-        m = tm * 32 + (tidx & 31);
-        if (n < a.n1 && m < a.n2 && !(a.symmetric && m > n)) return true;
-      }
-    }
-    pr += step;
-    if (pr >= a.npairs) return false;
-    if (a.symmetric) {
-      int64_t r = (int64_t)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
-      while ((r + 1) * (r + 2) / 2 <= pr) ++r;
-      while (r * (r + 1) / 2 > pr) --r;
-      n = r;
-      m = pr - r * (r + 1) / 2;
-    } else {
-      n = pr / a.n2;
-      m = pr % a.n2;
-    }
-    return true;
-  }
-};
 
 template <typename T>
 constexpr int pair_occ(int np, bool exact) {   // workgroups per CU a form is compiled for (and launched at)

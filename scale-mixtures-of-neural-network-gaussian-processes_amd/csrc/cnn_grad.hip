@@ -1,0 +1,469 @@
+// cnn_grad.hip — analytic hyper-parameter gradients of the log-marginal likelihood for the conv-NNGP kernel of cnn.hip
+// (experiments/nt_kernels.py:34-45), the conv counterpart of grad.hip: what objax.GradValues(model.loss, vars) supplies to
+// experiments/regression/train.py:61-67 when the kernel is get_cnn_kernel.
+//
+// With K~ = K(w, b, lw) + eps I, alpha = K~^-1 y and G = coef * alpha alpha^T - K~^-1 (grad.hip:1-18) the four terms are
+// sum_nm G_nm dK~_nm/d theta.  For one image pair (n, m) the forward-mode state is three H x W maps (K, Kw = dK/dw^2,
+// Kb = dK/db^2), starting from (K0, 0, 0); per image the diagonal has (q, qw, qb), starting from (q0, 0, 0).  Per layer
+// (box = 3x3 zero-padded box sum):
+//   Conv:  Kw <- box(K)/9 + w^2 box(Kw)/9     Kb <- 1 + w^2 box(Kb)/9     K <- w^2 box(K)/9 + b^2      (same for q, qw, qb)
+//   Act:   (o, phi_A, phi_qi, phi_qj) per pixel (grad.hip:13-18);  Kw <- phi_A Kw + phi_qi qw_n + phi_qj qw_m,  Kb likewise
+//          with qb;  K <- o.  Diagonal: qw <- (d o / d q) qw, qb <- (d o / d q) qb, q <- o.
+//   Flatten + Dense:  K_nm = lw^2 mean K,  dK_nm/dw^2 = lw^2 mean Kw,  dK_nm/db^2 = lw^2 mean Kb.
+//
+// Per-image tables.  Both activations factor the same way: with ra = 1/sqrt(q) (ReLU; 0 where q <= 0) or 1/sqrt(1 + 2q) (erf)
+//   ReLU:  phi_qi = sqrt(1 - c^2) sqrt(q_i q_j) / (4 pi q_i) = [sqrt(1 - c^2) / (4 pi ra_i ra_j)] * ra_i^2
+//   Erf:   phi_qi = -(2/pi) s / (sqrt(1 - s^2) (1 + 2 q_i))  = [-(2/pi) s / sqrt(1 - s^2)]       * ra_i^2
+// so phi_qi qw_n + phi_qj qw_m = [pair factor] * (ra_n^2 qw_n + ra_m^2 qw_m): THREE fields per image, layer and pixel --
+// ra, ra^2 qw, ra^2 qb -- where grad.hip keeps five per row.  The forward pair kernel is bound by streaming its one table
+// out of L2 (cnn.hip), so the fewer the better; sqrt(q_i q_j) is 1 / (ra_i ra_j), one reciprocal, as in the forward kernel.
+// A pixel whose variance is exactly zero (an all-zero neighbourhood with b_std = 0) has ra = 0 and so contributes no q-side
+// term: the map is not differentiable there, and 0 * inf must not reach the sums.
+#include <algorithm>
+#include <cmath>
+
+#include "cnn_pairs.hpp"
+#include "internal.hpp"
+#include "nngp_math.hpp"
+
+namespace {
+
+using namespace smn_cnn;
+
+constexpr int kCgFields = 3;   // ra, ra^2 dq/dw^2, ra^2 dq/db^2
+constexpr int kCgMaxHW = SMN_CNN_GRAD_MAX_PIXELS;
+
+// One workgroup per image (fp64 arithmetic): tab[((img * L + l) * 3 + f) * HW + p] for the pair kernel, and
+// dexact[img * 3 + {0, 1, 2}] = the exact K(img, img), dK/dw^2, dK/db^2 (last Dense included).
+template <typename T>
+__global__ void __launch_bounds__(256) cgrad_q_kernel(const T* __restrict__ x, ConvProg p, T* __restrict__ tab,
+                                                      double* __restrict__ dexact) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW;
+  double* maps = reinterpret_cast<double*>(smem);   // (q, qw, qb) x ping-pong: six padded maps
+  const int64_t img = blockIdx.x;
+  for (int i = threadIdx.x; i < 6 * PSZ; i += blockDim.x) maps[i] = 0.0;
+  __syncthreads();
+  for (int px = threadIdx.x; px < HW; px += blockDim.x) {
+    const T* xp = x + (img * HW + px) * p.C;
+    double s = 0.0;
+    for (int c = 0; c < p.C; ++c) s += (double)xp[c] * (double)xp[c];
+    maps[(px / W + 1) * PW + px % W + 1] = s / p.C;
+  }
+  __syncthreads();
+  double* cur = maps;
+  double* nxt = maps + 3 * PSZ;
+  for (int l = 0; l < p.layers; ++l) {
+    for (int px = threadIdx.x; px < HW; px += blockDim.x) {
+      const int h = px / W, w = px % W;
+      double bs[3];
+#pragma unroll
+      for (int f = 0; f < 3; ++f) {
+        const double* c = cur + f * PSZ + h * PW + w;   // top-left of the 3x3 window in the padded map
+        bs[f] = c[0] + c[1] + c[2] + c[PW] + c[PW + 1] + c[PW + 2] + c[2 * PW] + c[2 * PW + 1] + c[2 * PW + 2];
+      }
+      const double qt = p.w2 * bs[0] / 9.0 + p.b2;
+      const double qw = bs[0] / 9.0 + p.w2 * bs[1] / 9.0;
+      const double qb = 1.0 + p.w2 * bs[2] / 9.0;
+      double ra, ra2, qa, dq;
+      if (p.act == 0) {
+        ra = qt > 0.0 ? 1.0 / sqrt(qt) : 0.0;
+        ra2 = qt > 0.0 ? 1.0 / qt : 0.0;
+        qa = 0.5 * qt;
+        dq = 0.5;
+      } else {
+        const double t = 1.0 + 2.0 * qt;
+        ra = 1.0 / sqrt(t);
+        ra2 = 1.0 / t;
+        qa = (2.0 / nngp::kPi) * asin(2.0 * qt / t);
+        dq = (4.0 / nngp::kPi) / (t * sqrt(1.0 + 4.0 * qt));   // d/dq (2/pi) asin(2q / (1 + 2q))
+      }
+      T* t = tab + ((img * p.layers + l) * kCgFields) * HW + px;
+      t[0] = (T)ra;
+      t[HW] = (T)(ra2 * qw);
+      t[2 * HW] = (T)(ra2 * qb);
+      const int o = (h + 1) * PW + w + 1;
+      nxt[o] = qa;
+      nxt[PSZ + o] = dq * qw;
+      nxt[2 * PSZ + o] = dq * qb;
+    }
+    __syncthreads();
+    double* t = cur; cur = nxt; nxt = t;
+  }
+  // means over pixels (block tree reduction behind the maps)
+  double* red = maps + 6 * PSZ;   // 3 x 256 doubles
+  for (int f = 0; f < 3; ++f) {
+    double s = 0.0;
+    for (int px = threadIdx.x; px < HW; px += blockDim.x) s += cur[f * PSZ + (px / W + 1) * PW + px % W + 1];
+    red[f * 256 + threadIdx.x] = s;
+  }
+  __syncthreads();
+  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o)
+      for (int f = 0; f < 3; ++f) red[f * 256 + threadIdx.x] += red[f * 256 + threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) dexact[img * 3 + threadIdx.x] = p.lw2 * red[threadIdx.x * 256] / HW;
+}
+
+template <typename T>
+struct CGradArgs {
+  PairArgs<T> pa;          // x1 = x2 = the images, R1 = R2 = the tables above, the pair order; diag / out are not used
+  const double* dexact;    // [n][3]
+  const T* nkinv; int64_t ldki;   // -K~^-1 (lower triangle read)
+  const T* alpha;
+  double coef;
+  double* partial;         // [gridDim.x * 4 waves][4]
+};
+
+// Workgroups per CU a form is compiled for.  The state is three values per owned pixel: 16 pixels in fp64 are 96 VGPRs
+// before any temporary, so the 1024-pixel form takes the 256 registers of two waves per SIMD; the small forms fit in 128.
+#ifndef SMN_CGRAD_OCC16
+#define SMN_CGRAD_OCC16 2
+#endif
+#ifndef SMN_CGRAD_OCC4
+#define SMN_CGRAD_OCC4 4
+#endif
+template <typename T>
+constexpr int cgrad_occ(int np) {
+  return np <= 4 ? SMN_CGRAD_OCC4 : SMN_CGRAD_OCC16;
+}
+
+// The general LDS-map form of conv_pair_kernel (cnn.hip) carrying (K, Kw, Kb): one wave per image pair of the lower triangle,
+// PairWalk order, ONE padded map per wave.  A layer publishes K, reads its nine taps into the registers that held K, then
+// reuses the map for Kw and for Kb -- LDS operations of one wave execute in order, which is what the forward kernel relies
+// on -- so the LDS footprint is the forward kernel's.  Per-element arithmetic in T, the four sums in double, one partial per wave.
+template <typename T, int ACT, int NP, bool EXACT>
+__global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGradArgs<T> g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const PairArgs<T>& a = g.pa;
+  const ConvProg& p = a.prog;
+  const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int MSZ = PSZ + 2 * PW + 3;                     // map + the dummy slot's neighbourhood
+  T* map = reinterpret_cast<T*>(smem) + (size_t)wave * MSZ;
+  for (int i = lane; i < MSZ; i += 64) map[i] = T(0);   // halo stays zero for the whole kernel
+  int off_tab[EXACT ? 1 : NP];
+  const int off0 = (lane / W + 1) * PW + lane % W + 1, rstep = (64 / W) * PW;
+  if (!EXACT) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int px = lane + 64 * i;
+      off_tab[i] = px < HW ? (px / W + 1) * PW + px % W + 1 : PSZ + PW + 1;
+    }
+  }
+  // vlane / voff0 are `lane` and `off0` re-read as opaque values once per pair and once per box sum: the per-pixel addresses
+  // derived from them are then recomputed where they are used (an integer add each) instead of staying alive -- about a
+  // hundred registers for 16 pixels -- beside the state for the whole kernel
+  int vlane = lane, voff0 = off0;
+  auto off = [&](int i) { return EXACT ? voff0 + i * rstep : off_tab[EXACT ? 0 : i]; };
+  auto pix = [&](int i) { return EXACT ? vlane + 64 * i : min(vlane + 64 * i, HW - 1); };   // pixel a lane loads from
+  // v <- 3x3 box sum of v: publish, then nine taps per owned pixel (the previous tap reads were issued before the publish)
+  auto box = [&](T (&v)[NP]) {
+    asm volatile("" : "+v"(voff0));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < NP; ++i) map[off(i)] = v[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // (the row stride is re-read as a scalar here: left loop-invariant, the compiler keeps three row addresses per owned pixel
+    // alive across the whole layer loop -- 48 registers for 16 pixels -- and spills the state instead)
+    int pw = PW;
+    asm volatile("" : "+s"(pw));
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const T* r1 = map + off(i) - 1;          // left neighbour; the rows above and below are one add each, the taps immediates
+      const T* r0 = r1 - pw;
+      const T* r2 = r1 + pw;
+      v[i] = ((r0[0] + r0[1]) + (r0[2] + r1[0])) + ((r1[1] + r1[2]) + (r2[0] + r2[1])) + r2[2];
+      if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // 36 taps in flight, not 144
+    }
+  };
+  const T w2_9 = (T)(p.w2 / 9.0), b2 = (T)p.b2, inv9 = (T)(1.0 / 9.0);
+  const T inv_c = (T)(1.0 / p.C), lw2_hw = (T)(p.lw2 / HW), coef = (T)g.coef;
+  constexpr int KB = NP < 4 ? NP : 4;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum G dK/dw^2, sum G dK/db^2, sum G K, tr G (wave-uniform)
+  PairWalk<T> walk(a, wave);
+  int64_t n, m;
+  while (walk.next(n, m)) {
+    const T* xa = a.x1 + n * HW * p.C;
+    const T* xb = a.x2 + m * HW * p.C;
+    asm volatile("" : "+v"(vlane));
+    T k[NP], kw[NP], kb[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) k[i] = kw[i] = kb[i] = T(0);
+    for (int c = 0; c < p.C; ++c) {
+#pragma unroll
+      for (int i0 = 0; i0 < NP; i0 += KB) {
+        T va[KB], vb[KB];
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+          va[j] = xa[pix(i0 + j) * p.C + c];
+          vb[j] = xb[pix(i0 + j) * p.C + c];
+        }
+#pragma unroll
+        for (int j = 0; j < KB; ++j) k[i0 + j] = fma(va[j], vb[j], k[i0 + j]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) k[i] *= inv_c;
+    for (int l = 0; l < p.layers; ++l) {
+      const T* t1 = a.R1 + (n * p.layers + l) * kCgFields * HW;
+      const T* t2 = a.R2 + (m * p.layers + l) * kCgFields * HW;
+      box(k);
+      if (l > 0) {   // in the first layer Kw = Kb = 0 and so are their box sums
+        box(kw);
+        box(kb);
+      }
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int px = pix(i);
+        const T rr = t1[px] * t2[px];
+        const T uw = t1[HW + px] + t2[HW + px], ub = t1[2 * HW + px] + t2[2 * HW + px];
+        const T kt = fma(w2_9, k[i], b2);
+        const T kwt = fma(w2_9, kw[i], k[i] * inv9);
+        const T kbt = fma(w2_9, kb[i], T(1));
+        if (ACT == 0) {
+          const T c = nngp::clamp1(kt * rr);
+          const T ca = fabs(c);
+          const T as = nngp::asin_abs(ca, c * c);
+          const T s1 = nngp::fast_sqrt((T(1) - ca) * (T(1) + ca));
+          const T pm = T(nngp::kPi / 2) + copysign(as, c);
+          const T sp = rr > T(0) ? rcp_any<T>(rr) : T(0);           // sqrt(q_n q_m)
+          const T dA = pm * T(1.0 / (2.0 * nngp::kPi));
+          const T tq = s1 * sp * T(1.0 / (4.0 * nngp::kPi));
+          k[i] = sp * fma(pm, c, s1) * T(1.0 / (2.0 * nngp::kPi));
+          kw[i] = fma(dA, kwt, tq * uw);
+          kb[i] = fma(dA, kbt, tq * ub);
+        } else {
+          const T sv = nngp::clamp1(T(2) * kt * rr);
+          const T sa = fabs(sv);
+          const T as = nngp::asin_abs(sa, sv * sv);
+          const T rden = nngp::fast_rsqrt(fmax((T(1) - sa) * (T(1) + sa), sizeof(T) == 8 ? T(1e-300) : T(1e-30)));
+          const T dA = T(4.0 / nngp::kPi) * rr * rden;
+          const T tq = T(-2.0 / nngp::kPi) * sv * rden;
+          k[i] = T(2.0 / nngp::kPi) * copysign(as, sv);
+          kw[i] = fma(dA, kwt, tq * uw);
+          kb[i] = fma(dA, kbt, tq * ub);
+        }
+        // the table loads of four pixels in flight at a time: hoisted for all sixteen they cost more registers than the state
+        if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // Flatten (mean over pixels) + last Dense, then the contraction with G_nm
+    T s[3] = {T(0), T(0), T(0)};
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const bool ok = EXACT || lane + 64 * i < HW;
+      s[0] += ok ? kw[i] : T(0);
+      s[1] += ok ? kb[i] : T(0);
+      s[2] += ok ? k[i] : T(0);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_xor(s[q], o);
+      s[q] *= lw2_hw;
+    }
+    const bool dg = n == m;
+    if (dg) {   // the exact per-image values, as cnn.hip does for K(n, n)
+      s[0] = (T)g.dexact[n * 3 + 1];
+      s[1] = (T)g.dexact[n * 3 + 2];
+      s[2] = (T)g.dexact[n * 3 + 0];
+    }
+    const T gv = fma(coef * g.alpha[n], g.alpha[m], g.nkinv[n * g.ldki + m]);
+    const T gm = dg ? gv : T(2) * gv;   // the upper triangle is the mirror image
+    acc[0] += (double)(gm * s[0]);
+    acc[1] += (double)(gm * s[1]);
+    acc[2] += (double)(gm * s[2]);
+    if (dg) acc[3] += (double)gv;
+  }
+  if (lane == 0) {
+    double* out = g.partial + ((int64_t)blockIdx.x * 4 + wave) * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[q] = acc[q];
+  }
+}
+
+// Second stage: fixed-order sum of the per-wave partials (bitwise reproducible), as grad_reduce_kernel.
+__global__ void __launch_bounds__(256) cgrad_reduce_kernel(const double* __restrict__ partial, int64_t count,
+                                                           double* __restrict__ out) {
+  __shared__ double red[4][4];
+  const int tid = threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t t = tid; t < count; t += 256)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] += partial[t * 4 + q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    double v = acc[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) red[q][tid >> 6] = v;
+  }
+  __syncthreads();
+  if (tid < 4) out[tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+// Launch one form.  Tiled pair order as the forward kernel's launcher: from 256 pairs per resident workgroup on, the grid is
+// exactly the resident set g and the tile is (g / 64) x 32 image pairs, one pair per wave.  The tile height follows from the
+// occupancy this kernel compiles to (2 workgroups per CU for the 1024-pixel forms: 8 rows where the forward kernel has 16),
+// not from the forward kernel's.  *blocks_io: the grid asked for / launched (at most max_blocks, the size of the partials).
+template <typename T, typename K>
+int cgrad_launch_form(smn_ctx* ctx, K kern, CGradArgs<T> g, int64_t* blocks_io, int64_t max_blocks, size_t lds) {
+  SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) == hipSuccess && per_cu > 0) {
+    const int64_t r = (int64_t)ctx->num_cu * per_cu / 64 * 64;
+    if (r >= 64 && r <= max_blocks && g.pa.npairs >= 64 * 8 * (r / 8) * 4) {
+      *blocks_io = r;
+      g.pa.tile_bn = (int)(r / 64);
+    }
+  }
+  ProfScope ps(ctx, PROF_MISC, ctx->stream);
+  hipLaunchKernelGGL(kern, dim3((unsigned)*blocks_io), dim3(256), lds, ctx->stream, g);
+  return SMN_OK;
+}
+
+template <typename T, int ACT>
+int cgrad_launch(smn_ctx* ctx, const CGradArgs<T>& g, int64_t* blocks_io, int64_t max_blocks, size_t lds, int64_t hw) {
+  const bool w64 = 64 % g.pa.prog.W == 0;
+#define CGRAD_CASE(NP)                                                                                               \
+  if (hw <= 64 * NP) {                                                                                               \
+    if (hw == 64 * NP && w64)                                                                                        \
+      return cgrad_launch_form<T>(ctx, cgrad_pair_kernel<T, ACT, NP, true>, g, blocks_io, max_blocks, lds);          \
+    return cgrad_launch_form<T>(ctx, cgrad_pair_kernel<T, ACT, NP, false>, g, blocks_io, max_blocks, lds);           \
+  }
+  CGRAD_CASE(1)
+  CGRAD_CASE(4)
+  CGRAD_CASE(16)
+#undef CGRAD_CASE
+  return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms: H*W > %d", kCgMaxHW);
+}
+
+template <typename T>
+int cgrad_terms_t(smn_ctx* ctx, int act, int layers, double w_std, double b_std, double last_w_std, const void* x_d,
+                  int64_t n, int64_t H, int64_t W, int64_t C, const void* nkinv, int64_t ldki, const void* alpha, double coef,
+                  double out_h[4]) {
+  ConvProg p{act, layers, (int)H, (int)W, (int)C, w_std * w_std, b_std * b_std, last_w_std * last_w_std};
+  const int64_t HW = H * W;
+  const size_t psz = (size_t)(H + 2) * (W + 2);
+  const size_t lds_q = (6 * psz + 3 * 256) * sizeof(double);
+  const size_t lds_p = 4 * (psz + 2 * (W + 2) + 3) * sizeof(T);   // one padded map (+ dummy slot) per wave
+  if (lds_q > 160 * 1024 || lds_p > 160 * 1024)
+    return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms: image %lldx%lld too large for the on-chip maps", (long long)H,
+                    (long long)W);
+  const int64_t npairs = n * (n + 1) / 2;
+  int64_t blocks = (npairs + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  const int64_t max_blocks = std::max<int64_t>(256 * 8, (int64_t)ctx->num_cu * 8);
+  // doubles first (8-byte aligned): dexact [n][3], partial [max_blocks * 4][4], out [4]; then the tables [n][L][3][HW] in T
+  const size_t nd = (size_t)n * 3 + (size_t)max_blocks * 16 + 4;
+  const size_t ntab = (size_t)n * (size_t)(layers > 0 ? layers : 1) * kCgFields * (size_t)HW;
+  void* wsv = nullptr;
+  SMN_TRY(smn_workspace(ctx, 4, sizeof(double) * nd + sizeof(T) * ntab, &wsv));
+  double* dexact = static_cast<double*>(wsv);
+  double* partial = dexact + (size_t)n * 3;
+  double* out_d = partial + (size_t)max_blocks * 16;
+  T* tab = reinterpret_cast<T*>(out_d + 4);
+  {
+    ProfScope ps(ctx, PROF_PREP, ctx->stream);
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(cgrad_q_kernel<T>), lds_q));
+    hipLaunchKernelGGL(cgrad_q_kernel<T>, dim3((unsigned)n), dim3(256), lds_q, ctx->stream, static_cast<const T*>(x_d), p, tab,
+                       dexact);
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  CGradArgs<T> g;
+  g.pa.x1 = g.pa.x2 = static_cast<const T*>(x_d);
+  g.pa.R1 = g.pa.R2 = tab;
+  g.pa.diag = nullptr;
+  g.pa.n1 = g.pa.n2 = n;
+  g.pa.symmetric = 1; g.pa.mirror = 0;
+  g.pa.prog = p;
+  g.pa.out = nullptr; g.pa.ldo = 0;
+  g.pa.npairs = npairs;
+  g.pa.tile_bn = 0;
+  g.dexact = dexact;
+  g.nkinv = static_cast<const T*>(nkinv); g.ldki = ldki;
+  g.alpha = static_cast<const T*>(alpha);
+  g.coef = coef;
+  g.partial = partial;
+  SMN_TRY(act == SMN_ACT_RELU ? (cgrad_launch<T, 0>(ctx, g, &blocks, max_blocks, lds_p, HW))
+                              : (cgrad_launch<T, 1>(ctx, g, &blocks, max_blocks, lds_p, HW)));
+  SMN_CHECK_LAUNCH(ctx);
+  hipLaunchKernelGGL(cgrad_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, partial, blocks * 4, out_d);
+  SMN_CHECK_LAUNCH(ctx);
+  double s[4];
+  SMN_HIP(ctx, hipMemcpyAsync(s, out_d, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
+  SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  out_h[0] = s[0] * 2.0 * w_std;                          // d/dw_std = 2 w d/dw^2
+  out_h[1] = b_std == 0.0 ? 0.0 : s[1] * 2.0 * b_std;     // (the sum is finite by construction; 0 stays an exact 0)
+  out_h[2] = s[2] * 2.0 / last_w_std;                     // K = lw^2 K_L  =>  dK/dlw = 2 K / lw
+  out_h[3] = s[3];                                        // dK~/deps = I
+  return SMN_OK;
+}
+
+int cgrad_check(smn_ctx* ctx, const char* who, int dtype, int act, int num_hiddens, double last_w_std, int64_t n, int64_t H,
+                int64_t W, int64_t C) {
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype %d", dtype);
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
+  if (n <= 0 || H <= 0 || W <= 0 || C <= 0 || num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  if (!(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: bad hyper-parameters", who);
+  if (H * W > kCgMaxHW)
+    return smn_fail(ctx, SMN_ENOTSUP, "%s: H*W = %lld > %d (SMN_CNN_GRAD_MAX_PIXELS)", who, (long long)(H * W), kCgMaxHW);
+  return SMN_OK;
+}
+
+}  // namespace
+
+extern "C" int smn_kernel_cnn_grad_terms(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                                         double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                                         const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, double coef,
+                                         double terms_h[4]) {
+  if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms", dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (ldkinv < n) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms: bad sizes");
+  if (dtype == SMN_F64)
+    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                                 coef, terms_h);
+  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                              coef, terms_h);
+}
+
+// Fused: the forward conv build of the lower triangle straight into the factorisation workspace (smn_kernel_cnn), the
+// factorisation with identity (heads.hip: alpha, -K~^-1, quad, logdet), then the contraction above.
+extern "C" int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                                     double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                                     const void* y_d, double eps_abs, double df, double scale, double* quad_h,
+                                     double* logdet_h, int* info_h, double terms_h[4]) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, "smn_spr_cnn_loss_grad", dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad: scale must be > 0");
+  const size_t es = dtype_size(dtype);
+  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
+  void* post = nullptr;
+  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n), &post));
+  void* ninv = post;
+  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
+  double quad = 0.0, logdet = 0.0;
+  int info = 0;
+  const KernelInto build = [&](void* k_d, int64_t ldk) {
+    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER,
+                          k_d, ldk);
+  };
+  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, &quad, &logdet, &info));
+  if (quad_h) *quad_h = quad;
+  if (logdet_h) *logdet_h = logdet;
+  if (info_h) *info_h = info;
+  if (info != 0) {
+    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
+    return SMN_OK;
+  }
+  double coef = 1.0;
+  if (df > 0.0) coef = (df + (double)n) / ((df + quad / scale) * scale);
+  return smn_kernel_cnn_grad_terms(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, alpha,
+                                   coef, terms_h);
+}

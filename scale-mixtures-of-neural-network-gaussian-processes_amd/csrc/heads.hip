@@ -502,16 +502,15 @@ __global__ void identity_block_kernel(T* __restrict__ a, int64_t lda, int64_t n)
 //   are not (N = 4096: 2.08 against 2.22 ms; N = 245: 206 against 221 us; profiles/r04_small_n_latency.txt).
 constexpr int64_t kGradRectFromN = 8192;
 
-int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
-                         double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
-                         double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h) {
+// `build` writes the lower triangle of K (n rows, exact diagonal, no jitter) into the matrix it is handed: the layer recursion of
+// a Gram matrix for the MLP family (factor_with_identity below), the conv pair build for smn_spr_cnn_loss_grad (cnn_grad.hip).
+int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
+                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h) {
   if (round_up(n, kTile) < kGradRectFromN) {
     Aug g;
     SMN_TRY(aug_alloc(ctx, dtype, n, n, 1, &g));
     SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-    SMN_TRY(smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
-                          SMN_GET_NNGP, g.a, nullptr, g.lda));
+    SMN_TRY(build(g.a, g.lda));
     if (dtype == SMN_F64)
       hipLaunchKernelGGL(identity_block_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                          reinterpret_cast<double*>(g.at(g.n_pad, 0)), g.lda, n);
@@ -528,8 +527,7 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
   SMN_TRY(smn_workspace(ctx, 2, es * (size_t)n_total * (size_t)lda, &av));
   char* a = static_cast<char*>(av);
   SMN_HIP(ctx, hipMemsetAsync(a + es * (size_t)n * (size_t)lda, 0, es * (size_t)(n_total - n) * (size_t)lda, ctx->stream));
-  SMN_TRY(smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
-                        SMN_GET_NNGP, a, nullptr, lda));
+  SMN_TRY(build(a, lda));
   char* xrows = a + es * (size_t)n_pad * (size_t)lda;
   if (dtype == SMN_F64)
     hipLaunchKernelGGL(identity_block_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -556,6 +554,17 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
   if (logdet_h) *logdet_h = ld;
   if (info_h) *info_h = info;
   return SMN_OK;
+}
+
+int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                         double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
+                         double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
+                         int* info_h) {
+  const KernelInto build = [&](void* k_d, int64_t ldk) {
+    return smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
+                         SMN_GET_NNGP, k_d, nullptr, ldk);
+  };
+  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h);
 }
 
 int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,

@@ -1,5 +1,7 @@
 // internal.hpp — C++-side interfaces between the translation units of libsmnngp.so.
 #pragma once
+#include <functional>
+
 #include "common.hpp"
 
 constexpr int kTile = 128;   // GEMM block edge; every padded dimension is a multiple of it
@@ -125,6 +127,10 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
                          double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
                          double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
                          int* info_h);
+// the same with K written by the caller: build(k_d, ldk) fills the lower triangle of K (n rows) in the factorisation workspace
+using KernelInto = std::function<int(void* k_d, int64_t ldk)>;
+int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
+                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h);
 int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info);
 int gram_lower(smn_ctx* ctx, int dtype, const void* x_d, int64_t n, int64_t ldx, int64_t d, void* k0_d, int64_t ldk, void* q_d);
 // -x x^T (lower, into neg_inv [n, n] ld = ldo) and alpha = x z from the rows x [n, kcols] (ld = ldx, row i zero left of its

@@ -109,6 +109,10 @@ class CnnKernelFn:
         self.ctx = ctx
         self.entry = entry
 
+    @property
+    def params(self):
+        return (self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std)
+
     def __call__(self, x1, x2=None, get="nngp", fill="full"):
         if get != "nngp":
             raise NotImplementedError("conv kernel: only get='nngp' is on the hot path")

@@ -8,12 +8,52 @@ import numpy as np
 
 from .. import _lib
 from .._lib import DeviceArray, as_device
-from ..nt_kernels import KernelFn
+from ..nt_kernels import CnnKernelFn, KernelFn
 from .base import ConstraintTrainVar, Module
 from .bijectors import positive
 from .utils import jitter
 
-__all__ = ["SPR"]
+__all__ = ["SPR", "grad_route", "lml_value_and_grads"]
+
+
+def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
+    """Host part of the analytic gradient, shared by every kernel family: from terms = sum G dK~/d(w_std, b_std,
+    last_w_std, eps), quad = y^T K~^-1 y and logdet K~ to (log-pdf, derivatives of the log-pdf with respect to the
+    constrained values).  The derivatives come as a dict with keys "w_std", "b_std", "last_w_std", "eps" and, for the
+    Student-t head (df = 2a > 0, scale = b/a), "a" and "b"."""
+    import math
+    from .utils import digamma
+    q, ld = quad, logdet
+    dlp = {}                                                  # d logpdf / d constrained value
+    for key, t in zip(("w_std", "b_std", "last_w_std", "eps"), terms):
+        dlp[key] = 0.5 * t
+    if df <= 0.0:                                             # likelihoods.py:25-28
+        lp = -0.5 * q - 0.5 * n * math.log(2.0 * math.pi) - 0.5 * ld
+    else:                                                     # likelihoods.py:45-50, utils.py:178-183
+        a_, b_ = a, b
+        t = 0.5 * (df + n)
+        qs = q / scale
+        lp = (-t * math.log1p(qs / df) - 0.5 * n * math.log(df * math.pi) + math.lgamma(t) - math.lgamma(0.5 * df)
+              - 0.5 * (ld + n * math.log(scale)))
+        d_scale = t * qs / ((df + qs) * scale) - 0.5 * n / scale
+        d_df = (-0.5 * math.log1p(qs / df) + t * qs / (df * (df + qs)) - 0.5 * n / df
+                + 0.5 * digamma(t) - 0.5 * digamma(0.5 * df))
+        dlp["a"] = 2.0 * d_df - d_scale * b_ / (a_ * a_)      # df = 2a, scale = b/a
+        dlp["b"] = d_scale / a_
+    return lp, dlp
+
+
+def grad_route(kernel_fn, likelihood):
+    """The fused C-ABI entry SPR.loss_and_grad uses for this kernel function and likelihood: "smn_spr_loss_grad" (MLP /
+    dense ResNet) or "smn_spr_cnn_loss_grad" (get_cnn_kernel).  Anything else, the conv ResNet included, has no analytic
+    gradient: NotImplementedError, which train.build_train_step(method="auto") answers with central differences."""
+    if hasattr(likelihood, "lml_params"):
+        if isinstance(kernel_fn, KernelFn):
+            return "smn_spr_loss_grad"
+        if isinstance(kernel_fn, CnnKernelFn) and kernel_fn.entry == "smn_kernel_cnn":
+            return "smn_spr_cnn_loss_grad"
+    raise NotImplementedError("analytic gradients need an MLP / dense-ResNet KernelFn or a get_cnn_kernel CnnKernelFn and "
+                              "a Gaussian or Student-t likelihood; use train.value_and_grad_fd")
 
 
 class SPR(Module):
@@ -81,50 +121,50 @@ class SPR(Module):
         """(loss, {variable name: d loss / d RAW value}) -- the analytic counterpart of
         objax.GradValues(model.loss, model.vars()) in experiments/regression/train.py:61-67.
         One augmented factorisation gives alpha = K~^-1 y, K~^-1, the quadratic form and logdet; one pass over
-        the lower triangle of X X^T / d contracts G = coef alpha alpha^T - K~^-1 with the forward-mode
-        dK/d(w_std, b_std, last_w_std) (csrc/grad.hip).  The (a, b) derivatives of the Student-t head and the
-        softplus chain rule are closed forms on the host.  MLP / dense-ResNet kernels only."""
-        import math
-        from .utils import digamma
+        the lower triangle contracts G = coef alpha alpha^T - K~^-1 with the forward-mode
+        dK/d(w_std, b_std, last_w_std): over X X^T / d for MLP / dense-ResNet kernels (csrc/grad.hip), over the image
+        pairs for get_cnn_kernel (csrc/cnn_grad.hip, images of up to 1024 pixels).  The (a, b) derivatives of the
+        Student-t head and the softplus chain rule are closed forms on the host (lml_value_and_grads).  Anything else --
+        the conv ResNet, a likelihood without lml_params, larger images -- raises NotImplementedError."""
         kernel_fn = self.kernel.get_kernel_fn()
-        if not (isinstance(kernel_fn, KernelFn) and hasattr(self.likelihood, "lml_params")):
-            raise NotImplementedError("analytic gradients need an MLP / dense-ResNet KernelFn and a Gaussian or "
-                                      "Student-t likelihood; use train.value_and_grad_fd")
+        mlp = grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad"
         eps = self.eps.safe_value
         df, scale = self.likelihood.lml_params()
         x, ctx = self.x_data, self.x_data.ctx
-        net, act, L, w, b, lw = kernel_fn.params
         n = self.num_data
         quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
         terms = (C.c_double * 4)()
-        ctx.call("smn_spr_loss_grad", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1],
-                 self.y_data.ptr, eps, df, scale, C.byref(quad), C.byref(logdet), C.byref(info), terms)
-        names = {id(v): k for k, v in self.vars().items()}
+        if mlp:
+            net, act, L, w, b, lw = kernel_fn.params
+            ctx.call("smn_spr_loss_grad", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1],
+                     self.y_data.ptr, eps, df, scale, C.byref(quad), C.byref(logdet), C.byref(info), terms)
+        else:
+            if len(x.shape) != 4:
+                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+            act, L, w, b, lw = kernel_fn.params
+            try:
+                ctx.call("smn_spr_cnn_loss_grad", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2], x.shape[3],
+                         self.y_data.ptr, eps, df, scale, C.byref(quad), C.byref(logdet), C.byref(info), terms)
+            except _lib.SmnError as e:
+                if e.code == _lib.ENOTSUP:                    # images above the tangent kernel's limit
+                    raise NotImplementedError(str(e)) from e
+                raise
         nan = float("nan")
         if info.value != 0:
             return nan, {k: nan for k in self.vars()}
-        q, ld = quad.value, logdet.value
-        dlp = {}                                              # d logpdf / d constrained value
-        for var, t in ((self.kernel.w_std, terms[0]), (self.kernel.b_std, terms[1]),
-                       (self.kernel.last_w_std, terms[2]), (self.eps, terms[3])):
-            dlp[id(var)] = 0.5 * t
-        if df <= 0.0:                                         # likelihoods.py:25-28
-            lp = -0.5 * q - 0.5 * n * math.log(2.0 * math.pi) - 0.5 * ld
-        else:                                                 # likelihoods.py:45-50, utils.py:178-183
-            a_, b_ = self.likelihood.a.safe_value, self.likelihood.b.safe_value
-            t = 0.5 * (df + n)
-            qs = q / scale
-            lp = (-t * math.log1p(qs / df) - 0.5 * n * math.log(df * math.pi) + math.lgamma(t) - math.lgamma(0.5 * df)
-                  - 0.5 * (ld + n * math.log(scale)))
-            d_scale = t * qs / ((df + qs) * scale) - 0.5 * n / scale
-            d_df = (-0.5 * math.log1p(qs / df) + t * qs / (df * (df + qs)) - 0.5 * n / df
-                    + 0.5 * digamma(t) - 0.5 * digamma(0.5 * df))
-            dlp[id(self.likelihood.a)] = 2.0 * d_df - d_scale * b_ / (a_ * a_)     # df = 2a, scale = b/a
-            dlp[id(self.likelihood.b)] = d_scale / a_
+        student = df > 0.0
+        lp, dlp = lml_value_and_grads(terms, quad.value, logdet.value, n, df, scale,
+                                      self.likelihood.a.safe_value if student else None,
+                                      self.likelihood.b.safe_value if student else None)
+        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
+                  "eps": self.eps}
+        if student:
+            owners.update(a=self.likelihood.a, b=self.likelihood.b)
+        names = {id(v): k for k, v in self.vars().items()}
         grads = {}
-        for vid, g in dlp.items():
-            var = next(v for v in self.vars().values() if id(v) == vid)
-            grads[names[vid]] = float(-g / n * var.constraint.grad(var.value))
+        for key, g in dlp.items():
+            var = owners[key]
+            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
         return -lp / n, grads
 
     # ---- spax/models.py:100-120

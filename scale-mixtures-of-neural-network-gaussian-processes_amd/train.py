@@ -7,8 +7,8 @@ as softplus-inverse raw values (spax/base.py:15-25).  The gradient of the loss w
 values is taken by central differences: 2 loss evaluations (= 2 fused build + Cholesky passes on the GPU)
 per variable.  This is SURVEY.md section 8f.1's finite-difference fallback (use float64 data: in float32 the loss
 carries ~1e-6 relative noise and the quotient is dominated by it).  The analytic form, 1/2 tr((c aa^T - K^-1)
-dK/dtheta) with forward-mode dK/dtheta through the layer recursion, is SPR.loss_and_grad (csrc/grad.hip);
-build_train_step prefers it when the model supports it.
+dK/dtheta) with forward-mode dK/dtheta through the layer recursion, is SPR.loss_and_grad (csrc/grad.hip for the MLP
+family, csrc/cnn_grad.hip for get_cnn_kernel); build_train_step prefers it when the model supports it.
 """
 from __future__ import annotations
 
@@ -74,7 +74,8 @@ class Adam:
 def build_train_step(model, variables=None, optimizer=None, h=1e-4, method="auto"):
     """train_step(learning_rate) -> loss before the update  (regression/train.py:61-67).
     method: "analytic" (SPR.loss_and_grad), "fd" (central differences) or "auto" (analytic when the model's
-    kernel / likelihood support it, else finite differences)."""
+    kernel / likelihood support it -- MLP, dense-ResNet and get_cnn_kernel kernels with images of up to 1024 pixels --
+    else finite differences: the conv ResNet, larger images)."""
     if method not in ("auto", "analytic", "fd"):
         raise ValueError("method must be 'auto', 'analytic' or 'fd'")
     variables = variables if variables is not None else train_vars(model)
