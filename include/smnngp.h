@@ -286,6 +286,20 @@ int smn_spr_loss_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens
                       const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
                       double eps_abs, double df, double scale,
                       double* quad_h, double* logdet_h, int* info_h, double terms_h[4]);
+/* smn_spr_loss_grad_batch: nprob x smn_spr_loss_grad on ONE data set in one sequence of launches (grid.y = the problem), for
+ *   multi-start training and for refining the cells of a grid search: per-problem w_std[], b_std[], last_w_std[], eps_abs[],
+ *   df[] (NULL: Gaussian) and scale[] (host arrays of nprob doubles) -> quad_h[], logdet_h[], info_h[] (any may be NULL) and
+ *   terms_h [nprob][4].  Problem b returns, bit for bit, what smn_spr_loss_grad returns for its parameters.  X X^T / d is
+ *   formed once per call; the nprob joint matrices [[K~, .], [I, 0], [y^T, 0, 0]] lie side by side in the workspace and are
+ *   factored together, and the contraction reads -K~^-1 and alpha where the factorisation left them.  A problem that is not
+ *   positive definite reports its own info > 0 and NaN quad, logdet and terms; the others are unaffected and the call returns
+ *   SMN_OK.  Batches whose workspaces (nprob x (n_pad + (n+1)_pad)^2 elements) exceed the budget of smn_debug_batch_bytes run in
+ *   chunks.  From n_pad = 8192 on (the rectangle route of the serial call) the problems run one after another. */
+int smn_spr_loss_grad_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nprob,
+                            const double* w_std, const double* b_std, const double* last_w_std,
+                            const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
+                            const double* eps_abs, const double* df, const double* scale,
+                            double* quad_h, double* logdet_h, int* info_h, double* terms_h);
 
 /* ---- the same for the conv-NNGP kernel of smn_kernel_cnn (experiments/nt_kernels.py:34-45) ----
  * What objax.GradValues(model.loss, vars) supplies to experiments/regression/train.py:61-67 when the kernel function is

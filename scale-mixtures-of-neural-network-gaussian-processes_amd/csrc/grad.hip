@@ -16,7 +16,9 @@
 //           phi_A = (pi - acos c)/(2 pi)        phi_qi = sqrt(1-c^2) sqrt(q_i q_j) / (4 pi q_i)
 //   Erf:    phi   = (2/pi) asin s,   s = 2A / sqrt(P),  P = (1+2q_i)(1+2q_j)
 //           phi_A = 4 / (pi sqrt(P) sqrt(1-s^2))     phi_qi = -(2/pi) s / (sqrt(1-s^2) (1+2q_i))
+#include <climits>
 #include <cmath>
+#include <vector>
 
 #include "gemm_nt.hpp"
 #include "internal.hpp"
@@ -102,10 +104,8 @@ constexpr int kTabFields = 5;   // per activation layer and row: q, dq/dw2, dq/d
 // Diagonal of the same recursion (fp64 arithmetic): variance entering each activation, its derivatives and the two
 // per-row factors of act_r.  tab[(s*5 + f)*n + i], f = 0: q, 1: dq/dw2, 2: dq/db2, 3: ra, 4: rb.
 template <int NET, int ACT, typename R>
-__global__ void grad_tables_kernel(const double* __restrict__ q0, int64_t n, int nsets, double w2, double b2,
-                                   R* __restrict__ tab) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void grad_tables_row(const double* __restrict__ q0, int64_t n, int nsets, double w2, double b2,
+                                                R* __restrict__ tab, int64_t i) {
   double q = q0[i], dw = 0.0, db = 0.0;
   if (NET == NET_RESNET) {
     dw = q;
@@ -144,6 +144,14 @@ __global__ void grad_tables_kernel(const double* __restrict__ q0, int64_t n, int
   }
 }
 
+template <int NET, int ACT, typename R>
+__global__ void grad_tables_kernel(const double* __restrict__ q0, int64_t n, int nsets, double w2, double b2,
+                                   R* __restrict__ tab) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  grad_tables_row<NET, ACT, R>(q0, n, nsets, w2, b2, tab, i);
+}
+
 template <typename T>
 struct GradArgs {
   using R = T;                       // arithmetic of the per-element chain
@@ -162,8 +170,10 @@ constexpr int GT = 64;               // tile edge of the contraction
 // One 64 x 64 tile of the lower triangle per workgroup; a thread owns one column and 16 rows (wave w: rows w, w+4, ...)
 // and carries their (K, dK/dw2, dK/db2) through the layers together: the column-side table entries are loaded once per
 // layer, the row-side ones are wave-uniform (scalar loads).  Products in R, the four sums in double.
-template <typename T, int NET, int ACT>
-__global__ void __launch_bounds__(256) grad_contract_kernel(GradArgs<T> a) {
+// INPLACE (the batched form): -K~^-1 and alpha are read where the joint factorisation left them -- the lower triangle of the
+// Schur block (what extract_posterior mirrors into the serial call's copy) and the NEGATED right-hand-side row.
+template <typename T, int NET, int ACT, bool INPLACE>
+__device__ __forceinline__ void grad_contract_tile(const GradArgs<T>& a, double* __restrict__ partial) {
   using R = typename GradArgs<T>::R;
   int tr, tc;
   tri_decode(blockIdx.x, tr, tc);
@@ -216,12 +226,15 @@ __global__ void __launch_bounds__(256) grad_contract_kernel(GradArgs<T> a) {
     }
   }
   double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum G dK/dw2, sum G dK/db2, sum G K, tr G
-  const R aj = (R)a.alpha[jc], coef = (R)a.coef, lw2 = (R)a.lw2;
+  const R aj = INPLACE ? -(R)a.alpha[jc] : (R)a.alpha[jc], coef = (R)a.coef, lw2 = (R)a.lw2;
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int64_t i = row0 + w + 4 * r, ic = i < n ? i : n - 1;
     const bool valid = i < n && j < n && j <= i;
-    const R g = fma(coef * (R)a.alpha[ic], aj, (R)a.nkinv[ic * a.ldki + jc]);
+    const R ai = INPLACE ? -(R)a.alpha[ic] : (R)a.alpha[ic];
+    const int64_t hi = ic > jc ? ic : jc, lo = ic > jc ? jc : ic;
+    const R ninv = INPLACE ? (R)a.nkinv[hi * a.ldki + lo] : (R)a.nkinv[ic * a.ldki + jc];
+    const R g = fma(coef * ai, aj, ninv);
     const R m = !valid ? R(0) : (i == j ? R(1) : R(2));   // the upper triangle is the mirror image
     const R gm = m * g * lw2;
     acc[0] += (double)(gm * dw[r]);
@@ -238,12 +251,16 @@ __global__ void __launch_bounds__(256) grad_contract_kernel(GradArgs<T> a) {
     if ((tid & 63) == 0) red[q][tid >> 6] = v;
   }
   __syncthreads();
-  if (tid < 4) a.partial[(int64_t)blockIdx.x * 4 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+  if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+template <typename T, int NET, int ACT>
+__global__ void __launch_bounds__(256) grad_contract_kernel(GradArgs<T> a) {
+  grad_contract_tile<T, NET, ACT, false>(a, a.partial);
 }
 
 // Second stage: fixed-order sum of the per-tile partials (bitwise reproducible).
-__global__ void __launch_bounds__(256) grad_reduce_kernel(const double* __restrict__ partial, int64_t ntiles,
-                                                          double* __restrict__ out) {
+__device__ __forceinline__ void grad_reduce_block(const double* __restrict__ partial, int64_t ntiles, double* __restrict__ out) {
   __shared__ double red[4][4];
   const int tid = threadIdx.x;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -259,6 +276,120 @@ __global__ void __launch_bounds__(256) grad_reduce_kernel(const double* __restri
   }
   __syncthreads();
   if (tid < 4) out[tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+__global__ void __launch_bounds__(256) grad_reduce_kernel(const double* __restrict__ partial, int64_t ntiles,
+                                                          double* __restrict__ out) {
+  grad_reduce_block(partial, ntiles, out);
+}
+
+// ---- batched forms (smn_spr_loss_grad_batch): grid.y = the problem.  Each runs the text of the serial kernels above on its
+// own hyper-parameters, tables and Schur block, so every problem's sums carry the bits of its serial call.
+struct GradProb {
+  double w2, b2, lw2, df, scale;   // df <= 0: Gaussian head
+  double shift;                    // absolute shift of K's diagonal
+};
+constexpr int kBatchRes = 8;       // per problem: the four sums, quad, logdet, info, (pad)
+
+template <int NET, int ACT, typename R>
+__global__ void grad_tables_batch_kernel(const double* __restrict__ q0, int64_t n, int nsets,
+                                         const GradProb* __restrict__ prob, R* __restrict__ tab, int64_t tab_bs) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const GradProb p = prob[blockIdx.y];
+  grad_tables_row<NET, ACT, R>(q0, n, nsets, p.w2, p.b2, tab + (int64_t)blockIdx.y * tab_bs, i);
+}
+
+// coef of the Student-t head from the problem's own quadratic form: the host expression of smn_spr_loss_grad, operation by
+// operation (IEEE double add / multiply / divide; nothing here can contract into an FMA)
+__device__ __forceinline__ double grad_coef(double df, double scale, double quad, int64_t n) {
+#pragma clang fp contract(off)
+  if (!(df > 0.0)) return 1.0;
+  const double num = df + (double)n;
+  const double qs = quad / scale;
+  const double den = (df + qs) * scale;
+  return num / den;
+}
+
+template <typename T>
+struct GradBatchArgs {
+  const T* k0; int64_t ldk0;
+  const T* aug; int64_t lda, bstride, aug0;   // problem b's factored joint matrix at aug + b * bstride; Schur block from (aug0, aug0)
+  int64_t n;
+  const T* tab; int64_t tab_bs;
+  int nsets;
+  const GradProb* prob;
+  double* partial; int64_t ntiles;            // [batch][ntiles][4]
+};
+
+template <typename T, int NET, int ACT>
+__global__ void __launch_bounds__(256) grad_contract_batch_kernel(GradBatchArgs<T> b) {
+  const int64_t y = blockIdx.y;
+  const GradProb p = b.prob[y];
+  const T* m = b.aug + y * b.bstride;
+  GradArgs<T> a;
+  a.k0 = b.k0; a.ldk0 = b.ldk0;
+  a.nkinv = m + b.aug0 * b.lda + b.aug0; a.ldki = b.lda;
+  a.alpha = m + (b.aug0 + b.n) * b.lda + b.aug0;
+  a.n = b.n; a.tab = b.tab + y * b.tab_bs; a.nsets = b.nsets;
+  a.w2 = p.w2; a.b2 = p.b2; a.lw2 = p.lw2;
+  a.coef = grad_coef(p.df, p.scale, -(double)m[(b.aug0 + b.n) * b.lda + b.aug0 + b.n], b.n);
+  a.partial = nullptr;
+  grad_contract_tile<T, NET, ACT, true>(a, b.partial + y * b.ntiles * 4);
+}
+
+// one block per problem: its four sums, and beside them quad, logdet and info, so that ONE copy brings a chunk home
+template <typename T>
+__global__ void __launch_bounds__(256) grad_reduce_batch_kernel(const double* __restrict__ partial, int64_t ntiles,
+                                                                const T* __restrict__ aug, int64_t lda, int64_t bstride,
+                                                                int64_t qrow, const double* __restrict__ logdet,
+                                                                const int* __restrict__ info, double* __restrict__ res) {
+  const int64_t y = blockIdx.x;
+  double* r = res + y * kBatchRes;
+  grad_reduce_block(partial + y * ntiles * 4, ntiles, r);
+  if (threadIdx.x == 4) r[4] = -(double)aug[y * bstride + qrow * lda + qrow];
+  if (threadIdx.x == 5) r[5] = logdet[y];
+  if (threadIdx.x == 6) r[6] = (double)info[y];
+}
+
+// Everything of the joint matrices but K itself, all problems in one launch: rows [n, n_total) cleared, the identity padding,
+// the identity block under K, y^T behind it, the problem's absolute shift on K's diagonal (the arithmetic of aug_prep_kernel)
+// and the logdet / info reset.  16-byte stores; the shift touches K's rows only, the fill the rows under them.
+template <typename T>
+__global__ void __launch_bounds__(256) grad_assemble_batch_kernel(T* __restrict__ aug, int64_t lda, int64_t bstride, int64_t n,
+                                                                  int64_t n_pad, int64_t n_total, const T* __restrict__ y,
+                                                                  const GradProb* __restrict__ prob, double* __restrict__ logdet,
+                                                                  int* __restrict__ info) {
+  constexpr int VEC = 16 / sizeof(T);
+  using vec_t = typename Mfma<T>::vec_t;
+  T* a = aug + (int64_t)blockIdx.z * bstride;
+  const int64_t c0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (c0 >= n_total) return;
+  if (blockIdx.y == 0) {
+    const double sh = prob[blockIdx.z].shift;
+    if (sh != 0.0)
+      for (int e = 0; e < VEC; ++e) {
+        const int64_t c = c0 + e;
+        if (c < n) a[c * lda + c] = (T)((double)a[c * lda + c] + sh);
+      }
+  }
+  for (int64_t r = n + blockIdx.y; r < n_total; r += gridDim.y) {
+    vec_t v;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int64_t c = c0 + e;
+      T x = T(0);
+      if (r < n_pad) x = c == r ? T(1) : T(0);                      // identity padding
+      else if (r < n_pad + n) x = c == r - n_pad ? T(1) : T(0);     // identity block
+      else if (r == n_pad + n) x = c < n ? y[c] : T(0);             // y^T
+      v[e] = x;
+    }
+    *reinterpret_cast<vec_t*>(a + r * lda + c0) = v;
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    logdet[blockIdx.z] = 0.0;
+    info[blockIdx.z] = INT_MAX;
+  }
 }
 
 template <typename T>
@@ -323,6 +454,136 @@ int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, 
   return SMN_OK;
 }
 
+// The batched launches of one chunk behind its factorisation: tables, contraction, reduction (+ quad / logdet / info).
+template <typename T, int NET, int ACT>
+int grad_batch_launch(smn_ctx* ctx, const GradBatchArgs<T>& b, int nb, const double* q64, const double* logdet_d,
+                      const int* info_d, double* res_d) {
+  hipLaunchKernelGGL((grad_tables_batch_kernel<NET, ACT, T>), dim3((unsigned)((b.n + 255) / 256), (unsigned)nb), dim3(256), 0,
+                     ctx->stream, q64, b.n, b.nsets, b.prob, const_cast<T*>(b.tab), b.tab_bs);
+  SMN_CHECK_LAUNCH(ctx);
+  {
+    ProfScope ps(ctx, PROF_MISC, ctx->stream);
+    hipLaunchKernelGGL((grad_contract_batch_kernel<T, NET, ACT>), dim3((unsigned)b.ntiles, (unsigned)nb), dim3(256), 0,
+                       ctx->stream, b);
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  const int64_t qrow = b.aug0 + b.n;
+  hipLaunchKernelGGL(grad_reduce_batch_kernel<T>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, b.partial, b.ntiles, b.aug,
+                     b.lda, b.bstride, qrow, logdet_d, info_d, res_d);
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
+// The joint route of smn_spr_loss_grad for nprob problems at once (heads.hip factor_built_with_identity, batched the way
+// spr_batch batches the loss): K0 and its diagonal once; per chunk the G joint matrices [[K~, .], [I, 0], [y^T, 0, 0]] side by
+// side in workspace slot 2, ONE factorisation with grid.y = G, and the contraction reading -K~^-1 and alpha where it left them.
+template <typename T>
+int grad_batch_t(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nprob, const double* w_std, const double* b_std,
+                 const double* last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
+                 const double* eps_abs, const double* df, const double* scale, double* quad_h, double* logdet_h, int* info_h,
+                 double* terms_h) {
+  const int nsets = net == SMN_NET_MLP ? num_hiddens : num_hiddens + 1;
+  if (nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "num_hiddens too large (max %d activation layers)", kMaxSets);
+  const size_t es = sizeof(T);
+  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
+  void* k0 = nullptr;
+  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
+  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
+  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));
+  const int64_t n_pad = round_up(n, kTile), n_total = n_pad + round_up(n + 1, kTile), lda = n_total, bstride = n_total * lda;
+  const size_t per = es * (size_t)bstride;
+  int chunk = (int)std::min<size_t>((size_t)nprob, std::max<size_t>(1, ctx->batch_bytes / per));
+  if (chunk > 65535) chunk = 65535;   // grid.y / grid.z
+  void *av = nullptr, *gv = nullptr, *sv = nullptr;
+  SMN_TRY(smn_workspace(ctx, 2, per * (size_t)chunk, &av));
+  const int64_t t64 = (n + GT - 1) / GT, ntiles = t64 * (t64 + 1) / 2;
+  const size_t ntab = (size_t)n * kTabFields * (size_t)(nsets > 0 ? nsets : 1);   // T-typed; sized as doubles, per problem
+  SMN_TRY(smn_workspace(ctx, 4, sizeof(double) * ((size_t)n + (size_t)chunk * (ntab + (size_t)ntiles * 4 + kBatchRes)), &gv));
+  double* q64 = static_cast<double*>(gv);
+  double* tabd = q64 + n;
+  double* partial = tabd + (size_t)chunk * ntab;
+  double* res_d = partial + (size_t)chunk * (size_t)ntiles * 4;
+  // per-problem scalars: GradProb and logdet (doubles), info (ints)
+  SMN_TRY(smn_workspace(ctx, 8, (sizeof(GradProb) + sizeof(double) + sizeof(int)) * (size_t)chunk, &sv));
+  GradProb* prob_d = static_cast<GradProb*>(sv);
+  double* ld_d = reinterpret_cast<double*>(prob_d + chunk);
+  int* info_d = reinterpret_cast<int*>(ld_d + chunk);
+  hipLaunchKernelGGL(cast_q_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<const T*>(q), q64, n);
+  SMN_CHECK_LAUNCH(ctx);
+  // host sources of the two parameter uploads of a chunk: they live until the chunk's synchronisation (and a failed call
+  // drains the stream before they go, below), so neither upload needs a synchronisation of its own
+  std::vector<GradProb> prob_h((size_t)chunk);
+  std::vector<char> progs_h;
+  std::vector<double> res_h((size_t)chunk * kBatchRes);
+  struct Drain {   // an error return: nothing in flight may still read the vectors above
+    smn_ctx* c; bool armed = true;
+    ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  for (int p0 = 0; p0 < nprob; p0 += chunk) {
+    const int nb = std::min(chunk, nprob - p0);
+    SMN_TRY(recursion_lower_batch(ctx, dtype, net, act, num_hiddens, nb, w_std + p0, b_std + p0, last_w_std + p0, k0, n, ld0, q, av,
+                                  lda, bstride, progs_h));
+    for (int b = 0; b < nb; ++b) {
+      const int g = p0 + b;
+      prob_h[(size_t)b] = GradProb{w_std[g] * w_std[g], b_std[g] * b_std[g], last_w_std[g] * last_w_std[g], df ? df[g] : 0.0,
+                                   scale ? scale[g] : 1.0, eps_abs[g]};
+    }
+    SMN_HIP(ctx, hipMemcpyAsync(prob_d, prob_h.data(), sizeof(GradProb) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+    {
+      constexpr int VEC = 16 / (int)sizeof(T);
+      dim3 ga((unsigned)((n_total / VEC + 255) / 256), (unsigned)std::min<int64_t>(n_total - n, 1024), (unsigned)nb);
+      hipLaunchKernelGGL(grad_assemble_batch_kernel<T>, ga, dim3(256), 0, ctx->stream, static_cast<T*>(av), lda, bstride, n, n_pad,
+                         n_total, static_cast<const T*>(y_d), prob_d, ld_d, info_d);
+    }
+    SMN_CHECK_LAUNCH(ctx);
+    FactorCall f{dtype, av, n_total, n_pad, lda, n, 0.0, 0.0, false};
+    f.id0 = n_pad;
+    f.id1 = n_pad + n / kTile * kTile;
+    f.prepped = true;
+    f.batch = nb; f.batch_stride = bstride; f.batch_logdet = ld_d; f.batch_info = info_d;
+    SMN_TRY(cholesky_padded(ctx, f));
+    GradBatchArgs<T> ba;
+    ba.k0 = static_cast<const T*>(k0); ba.ldk0 = ld0;
+    ba.aug = static_cast<const T*>(av); ba.lda = lda; ba.bstride = bstride; ba.aug0 = n_pad;
+    ba.n = n; ba.tab = reinterpret_cast<const T*>(tabd); ba.tab_bs = (int64_t)ntab; ba.nsets = nsets;
+    ba.prob = prob_d; ba.partial = partial; ba.ntiles = ntiles;
+    int rc;
+    // a chunk of up to eight problems (a single start above all) publishes straight into the pinned mailbox, as the serial
+    // call's read-out does: one synchronisation, no copy
+    const bool mail = (size_t)nb * kBatchRes <= (size_t)smn_ctx::kMailGram;
+    double* out_d = mail ? ctx->d_mail : res_d;
+    if (net == SMN_NET_MLP && act == SMN_ACT_RELU) rc = grad_batch_launch<T, NET_MLP, ACT_RELU>(ctx, ba, nb, q64, ld_d, info_d, out_d);
+    else if (net == SMN_NET_MLP) rc = grad_batch_launch<T, NET_MLP, ACT_ERF>(ctx, ba, nb, q64, ld_d, info_d, out_d);
+    else if (act == SMN_ACT_RELU) rc = grad_batch_launch<T, NET_RESNET, ACT_RELU>(ctx, ba, nb, q64, ld_d, info_d, out_d);
+    else rc = grad_batch_launch<T, NET_RESNET, ACT_ERF>(ctx, ba, nb, q64, ld_d, info_d, out_d);
+    SMN_TRY(rc);
+    if (!mail)
+      SMN_HIP(ctx, hipMemcpyAsync(res_h.data(), res_d, sizeof(double) * (size_t)nb * kBatchRes, hipMemcpyDeviceToHost, ctx->stream));
+    SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double* res = mail ? ctx->h_mail : res_h.data();
+    for (int b = 0; b < nb; ++b) {
+      const int g = p0 + b;
+      const double* r = res + (size_t)b * kBatchRes;
+      int info = (int)r[6];
+      if (info == INT_MAX) info = 0;
+      if (info_h) info_h[g] = info;
+      if (quad_h) quad_h[g] = info ? std::nan("") : r[4];
+      if (logdet_h) logdet_h[g] = info ? std::nan("") : r[5];
+      double* t = terms_h + (size_t)g * 4;
+      if (info != 0) {
+        for (int i = 0; i < 4; ++i) t[i] = std::nan("");
+        continue;
+      }
+      t[0] = r[0] * 2.0 * w_std[g];
+      t[1] = r[1] * 2.0 * b_std[g];
+      t[2] = r[2] * 2.0 / last_w_std[g];
+      t[3] = r[3];
+    }
+  }
+  drain.armed = false;   // the last chunk's synchronisation has passed
+  return SMN_OK;
+}
+
 }  // namespace
 
 extern "C" int smn_lml_grad_terms(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
@@ -380,4 +641,39 @@ extern "C" int smn_spr_loss_grad(smn_ctx* ctx, int dtype, int net, int act, int 
   if (df > 0.0) coef = (df + (double)n) / ((df + quad / scale) * scale);
   return smn_lml_grad_terms(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, n, ld0, q, ninv, ld0, alpha,
                             coef, terms_h);
+}
+
+// nprob x smn_spr_loss_grad on one data set (their own w_std, b_std, last_w_std, shift and head) as ONE sequence of launches
+// with grid.y = the problem; below the rectangle route's size only -- from there on one problem fills the chip, and the
+// problems run one after another through the serial call.
+extern "C" int smn_spr_loss_grad_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nprob,
+                                       const double* w_std, const double* b_std, const double* last_w_std, const void* x_d,
+                                       int64_t n, int64_t ldx, int64_t d, const void* y_d, const double* eps_abs,
+                                       const double* df, const double* scale, double* quad_h, double* logdet_h, int* info_h,
+                                       double* terms_h) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (nprob <= 0 || !w_std || !b_std || !last_w_std || !eps_abs)
+    return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty batch or null parameter array");
+  if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty");
+  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
+  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "num_hiddens < 0");
+  for (int b = 0; b < nprob; ++b) {
+    if (df && df[b] > 0.0 && !(scale && scale[b] > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: scale must be > 0");
+    if (!(last_w_std[b] != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: bad hyper-parameters");
+  }
+  if (grad_uses_rectangle(n)) {
+    for (int b = 0; b < nprob; ++b)
+      SMN_TRY(smn_spr_loss_grad(ctx, dtype, net, act, num_hiddens, w_std[b], b_std[b], last_w_std[b], x_d, n, ldx, d, y_d, eps_abs[b],
+                                df ? df[b] : 0.0, scale ? scale[b] : 1.0, quad_h ? quad_h + b : nullptr,
+                                logdet_h ? logdet_h + b : nullptr, info_h ? info_h + b : nullptr, terms_h + (size_t)b * 4));
+    return SMN_OK;
+  }
+  if (dtype == SMN_F64)
+    return grad_batch_t<double>(ctx, dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, eps_abs, df,
+                                scale, quad_h, logdet_h, info_h, terms_h);
+  return grad_batch_t<float>(ctx, dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, eps_abs, df, scale,
+                             quad_h, logdet_h, info_h, terms_h);
 }

@@ -501,6 +501,7 @@ __global__ void identity_block_kernel(T* __restrict__ a, int64_t lda, int64_t n)
 //   At these sizes the factorisation is chain-bound and those updates are free, while the rectangle route's extra launches
 //   are not (N = 4096: 2.08 against 2.22 ms; N = 245: 206 against 221 us; profiles/r04_small_n_latency.txt).
 constexpr int64_t kGradRectFromN = 8192;
+bool grad_uses_rectangle(int64_t n) { return round_up(n, kTile) >= kGradRectFromN; }
 
 // `build` writes the lower triangle of K (n rows, exact diagonal, no jitter) into the matrix it is handed: the layer recursion of
 // a Gram matrix for the MLP family (factor_with_identity below), the conv pair build for smn_spr_cnn_loss_grad (cnn_grad.hip).

@@ -131,8 +131,18 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
 using KernelInto = std::function<int(void* k_d, int64_t ldk)>;
 int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
                                void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h);
+// true from the size on at which the gradient takes the rectangle route instead of the joint factorisation (heads.hip)
+bool grad_uses_rectangle(int64_t n);
 int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info);
 int gram_lower(smn_ctx* ctx, int dtype, const void* x_d, int64_t n, int64_t ldx, int64_t d, void* k0_d, int64_t ldk, void* q_d);
+// smn_recursion's symmetric NNGP form (lower 64x64 tiles + mirror, exact diagonal) for nbatch problems over ONE Gram matrix:
+// problem g runs under (w_std[g], b_std[g], last_w_std[g]) (host arrays) and writes out_d + g * out_bs elements (ld = ldo).
+// One table launch and one recursion launch with grid.y = nbatch; per problem the bits of the serial call.
+// No synchronisation: the host source of the layer programs' upload is kept in `stage`, which the caller leaves alone until it
+// has synchronised the stream itself.
+int recursion_lower_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nbatch, const double* w_std,
+                          const double* b_std, const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
+                          const void* q_d, void* out_d, int64_t ldo, int64_t out_bs, std::vector<char>& stage);
 // -x x^T (lower, into neg_inv [n, n] ld = ldo) and alpha = x z from the rows x [n, kcols] (ld = ldx, row i zero left of its
 // 128-column tile) and the vector z [kcols]; *quad_dev = z^T z.  cholesky.hip.
 int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const void* z, int64_t kcols, int64_t n,

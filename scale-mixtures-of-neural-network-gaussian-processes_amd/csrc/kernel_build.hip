@@ -432,15 +432,24 @@ struct RecArgs {
   LayerProg prog; int exact_diag;
   T* out_k; T* out_t; int64_t ldo; int rows_per_block;
   int sym_tiles;   // recursion_sym_kernel: 1 one workgroup per LOWER 64x64 tile (+ mirror), 2 one per tile of the n1 x n2 rectangle
+  // batched form (recursion_lower_batch: the batched gradient's K): problem blockIdx.y = the same K0 under its own layer
+  // program progs[y], its own table block (tab_bs elements apart) and its own output matrix (out_bs elements apart)
+  const LayerProg* progs; int64_t tab_bs, out_bs;
 };
 
 // Stand-alone layer recursion over a stored K0, one workgroup per 64x64 tile, column and row tables in LDS.
 // Symmetric form (x2 == x1, full output): LOWER tiles only.  The element chains run once per unordered pair; the tile is
 // written straight (16-byte stores) and, through an LDS transpose, mirrored into the upper triangle.  Halves the VALU work
 // that bounds the 4-layer map and the K0 bytes read.  Cross form (sym_tiles == 2): every tile of the rectangle, no mirror.
-template <typename T, int NET, int ACT, bool NTK>
+template <typename T, int NET, int ACT, bool NTK, bool BATCH = false>
 __global__ void __launch_bounds__(256) recursion_sym_kernel(RecArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  if constexpr (BATCH) {   // the same text under problem blockIdx.y's program, tables and output: the same bits per problem
+    const int64_t y = blockIdx.y;
+    a.prog = a.progs[y];
+    a.tab1 += y * a.tab_bs; a.tab2 += y * a.tab_bs; a.dg += y * a.tab_bs; a.dgt += y * a.tab_bs;
+    if (a.out_k) a.out_k += y * a.out_bs;
+  }
   constexpr int TS = 64, VEC = 16 / sizeof(T);
   constexpr int LPR = TS / VEC;        // lanes per tile row
   constexpr int RPP = 256 / LPR;       // tile rows covered per pass of the workgroup
@@ -949,6 +958,7 @@ int recursion_t(smn_ctx* ctx, const BuildSpec& spec, const void* k0, int64_t n1,
   a.out_k = (get_mask & SMN_GET_NNGP) ? static_cast<T*>(nngp) : nullptr;
   a.out_t = want_ntk ? static_cast<T*>(ntk) : nullptr;
   a.ldo = ldk; a.rows_per_block = 0;
+  a.progs = nullptr; a.tab_bs = a.out_bs = 0;
   // 16-byte vector path needs aligned rows
   if (ldk0 % (16 / sizeof(T)) || ldk % (16 / sizeof(T)) || (reinterpret_cast<uintptr_t>(k0) & 15) ||
       (a.out_k && (reinterpret_cast<uintptr_t>(a.out_k) & 15)) || (a.out_t && (reinterpret_cast<uintptr_t>(a.out_t) & 15)))
@@ -963,7 +973,80 @@ int recursion_t(smn_ctx* ctx, const BuildSpec& spec, const void* k0, int64_t n1,
   return launch_rec<T>(ctx, a, dim3((unsigned)ntiles), slds, want_ntk);
 }
 
+// recursion_t's symmetric NNGP form for nbatch layer programs over ONE stored K0: tables per problem (grid.y of
+// diag_tables_kernel, as the batched fused build makes them), one launch of the lower-tile kernel with grid.y = nbatch.
+template <typename T>
+int recursion_batch_t(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const double* bw, const double* bb, const double* blw,
+                      const void* k0, int64_t n, int64_t ldk0, const void* q, void* out, int64_t ldo, int64_t out_bs,
+                      std::vector<char>& stage) {
+  stage.resize(sizeof(LayerProg) * (size_t)nbatch);   // the upload's source: the caller keeps it until its next synchronisation
+  LayerProg* hp = reinterpret_cast<LayerProg*>(stage.data());
+  for (int g = 0; g < nbatch; ++g) {
+    BuildSpec sg = spec;
+    sg.w_std = bw[g]; sg.b_std = bb[g]; sg.last_w_std = blw[g];
+    SMN_TRY(make_prog(ctx, sg, &hp[(size_t)g]));
+    if (hp[(size_t)g].net == NET_NONE) return smn_fail(ctx, SMN_EINVAL, "recursion needs a net");
+    set_fast<T>(&hp[(size_t)g], false);
+  }
+  const LayerProg& prog = hp[0];
+  const int trows = 2 * prog.nsets + 2;
+  const int64_t tlen = n, tab_bs = (int64_t)trows * tlen;
+  void *tabv = nullptr, *pv = nullptr;
+  SMN_TRY(smn_workspace(ctx, 1, sizeof(T) * (size_t)tab_bs * (size_t)nbatch, &tabv));
+  SMN_TRY(smn_workspace(ctx, 6, sizeof(LayerProg) * (size_t)nbatch, &pv));
+  LayerProg* progs_d = static_cast<LayerProg*>(pv);
+  SMN_HIP(ctx, hipMemcpyAsync(progs_d, hp, sizeof(LayerProg) * (size_t)nbatch, hipMemcpyHostToDevice, ctx->stream));
+  T* tab1 = static_cast<T*>(tabv);
+  T* dg1 = tab1 + (int64_t)(2 * prog.nsets) * tlen;
+  T* dgt1 = dg1 + tlen;
+  hipLaunchKernelGGL((diag_tables_kernel<T, T>), dim3((unsigned)((n + 255) / 256), (unsigned)nbatch), dim3(256), 0, ctx->stream,
+                     static_cast<const T*>(q), n, prog, tab1, tlen, dg1, dgt1, static_cast<const LayerProg*>(progs_d), tab_bs);
+  SMN_CHECK_LAUNCH(ctx);
+  RecArgs<T> a;
+  a.k0 = static_cast<const T*>(k0); a.ldk0 = ldk0; a.n1 = n; a.n2 = n;
+  a.tab1 = tab1; a.tab2 = tab1; a.ldt1 = tlen; a.ldt2 = tlen; a.dg = dg1; a.dgt = dgt1;
+  a.prog = prog; a.exact_diag = 1;
+  a.out_k = static_cast<T*>(out); a.out_t = nullptr;
+  a.ldo = ldo; a.rows_per_block = 0;
+  a.progs = progs_d; a.tab_bs = tab_bs; a.out_bs = out_bs;
+  if (ldk0 % (16 / sizeof(T)) || ldo % (16 / sizeof(T)) || out_bs % (16 / sizeof(T)) || (reinterpret_cast<uintptr_t>(k0) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & 15))
+    return smn_fail(ctx, SMN_EINVAL, "batched recursion: k0/out must be 16-byte aligned");
+  constexpr int TS = 64;
+  const int64_t t1 = (n + TS - 1) / TS, ntiles = t1 * (t1 + 1) / 2;
+  if (ntiles >= (int64_t)INT32_MAX || nbatch > 65535) return smn_fail(ctx, SMN_ENOTSUP, "batched recursion: grid too large");
+  a.sym_tiles = 1;
+  const size_t slds = sizeof(T) * ((size_t)(prog.nsets * 2 + 1) * 2 * TS + (size_t)TS * (TS + 1));
+  const int net = prog.net, act = prog.act;
+#define REC_CASE(N, A)                                                                  \
+  if (net == N && act == A) {                                                           \
+    auto kern = recursion_sym_kernel<T, N, A, false, true>;                             \
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), slds));             \
+    {                                                                                   \
+      ProfScope ps(ctx, PROF_RECURSION, ctx->stream);                                   \
+      hipLaunchKernelGGL(kern, dim3((unsigned)ntiles, (unsigned)nbatch), dim3(256), slds, ctx->stream, a); \
+    }                                                                                   \
+    SMN_CHECK_LAUNCH(ctx);                                                              \
+    return SMN_OK;                                                                      \
+  }
+  REC_CASE(NET_MLP, ACT_RELU)
+  REC_CASE(NET_MLP, ACT_ERF)
+  REC_CASE(NET_RESNET, ACT_RELU)
+  REC_CASE(NET_RESNET, ACT_ERF)
+#undef REC_CASE
+  return smn_fail(ctx, SMN_EINVAL, "recursion: bad net/act");
+}
+
 }  // namespace
+
+int recursion_lower_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nbatch, const double* w_std,
+                          const double* b_std, const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
+                          const void* q_d, void* out_d, int64_t ldo, int64_t out_bs, std::vector<char>& stage) {
+  BuildSpec s{dtype, net, act, num_hiddens, 1.0, 0.0, 1.0};
+  if (dtype == SMN_F64)
+    return recursion_batch_t<double>(ctx, s, nbatch, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, out_d, ldo, out_bs, stage);
+  return recursion_batch_t<float>(ctx, s, nbatch, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, out_d, ldo, out_bs, stage);
+}
 
 int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, int64_t d,
              void* dst, int64_t rows_pad, int64_t kp, double* q, int64_t rows_a, const void* src2, int64_t n2, int64_t lds2,

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import as_device, default_context
 
-__all__ = ["find_grid", "loss_batch", "predict_batch"]
+__all__ = ["find_grid", "loss_batch", "loss_and_grad_batch", "predict_batch"]
 
 _NET = {"mlp": _lib.NET_MLP, None: _lib.NET_MLP, "resnet": _lib.NET_DENSE_RESNET}
 
@@ -49,6 +49,32 @@ def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_
              x.ptr, n, x.ld, d, y.ptr, cols[3][1], cols[4][1], cols[5][1], pd(lp), pd(quad), pd(logdet),
              info.ctypes.data_as(C.POINTER(C.c_int)))
     return lp, quad, logdet, info
+
+
+def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0,
+                        scale=1.0):
+    """G x SPR.loss_and_grad's device call on one data set in one batched pass (smn_spr_loss_grad_batch): multi-start
+    training (train.build_multistart_step) and gradient refinement of the cells of a grid search.  Arguments as for
+    loss_batch (MLP and dense-ResNet kernels).  Returns (logpdf[G], quad[G], logdet[G], info[G], terms[G, 4]) as NumPy
+    arrays: terms[g] = sum G dK~/d(w_std, b_std, last_w_std, eps) exactly as smn_spr_loss_grad returns them for problem g;
+    logpdf from quad and logdet by the host arithmetic of SPR.loss_and_grad; NaN where info != 0."""
+    from .spax.models import lml_value_and_grads
+    g = max(np.size(v) for v in (w_std, b_std, last_w_std, eps, df, scale))
+    cols = [_darr(np.broadcast_to(np.asarray(v, dtype=np.float64), (g,))) for v in (w_std, b_std, last_w_std, eps, df, scale)]
+    n, d = x.shape
+    quad, logdet = np.empty(g), np.empty(g)
+    terms = np.empty((g, 4))
+    info = np.zeros(g, dtype=np.int32)
+    pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))    # noqa: E731
+    ctx.call("smn_spr_loss_grad_batch", x.dcode, _NET[network], _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1],
+             cols[2][1], x.ptr, n, x.ld, d, y.ptr, cols[3][1], cols[4][1], cols[5][1], pd(quad), pd(logdet),
+             info.ctypes.data_as(C.POINTER(C.c_int)), pd(terms))
+    lp = np.full(g, np.nan)
+    for i in range(g):
+        if info[i] == 0:
+            lp[i] = lml_value_and_grads(terms[i], float(quad[i]), float(logdet[i]), n, float(cols[4][0][i]), float(cols[5][0][i]),
+                                        1.0, 1.0)[0]    # (a, b enter the derivatives only)
+    return lp, quad, logdet, info, terms
 
 
 def predict_batch(ctx, x, y, x_test, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0,

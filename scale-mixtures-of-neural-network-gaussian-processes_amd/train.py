@@ -18,7 +18,8 @@ import numpy as np
 
 from .spax.base import TrainVar
 
-__all__ = ["train_vars", "value_and_grad", "value_and_grad_fd", "Adam", "PlateauSchedule", "build_train_step"]
+__all__ = ["train_vars", "value_and_grad", "value_and_grad_fd", "Adam", "PlateauSchedule", "build_train_step",
+           "BatchAdam", "MultiStartStep", "build_multistart_step"]
 
 
 def train_vars(model):
@@ -96,6 +97,132 @@ def build_train_step(model, variables=None, optimizer=None, h=1e-4, method="auto
         return value
 
     return train_step
+
+
+class BatchAdam:
+    """Adam over G independent starts: `raw` maps each variable name to an array of G raw values, updated in place
+    element by element with the arithmetic of Adam above (same defaults, same order of operations, so start g moves
+    exactly as a single-start run from the same value would).  Entries whose gradient is not finite are left alone, with
+    their moments, as Adam leaves a variable with a non-finite gradient alone; the step count is shared."""
+
+    def __init__(self, raw, beta1=0.9, beta2=0.999, eps=1e-8):
+        self.raw, self.b1, self.b2, self.eps = raw, beta1, beta2, eps
+        self.m = {k: np.zeros_like(v) for k, v in raw.items()}
+        self.v = {k: np.zeros_like(v) for k, v in raw.items()}
+        self.t = 0
+
+    def __call__(self, lr, grads):
+        self.t += 1
+        lr_t = lr * math.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t)
+        for k, g in grads.items():
+            ok = np.isfinite(g)
+            g0 = np.where(ok, g, 0.0)
+            m = self.b1 * self.m[k] + (1 - self.b1) * g0
+            v = self.b2 * self.v[k] + (1 - self.b2) * g0 * g0
+            self.m[k] = np.where(ok, m, self.m[k])
+            self.v[k] = np.where(ok, v, self.v[k])
+            self.raw[k][...] = np.where(ok, self.raw[k] - lr_t * self.m[k] / (np.sqrt(self.v[k]) + self.eps), self.raw[k])
+
+
+class MultiStartStep:
+    """G training runs of one SPR model from G initialisations, advanced together: step(lr) makes ONE batched device call
+    (sweeps.loss_and_grad_batch -> smn_spr_loss_grad_batch, grid.y = G) for all starts, turns each start's terms into
+    d loss / d raw by the host arithmetic of SPR.loss_and_grad (spax.models.lml_value_and_grads, softplus chain rule;
+    Student-t: df = 2a, scale = b/a per start) and applies Adam element-wise.  The log-marginal likelihood is not convex in
+    the hyper-parameters; at the reference's problem sizes one start leaves the chip idle, so G starts cost about what one
+    does.
+
+    .raw       name -> array[G] of raw (unconstrained) values, names as in model.vars()
+    .losses    the losses of the last step (before its update); NaN marks a start whose matrix was not positive definite:
+               it is left where it is (and keeps reporting NaN) and does not disturb the others
+    .best()    index of the lowest finite loss
+    .assign_best()  writes that start into the model's variables, so that test_nll and Checkpointer work as before"""
+
+    def __init__(self, model, starts, optimizer=None):
+        from . import _lib
+        from .spax.models import grad_route
+        kernel_fn = model.kernel.get_kernel_fn()
+        if grad_route(kernel_fn, model.likelihood) != "smn_spr_loss_grad":
+            raise NotImplementedError("multi-start training supports the MLP and dense-ResNet kernels only")
+        self.model = model
+        self.variables = train_vars(model)
+        if set(starts) != set(self.variables):
+            raise ValueError("starts must name every trainable of the model: %s" % sorted(self.variables))
+        self.raw = {k: np.array(starts[k], dtype=np.float64).reshape(-1) for k in self.variables}
+        sizes = {v.size for v in self.raw.values()}
+        if len(sizes) != 1 or min(sizes) < 1:
+            raise ValueError("every entry of starts needs the same number G >= 1 of raw values")
+        self.num_starts = sizes.pop()
+        net, act, self._layers = kernel_fn.params[:3]
+        self._network = "mlp" if net == _lib.NET_MLP else "resnet"
+        self._activation = {v: k for k, v in _lib.ACT.items()}[act]
+        owners = {"w_std": model.kernel.w_std, "b_std": model.kernel.b_std, "last_w_std": model.kernel.last_w_std, "eps": model.eps}
+        self._student = model.likelihood.lml_params()[0] > 0.0
+        if self._student:
+            owners.update(a=model.likelihood.a, b=model.likelihood.b)
+        names = {id(v): k for k, v in model.vars().items()}
+        self._name = {key: names[id(var)] for key, var in owners.items()}     # "w_std" -> "(SPR).kernel(NNGPKernel).w_std"
+        self._var = owners
+        self.optimizer = optimizer or BatchAdam(self.raw)
+        self.losses = np.full(self.num_starts, np.nan)
+
+    def _constrained(self, key):
+        var = self._var[key]
+        return np.asarray(var.constraint(self.raw[self._name[key]]), dtype=np.float64)
+
+    def value_and_grad(self):
+        """(losses[G], {name: d loss / d raw [G]}) at the current raw values: one batched device call."""
+        from . import sweeps
+        from .spax.models import lml_value_and_grads
+        model, g, n = self.model, self.num_starts, self.model.num_data
+        val = {key: self._constrained(key) for key in self._var}
+        if self._student:
+            df, scale = 2.0 * val["a"], val["b"] / val["a"]
+        else:
+            df, scale = np.zeros(g), np.ones(g)
+        x = model.x_data
+        _, quad, logdet, info, terms = sweeps.loss_and_grad_batch(
+            x.ctx, x, model.y_data, network=self._network, num_hiddens=self._layers, activation=self._activation,
+            w_std=val["w_std"], b_std=val["b_std"], last_w_std=val["last_w_std"], eps=val["eps"], df=df, scale=scale)
+        losses = np.full(g, np.nan)
+        grads = {name: np.full(g, np.nan) for name in self.raw}
+        for s in range(g):
+            if info[s] != 0:
+                continue
+            lp, dlp = lml_value_and_grads(terms[s], float(quad[s]), float(logdet[s]), n, float(df[s]), float(scale[s]),
+                                          float(val["a"][s]) if self._student else None,
+                                          float(val["b"][s]) if self._student else None)
+            losses[s] = -lp / n
+            for key, d in dlp.items():
+                name = self._name[key]
+                grads[name][s] = float(-d / n * self._var[key].constraint.grad(self.raw[name][s]))
+        return losses, grads
+
+    def step(self, learning_rate):
+        """One step of every start; returns the G losses before the update."""
+        self.losses, grads = self.value_and_grad()
+        self.optimizer(learning_rate, grads)
+        return self.losses
+
+    __call__ = step
+
+    def best(self):
+        if not np.isfinite(self.losses).any():
+            raise ValueError("no start has a finite loss (take a step first)")
+        return int(np.nanargmin(np.where(np.isfinite(self.losses), self.losses, np.nan)))
+
+    def assign_best(self):
+        s = self.best()
+        for name, var in self.variables.items():
+            var.assign(float(self.raw[name][s]))
+        return s
+
+
+def build_multistart_step(model, starts, optimizer=None):
+    """step(learning_rate) -> losses[G] before the update, for G starts of `model` trained side by side (MultiStartStep).
+    starts: {name in model.vars(): array of G raw values}.  MLP and dense-ResNet kernels with a Gaussian or Student-t
+    likelihood; conv kernels raise NotImplementedError (use build_train_step per start)."""
+    return MultiStartStep(model, starts, optimizer)
 
 
 class PlateauSchedule:
