@@ -327,6 +327,59 @@ int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
                           double eps_abs, double df, double scale,
                           double* quad_h, double* logdet_h, int* info_h, double terms_h[4]);
 
+/* ---- sparse variational classifier, evaluation (spax/models.py:58-78 SVSP.test_acc_nll; experiments/classification/test.py) ----
+ * With inducing images Z [I], q_mu [C,I], q_var [C,I] = diag(q_sqrt) as the reference uses it (NOT squared) and K the NNGP kernel:
+ *     K_rel = K_ZZ + eps tr(K_ZZ)/I I   (NNGPKernel.predict: relative ridge)      K_abs = K_ZZ + eps I   (models.py:68)
+ *     mean[t,c] = (K_tZ K_rel^-1 q_mu^T)[t,c]        v0[t] = K(x_t,x_t) - K_tZ K_rel^-1 K_Zt        A = K_tZ K_abs^-1
+ *     var[t,c]  = v0[t] + sum_j A[t,j]^2 q_var[c,j]  (sample_f_iid reads only the diagonal of the reference's [B,B] covariance)
+ *     f[c,t,s]  = mean[t,c] + sigma[t,c] xi[c,t,s],  xi iid N(0,1) (GaussianPrior: sigma = sqrt(var)) or Student-t(2a)
+ *                 (InverseGammaPrior: sigma = sqrt(b/a var));   lsm = f - logsumexp_c f
+ *     score[t,c] = logsumexp_s lsm[c,t,s]      ll[t] = score[t,y_t] - log S      pred[t] = argmax_c score[t,c]
+ *
+ * smn_kernel_conv_diag: diag_d[i] = K(x_i, x_i), i < n, of smn_kernel_cnn (kind 0) or smn_kernel_conv_resnet (kind 1; num_hiddens
+ *   is the block size): the per-image pass those builds run first, alone; no pair kernel is launched and the values are, bit
+ *   for bit, the diagonal of the symmetric build.  x_d [n,H,W,C], diag_d [n] of `dtype`.
+ * smn_svsp_moments: k_zz_d [I,I] (full), q_mu_d [C,I], q_var_d [C,I] are ALWAYS fp64 -- a 1e-6 jitter is not numerically
+ *   positive definite in fp32 --; k_zt_d [I,T], ktt_diag_d [T], mean_d [T,C], var_d [T,C] are `dtype`.  Both factorisations and
+ *   the three solves run in fp64 through smn_cholesky / smn_trsm.  *info_h: 0, or the 1-based index of the first pivot of K_rel
+ *   (then K_abs) that is non-positive or below I * 2^-52 * max_j K_jj; then mean and var are NaN and the call returns SMN_OK.
+ *   *nonpos_h: entries of var that are <= 0 (their sigma is NaN downstream, as the reference's sqrt gives; nothing is clamped).
+ * smn_mc_softmax: mean_d, sigma_d [T,C] of `dtype`; labels_h [T] host int32, validated to [0,C) (SMN_EINVAL); df <= 0 normal,
+ *   df > 0 Student-t(df) variates; point0 = global index of the first point; noise_d NULL, or [T,C,S] standard variates of
+ *   `dtype` to use instead of the generator.  Out: ll_d [T] fp64, pred_d [T] int32 (first maximum), score_d [T,C] fp64 or NULL.
+ *   `dtype` selects the arithmetic of the generator, the fused multiply-add and the exponentials; the running maxima over
+ *   the draws, every merge of (max, sum) pairs and the outputs are fp64 (for C <= 16 a lane's own running sums are `dtype`:
+ *   terms in [0, 1] relative to its fp64 maximum).  Log-sum-exps over S are online: nothing of size T C S exists, and with
+ *   noise_d == NULL the variates are made in registers and never stored.  1 <= C <= SMN_SVSP_MAX_CLASSES.  Synchronises.
+ * smn_rng_variates: out_d [npoints,C,S] of `dtype` = exactly the variates smn_mc_softmax(noise_d = NULL) consumes for points
+ *   point0 .. point0 + npoints - 1.
+ *
+ * Generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), key = (seed & 0xffffffff, seed >> 32).  The variate of
+ * (seed, global point index p, class c, draw s, df) is a pure function of those five values -- not of T, the batch a point
+ * arrives in, the grid, or C.  Counter layout (four 32-bit words; p, s < 2^32):
+ *     normal     ctr = (s, p, c >> 2, 0): the block's words (r0, r1) give classes 4g, 4g+1 and (r2, r3) classes 4g+2, 4g+3 by
+ *                Box-Muller: u = (r_even + 1/2) 2^-32, z = sqrt(-2 ln u) (cos, sin)(2 pi (r_odd + 1/2) 2^-32)
+ *     Student-t  ctr = (s, p, c, 0x80000000 | k), k = 0 .. 31: Bailey's polar method, two tries per block -- (r0, r1), then
+ *                (r2, r3) -> (u, v) = (r + 1/2) 2^-31 - 1; the first try with w = u^2 + v^2 <= 1 gives
+ *                t = u sqrt(df (w^(-2/df) - 1) / w).  64 tries at most (a loop of fixed trip count; 1e-43 of the variates
+ *                find none and are 0).
+ * fp32 evaluates the same formulas in fp32 on the top 23 bits of a word for u in (0, 1) ((r >> 9) 2^-23 + 2^-24) and the top 24
+ * for (u, v) in (-1, 1) ((r >> 8) 2^-23 + 2^-24 - 1): odd multiples of 2^-24, exact in fp32, never 0 or +-1.
+ * smn_debug_philox: test hook, one raw block: out = Philox4x32-10(ctr, key), computed on the device. */
+#define SMN_SVSP_MAX_CLASSES 128
+int smn_kernel_conv_diag(smn_ctx* ctx, int dtype, int kind, int act, int num_hiddens,
+                         double w_std, double b_std, double last_w_std,
+                         const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, void* diag_d);
+int smn_svsp_moments(smn_ctx* ctx, int dtype, const void* k_zz_d, const void* k_zt_d, const void* ktt_diag_d,
+                     const void* q_mu_d, const void* q_var_d, int64_t I, int64_t T, int64_t C, double eps,
+                     void* mean_d, void* var_d, int* info_h, int64_t* nonpos_h);
+int smn_mc_softmax(smn_ctx* ctx, int dtype, const void* mean_d, const void* sigma_d, const int* labels_h,
+                   int64_t T, int64_t C, int64_t S, double df, uint64_t seed, int64_t point0, const void* noise_d,
+                   void* ll_d, void* pred_d, void* score_d);
+int smn_rng_variates(smn_ctx* ctx, int dtype, uint64_t seed, double df, int64_t point0, int64_t npoints, int64_t C,
+                     int64_t S, void* out_d);
+int smn_debug_philox(smn_ctx* ctx, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other
  * ranks by any host channel; every rank then calls smn_comm_init.  smn_allgather is an RCCL

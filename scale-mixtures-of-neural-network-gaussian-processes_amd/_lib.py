@@ -94,6 +94,11 @@ PROTOTYPES = {
     "smn_spr_loss_grad_batch": [_vp, _i, _i, _i, _i, _i, _pd, _pd, _pd, _vp, _i64, _i64, _i64, _vp, _pd, _pd, _pd, _pd, _pd, _pi, _pd],
     "smn_kernel_cnn_grad_terms": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _d, _pd],
     "smn_spr_cnn_loss_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _d, _d, _d, _pd, _pd, _pi, _pd],
+    "smn_kernel_conv_diag": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp],
+    "smn_svsp_moments": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _d, _vp, _vp, _pi, _pi64],
+    "smn_mc_softmax": [_vp, _i, _vp, _vp, _pi, _i64, _i64, _i64, _d, C.c_uint64, _i64, _vp, _vp, _vp, _vp],
+    "smn_rng_variates": [_vp, _i, C.c_uint64, _d, _i64, _i64, _i64, _i64, _vp],
+    "smn_debug_philox": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "smn_comm_init": [_vp, _i, _i, C.c_char_p],
     "smn_comm_destroy": [_vp],
     "smn_allgather": [_vp, _i, _i, _vp, _vp, _i64],

@@ -10,6 +10,11 @@ A reference run directory holds
 component of their name (a, b, w_std, b_std, last_w_std, eps | diag_reg), and rebuilds the SPR model.
 This module reads and writes the same layout, so hyper-parameters trained by the reference can be
 evaluated by this engine and vice versa.  Host-only except ``restore_spr`` (the model uploads X).
+
+Classification runs (``experiments/classification/train.py`` / ``test.py:83-144``) use the same layout with the
+variables of SVSP: ``inducing_variable`` [I,H,W,C], ``q_mu`` [C,I], ``q_sqrt`` [C,I] (raw), ``w_std``, ``b_std``,
+``last_w_std``, ``eps`` and, for svtp, ``a`` / ``b``; ``read_svsp_run`` / ``restore_svsp`` read them.  Their ``meta.npy``
+is the pickled ``vars(args)`` itself (``classification/train.py:247``), without the ``args`` wrapper of the regression runs.
 """
 from __future__ import annotations
 
@@ -19,7 +24,8 @@ import os
 import numpy as np
 
 __all__ = ["save_var_collection", "load_var_collection", "get_from_vars", "Checkpointer", "save_meta",
-           "load_meta", "latest_index", "read_run", "restore_spr"]
+           "load_meta", "latest_index", "read_run", "restore_spr", "read_svsp_run", "restore_svsp", "save_svsp_meta",
+           "load_svsp_meta"]
 
 FILE_MATCH = "*.npz"
 FILE_FORMAT = "{:03d}.npz"
@@ -160,4 +166,88 @@ def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtyp
             model.likelihood.a.assign(raw["a"])
         if raw["b"] is not None:
             model.likelihood.b.assign(raw["b"])
+    return model, context
+
+
+SVSP_KEYS = ("a", "b", "w_std", "b_std", "last_w_std", "inducing_variable", "q_mu", "q_sqrt", "eps")
+
+
+def save_svsp_meta(ckpt_dir, args):
+    """meta.npy as experiments/classification/train.py:247 writes it: the run's argument dict itself, pickled -- NOT wrapped
+    in ``dict(args=...)`` as the regression runs' is (``save_meta``)."""
+    np.save(os.path.join(ckpt_dir, "meta.npy"), dict(args))
+
+
+def load_svsp_meta(ckpt_dir):
+    """The argument dict of a classification run (experiments/classification/test.py:84 reads ``.item()`` and indexes it
+    directly).  A dict that holds nothing but an ``args`` dict -- the regression layout -- is unwrapped too.  meta.npy is a
+    pickle: only load run directories you trust."""
+    meta = np.load(os.path.join(ckpt_dir, "meta.npy"), allow_pickle=True).item()
+    if set(meta) == {"args"} and isinstance(meta["args"], dict):
+        return meta["args"]
+    return meta
+
+
+def read_svsp_run(ckpt_dir, ckpt_index=None):
+    """(raw variable dict, context args) of a classification run directory, as experiments/classification/test.py:83-105
+    reads it: variables matched by the last dotted component, a missing ``last_w_std`` taken from the run's arguments.
+    ``eps`` is returned when stored (raw), but see ``restore_svsp``: the reference's test script never uses it."""
+    if ckpt_index is None:
+        ckpt_index = latest_index(ckpt_dir)
+    saved = load_var_collection(os.path.join(ckpt_dir, FILE_FORMAT.format(ckpt_index)))
+    context = load_svsp_meta(ckpt_dir)
+    raw = {k: get_from_vars(saved, k) for k in SVSP_KEYS}
+    if raw["last_w_std"] is None:
+        raw["last_w_std"] = np.array(context["last_w_std"], dtype=np.float64)   # test.py:104-105, taken as the raw value
+    for k in ("inducing_variable", "q_mu", "q_sqrt", "w_std", "b_std"):
+        if raw[k] is None:
+            raise KeyError("checkpoint %r holds no variable named %r" % (ckpt_dir, k))
+    return raw, context
+
+
+def restore_svsp(ckpt_dir, ckpt_index=None, eps=None, dtype=np.float64):
+    """experiments/classification/test.py:83-144: rebuild the SVSP classifier of a run directory for evaluation.
+    ``method`` is "svgp" (GaussianPrior) or "svtp" (InverseGammaPrior(alpha, beta) of the run's arguments, a / b from the
+    checkpoint); ``network`` "cnn" selects get_cnn_kernel, anything else get_conv_resnet_kernel (as test.py does).
+
+    A quirk kept on purpose: test.py never restores ``eps`` -- it evaluates every run at the constructor default 1e-6,
+    whatever the run trained or stored.  ``eps=None`` reproduces that; ``eps="stored"`` assigns the checkpoint's raw
+    value, a float sets it.  Resizing test images to the inducing images' shape is the caller's job."""
+    from . import nt_kernels
+    from .spax.kernels import NNGPKernel
+    from .spax.models import SVSP
+    from .spax.priors import GaussianPrior, InverseGammaPrior
+    raw, context = read_svsp_run(ckpt_dir, ckpt_index)
+    method, network = context["method"], context["network"]
+    num_hiddens, activation = context["num_hiddens"], context["activation"]
+    base_kernel_fn = nt_kernels.get_cnn_kernel if network == "cnn" else nt_kernels.get_conv_resnet_kernel
+    q_mu = np.asarray(raw["q_mu"], dtype=np.float64)
+    num_class = q_mu.shape[0]
+
+    def get_kernel_fn(w_std, b_std, last_w_std):
+        return base_kernel_fn(num_hiddens, num_class, activation, w_std=w_std, b_std=b_std, last_w_std=last_w_std)
+
+    kernel = NNGPKernel(get_kernel_fn, 1.0, 1.0, 1.0)
+    if method == "svgp":
+        prior = GaussianPrior()
+    elif method == "svtp":
+        prior = InverseGammaPrior(context["alpha"], context["beta"])
+    else:
+        raise ValueError("Unsupported method '%s'" % method)
+    kw = {} if eps is None or eps == "stored" else dict(eps=float(eps))
+    model = SVSP(prior, kernel, np.asarray(raw["inducing_variable"]), num_latent_gps=num_class, dtype=dtype, **kw)
+    model.kernel.w_std.assign(raw["w_std"])
+    model.kernel.b_std.assign(raw["b_std"])
+    model.kernel.last_w_std.assign(raw["last_w_std"])
+    model.q_mu.assign(q_mu)
+    model.q_sqrt.assign(raw["q_sqrt"])
+    if method == "svtp":
+        if raw["a"] is not None:
+            model.prior.a.assign(raw["a"])
+        if raw["b"] is not None:
+            model.prior.b.assign(raw["b"])
+    if isinstance(eps, str) and eps == "stored":
+        if raw["eps"] is None:
+            raise KeyError("checkpoint %r stores no eps" % ckpt_dir)
+        model.eps.assign(raw["eps"])
     return model, context

@@ -599,7 +599,33 @@ int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, cons
   return SMN_OK;
 }
 
+template <typename T>
+int cnn_diag_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, const void* x, int64_t n, int64_t H, int64_t W,
+               int64_t C, void* diag) {
+  ConvProg p{act, layers, (int)H, (int)W, (int)C, w * w, b * b, lw * lw};
+  const size_t lds_q = (2 * (size_t)(H + 2) * (W + 2) + 256) * sizeof(double);
+  if (lds_q > 160 * 1024)
+    return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: image %lldx%lld too large for the on-chip map", (long long)H, (long long)W);
+  void* tv = nullptr;   // the factor tables the pass writes beside the diagonal: scratch here
+  SMN_TRY(smn_workspace(ctx, 1, sizeof(T) * (size_t)n * (size_t)(layers > 0 ? layers : 1) * (size_t)(H * W) + 64, &tv));
+  {
+    ProfScope ps(ctx, PROF_PREP, ctx->stream);
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(conv_q_kernel<T>), lds_q));
+    hipLaunchKernelGGL(conv_q_kernel<T>, dim3((unsigned)n), dim3(256), lds_q, ctx->stream, static_cast<const T*>(x), n, p,
+                       static_cast<T*>(tv), static_cast<T*>(diag), 0, static_cast<T*>(nullptr));
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
 }  // namespace
+
+int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,
+             int64_t H, int64_t W, int64_t C, void* diag_d) {
+  if (H * W > 64 * kMaxPix) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: H*W > %d", 64 * kMaxPix);
+  if (dtype == SMN_F64) return cnn_diag_t<double>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
+  return cnn_diag_t<float>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
+}
 
 extern "C" int smn_kernel_cnn(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                               double last_w_std, const void* x1_d, int64_t n1, const void* x2_d, int64_t n2, int64_t H,

@@ -373,7 +373,37 @@ int resnet_t(smn_ctx* ctx, int act, int block_size, double w, double b, double l
   return SMN_OK;
 }
 
+template <typename T>
+int resnet_diag_t(smn_ctx* ctx, int act, int block_size, double w, double b, double lw, const void* x, int64_t n, int64_t H,
+                  int64_t W, int64_t C, void* diag) {
+  NetProg p{};
+  p.act = act; p.H = (int)H; p.W = (int)W; p.C = (int)C;
+  p.w2 = w * w; p.b2 = b * b; p.lw2 = lw * lw;
+  const int tab = build_prog(&p, block_size, (int)H, (int)W);
+  if (tab == -1) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: block_size %d needs more than %d ops", block_size, kMaxOps);
+  if (tab == -2) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: image size %lldx%lld is not divisible by the strides (needs multiples of 8)", (long long)H, (long long)W);
+  const size_t lds_q = (3 * (size_t)(H + 2) * (W + 2) + 256) * sizeof(double);
+  if (lds_q > 160 * 1024)
+    return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: image %lldx%lld too large for the on-chip maps", (long long)H, (long long)W);
+  void* tv = nullptr;   // the factor tables the pass writes beside the diagonal: scratch here
+  SMN_TRY(smn_workspace(ctx, 1, sizeof(T) * (size_t)n * (size_t)tab + 64, &tv));
+  {
+    ProfScope ps(ctx, PROF_PREP, ctx->stream);
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(resnet_q_kernel<T>), lds_q));
+    hipLaunchKernelGGL(resnet_q_kernel<T>, dim3((unsigned)n), dim3(256), lds_q, ctx->stream, static_cast<const T*>(x), p,
+                       static_cast<T*>(tv), static_cast<T*>(diag));
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
 }  // namespace
+
+int conv_resnet_diag(smn_ctx* ctx, int dtype, int act, int block_size, double w, double b, double lw, const void* x_d,
+                     int64_t n, int64_t H, int64_t W, int64_t C, void* diag_d) {
+  if (dtype == SMN_F64) return resnet_diag_t<double>(ctx, act, block_size, w, b, lw, x_d, n, H, W, C, diag_d);
+  return resnet_diag_t<float>(ctx, act, block_size, w, b, lw, x_d, n, H, W, C, diag_d);
+}
 
 extern "C" int smn_kernel_conv_resnet(smn_ctx* ctx, int dtype, int act, int block_size, double w_std, double b_std,
                                       double last_w_std, const void* x1_d, int64_t n1, const void* x2_d, int64_t n2,

@@ -35,7 +35,7 @@ struct smn_ctx {
   size_t ev_pool_used = 0;
   std::string err;
   // cached workspace arenas (grown on demand, freed with the context)
-  static constexpr int kSlots = 10;
+  static constexpr int kSlots = 12;
   void* ws[kSlots] = {};
   size_t ws_bytes[kSlots] = {};
   // small device scalar block: [0..15] doubles scratch, ints after

@@ -181,3 +181,10 @@ int transpose_flip(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* 
 int allgather_piece_on(smn_ctx* ctx, hipStream_t st, int dtype, const void* mine_d, void* stage_d, const ColPieces& cp, int g);
 int scatter_piece_on(smn_ctx* ctx, hipStream_t st, int dtype, const void* stage_d, int64_t n, const ColPieces& cp, int g,
                      void* k_d, int64_t ldk, double diag_add);
+
+// K(x_i, x_i) for i < n: the per-image pass of smn_kernel_cnn / smn_kernel_conv_resnet alone (cnn.hip / cnn_resnet.hip), the
+// same launch that fills the diagonal of their symmetric build, so the values are those bits.  diag_d [n] of `dtype`.
+int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,
+             int64_t H, int64_t W, int64_t C, void* diag_d);
+int conv_resnet_diag(smn_ctx* ctx, int dtype, int act, int block_size, double w, double b, double lw, const void* x_d,
+                     int64_t n, int64_t H, int64_t W, int64_t C, void* diag_d);

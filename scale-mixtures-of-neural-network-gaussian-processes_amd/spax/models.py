@@ -1,5 +1,6 @@
-"""spax/models.py mirror — SPR (exact GP / Student-t process regression).  SVSP is out of scope
-(sparse variational classifier: SURVEY.md section 2, row 7)."""
+"""spax/models.py mirror — SPR (exact GP / Student-t process regression) and the EVALUATION half of SVSP (the sparse
+variational scale-mixture classifier: test_acc_nll / evaluate).  Training SVSP -- its loss needs reverse-mode gradients
+through the conv kernel with respect to the inducing images -- is not part of this engine: SVSP.loss raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,11 +10,12 @@ import numpy as np
 from .. import _lib
 from .._lib import DeviceArray, as_device
 from ..nt_kernels import CnnKernelFn, KernelFn
-from .base import ConstraintTrainVar, Module
+from .base import ConstraintTrainVar, Module, TrainVar
 from .bijectors import positive
+from .priors import split_key
 from .utils import jitter
 
-__all__ = ["SPR", "grad_route", "lml_value_and_grads"]
+__all__ = ["SPR", "SVSP", "grad_route", "lml_value_and_grads"]
 
 
 def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
@@ -198,3 +200,129 @@ class SPR(Module):
         )
         ll = np.mean(log_prob)
         return -ll
+
+
+class SVSP(Module):
+    """spax/models.py:9-78: sparse variational GP / Student-t process classifier over `num_latent_gps` classes, with the
+    reference's constructor, trainables (inducing_variable, q_mu, q_sqrt, eps) and `test_acc_nll`.
+
+    Everything that grows with the data runs on the device: the cross kernel K(Z, x) and the per-image diagonal
+    K(x_t, x_t) of the conv kernels, the posterior moments (smn_svsp_moments; the I x I side in fp64 whatever `dtype` is), and
+    the Monte-Carlo softmax head (smn_mc_softmax), which draws its S variates per (point, class) in registers.  Between the
+    last two the host turns the T x C variances into sigma = sqrt(scale * var) (one small download and upload per batch).
+    The reference's [B,B] test
+    covariance is never formed: sample_f_iid reads its diagonal only, so every point is independent of its batch.
+    `dtype` is the precision of the images, the cross kernel, the moments and the head's arithmetic.
+    K(Z, Z) is kept per (kernel, hyper-parameters, CONTENT of the inducing images): it is I^2 image pairs.  The two I x I
+    factorisations are not kept: smn_svsp_moments redoes them in every call, a few launches at I = 200."""
+
+    def __init__(self, prior, kernel, inducing_variable, *, num_latent_gps: int = 1, eps: float = 1e-6, dtype=np.float64):
+        super().__init__()
+        self.prior = prior
+        self.kernel = kernel
+        self.num_latent_gps = int(num_latent_gps)
+        self.inducing_variable = TrainVar(np.asarray(inducing_variable))
+        self.num_inducing = self.inducing_variable.value.shape[0]
+        self.q_mu = TrainVar(np.zeros((self.num_latent_gps, self.num_inducing)))
+        self.q_sqrt = ConstraintTrainVar(np.ones((self.num_latent_gps, self.num_inducing)), constraint=positive())
+        self.eps = ConstraintTrainVar(eps, constraint=positive())
+        self.dtype = np.dtype(dtype)
+        _lib.dtype_code(self.dtype)                               # float32 / float64 only
+        self._kzz_cache = None
+
+    def loss(self, key, x_batch, y_batch, num_train, num_samples, aux=False):
+        raise NotImplementedError("SVSP.loss (the negative ELBO) needs gradients with respect to the inducing images; this "
+                                  "engine evaluates trained SVSP models only (test_acc_nll / evaluate)")
+
+    # ---- device state that depends on the kernel hyper-parameters and the inducing images only
+    def inducing_state(self, kernel_fn=None, ctx=None, refresh=False):
+        """(Z on the device in the model's dtype, K(Z, Z) on the device in fp64) at the current hyper-parameters.  Kept between
+        calls; whether the kept pair still belongs to the inducing images is decided by comparing their content with a copy
+        (an array edited in place, or another one at a recycled address, is seen).  refresh: rebuild regardless."""
+        kernel_fn = kernel_fn or self.kernel.get_kernel_fn()
+        ctx = ctx or _lib.default_context()
+        if not isinstance(kernel_fn, CnnKernelFn):
+            raise NotImplementedError("SVSP evaluation is wired for get_cnn_kernel / get_conv_resnet_kernel (the kernels "
+                                      "of experiments/classification); got %s" % type(kernel_fn).__name__)
+        z_host = self.inducing_variable.value
+        if z_host.ndim != 4:
+            raise ValueError("inducing_variable must be [I,H,W,C] images")
+        key = (kernel_fn.entry, tuple(kernel_fn.params), z_host.shape, ctx)
+        hit = self._kzz_cache
+        if not refresh and hit is not None and hit[0] == key and np.array_equal(hit[3], z_host):
+            return hit[1], hit[2]
+        z64 = ctx.to_device(np.ascontiguousarray(z_host, dtype=np.float64))
+        k_zz = kernel_fn(z64, None, get="nngp")                   # fp64, full, whatever the model's dtype
+        z = z64 if self.dtype == np.float64 else ctx.to_device(np.ascontiguousarray(z_host, dtype=self.dtype))
+        self._kzz_cache = (key, z, k_zz, z_host.copy())
+        return z, k_zz
+
+    def posterior_moments(self, x_batch, ctx=None):
+        """(mean [T,C], var [T,C]) device arrays of the latent function at x_batch, info, number of var entries <= 0."""
+        ctx = ctx or (x_batch.ctx if isinstance(x_batch, DeviceArray) else _lib.default_context())
+        kernel_fn = self.kernel.get_kernel_fn()
+        z, k_zz = self.inducing_state(kernel_fn, ctx)
+        x = as_device(x_batch, ctx, dtype=self.dtype)
+        if len(x.shape) != 4 or tuple(x.shape[1:]) != tuple(z.shape[1:]):
+            raise ValueError("x_batch %s does not have the shape of the inducing images %s (resizing is the caller's job)"
+                             % (tuple(x.shape), tuple(z.shape[1:])))
+        t, (n_i, c) = x.shape[0], (self.num_inducing, self.num_latent_gps)
+        q_mu = np.asarray(self.q_mu.value, dtype=np.float64)
+        q_var = np.asarray(self.q_sqrt.constraint(self.q_sqrt.value), dtype=np.float64)   # diag(q_sqrt) itself: not squared
+        if q_mu.shape != (c, n_i) or q_var.shape != (c, n_i):
+            raise ValueError("q_mu / q_sqrt must be [num_latent_gps, num_inducing] = %s" % ((c, n_i),))
+        k_zt = kernel_fn(z, x, get="nngp")                        # [I,T]
+        ktt = ctx.empty((t,), self.dtype)
+        act, depth, w, b, lw = kernel_fn.params
+        ctx.call("smn_kernel_conv_diag", x.dcode, 0 if kernel_fn.entry == "smn_kernel_cnn" else 1, act, depth, w, b, lw,
+                 x.ptr, t, x.shape[1], x.shape[2], x.shape[3], ktt.ptr)
+        mean, var = ctx.empty((t, c), self.dtype), ctx.empty((t, c), self.dtype)
+        info, nonpos = C.c_int(), C.c_int64()
+        q_mu_d, q_var_d = ctx.to_device(q_mu), ctx.to_device(q_var)                        # fp64 whatever the model's dtype
+        ctx.call("smn_svsp_moments", x.dcode, k_zz.ptr, k_zt.ptr, ktt.ptr, q_mu_d.ptr, q_var_d.ptr, n_i, t, c,
+                 self.eps.safe_value, mean.ptr, var.ptr, C.byref(info), C.byref(nonpos))
+        return mean, var, info.value, nonpos.value
+
+    def predict_scores(self, key, x_batch, y_batch, num_samples):
+        """Per point: (log-likelihood of the label [T], predicted class [T], class scores [T,C]) as host arrays."""
+        seed, point0 = split_key(key)
+        mean, var, _, _ = self.posterior_moments(x_batch)
+        ctx = mean.ctx
+        t, c = mean.shape
+        labels = np.ascontiguousarray(np.asarray(y_batch).reshape(-1), dtype=np.int32)
+        if labels.shape[0] != t:
+            raise ValueError("y_batch has %d labels for %d points" % (labels.shape[0], t))
+        df, scale = self.prior.head_params()
+        with np.errstate(invalid="ignore"):
+            sigma = ctx.to_device(np.sqrt(scale * var.raw_numpy()).astype(self.dtype))    # NaN where var < 0, as the reference
+        ll, score = ctx.empty((t,), np.float64), ctx.empty((t, c), np.float64)
+        pred_d = C.c_void_p()
+        ctx.call("smn_malloc", max(4 * t, 16), C.byref(pred_d))
+        try:
+            ctx.call("smn_mc_softmax", mean.dcode, mean.ptr, sigma.ptr, labels.ctypes.data_as(C.POINTER(C.c_int)), t, c,
+                     int(num_samples), df, seed, point0, None, ll.ptr, pred_d, score.ptr)
+            pred = np.empty(t, dtype=np.int32)
+            ctx.call("smn_memcpy_d2h", pred.ctypes.data_as(C.c_void_p), pred_d, 4 * t)
+        finally:
+            ctx.call("smn_free", pred_d)
+        return ll.raw_numpy(), pred, score.raw_numpy()
+
+    # ---- spax/models.py:58-78
+    def test_acc_nll(self, key, x_batch, y_batch, num_samples):
+        """(nll, correct_count) of one batch.  `key`: int seed or (seed, global index of the batch's first point)."""
+        ll, pred, _ = self.predict_scores(key, x_batch, y_batch, num_samples)
+        return float(-np.mean(ll)), int(np.sum(pred == np.asarray(y_batch).reshape(-1)))
+
+    def evaluate(self, x, y, num_samples, seed=10, batch=None):
+        """experiments/classification/test.py:45-57 (test_epoch) over a whole set -> (nll, accuracy in percent).  The set
+        is cut into chunks of `batch` points for memory only: a point's variates are keyed by its global index, so the
+        result does not depend on the chunking."""
+        n = len(y)
+        batch = int(batch) if batch else 2500
+        nll_sum, correct = 0.0, 0
+        for i0 in range(0, n, batch):
+            i1 = min(n, i0 + batch)
+            nll, cc = self.test_acc_nll((seed, i0), x[i0:i1], y[i0:i1], num_samples)
+            nll_sum += nll * (i1 - i0)
+            correct += cc
+        return nll_sum / n, correct * 100.0 / n
