@@ -380,6 +380,57 @@ int smn_rng_variates(smn_ctx* ctx, int dtype, uint64_t seed, double df, int64_t 
                      int64_t S, void* out_d);
 int smn_debug_philox(smn_ctx* ctx, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* ---- sparse variational classifier, training (spax/models.py:30-56 SVSP.loss; spax/priors.py:21-26,36-42,52-58,70-82;
+ *      experiments/classification/train.py:61-75) ----
+ * The negative ELBO and its analytic gradient with respect to every trainable except the inducing images.  U = [Z; x] (I inducing
+ * and B batch images), K = K(U,U), q_var = diag(q_sqrt) as above, scale = 1 / s = 1 (GaussianPrior) or b/a / a/b
+ * (InverseGammaPrior), df = 2a, N = num_train:
+ *     K_abs = K_ZZ + eps I     K_rel = K_ZZ + eps tr(K_ZZ)/I I     Kinv = K_abs^-1     A = K_xZ Kinv     P = K_rel^-1 K_Zx
+ *     mean[c] = A q_mu[c]  (K_abs here; the evaluation path uses K_rel: the reference's own difference)
+ *     cov[c]  = A diag(q_var[c]) A^T + K_xx - K_xZ P          L_c = chol(scale cov[c])
+ *     f[c,b,s] = mean[c,b] + sum_k L_c[b,k] xi[c,k,s]         xi[c,k,s] = the variate of (seed, point0 + k, class c, draw s)
+ *     ll = mean_{b,s} log_softmax_c(f)[y_b,b,s]
+ *     kl = 1/2 (C logdet K_ZZ [no jitter] - sum log q_var - I C + sum_c sum_i Kinv_ii q_var[c,i] + s sum_c q_mu[c]^T Kinv q_mu[c])
+ *     loss = -ll + kl / N   (+ the closed-form inverse-gamma terms of priors.py:78-81, which the host adds)
+ * The Student-t variates are iid per (class, point, draw) (priors.py:52-58 through utils.py multivariate_t: NOT a multivariate t);
+ * their pathwise derivative in df (Bailey's polar method at fixed (u, v)) replaces the implicit gamma gradient of JAX's random.t.
+ *
+ * smn_rng_variates_ddf: out_d [npoints,C,S] = exactly what smn_rng_variates returns, dout_d [npoints,C,S] = d out / d df
+ *   (zeros for df <= 0):  dt/ddf = t/2 [1/df + (2 ln w / df^2) w^(-2/df) / (w^(-2/df) - 1)].
+ * smn_svsp_head_grad: mean_d [C,B], cov_d [C,B,B] (lower triangles read), gmean_d [C,B], gcov_d [C,B,B] (symmetric, full) are
+ *   ALWAYS fp64; labels_h [B] host int32, validated.  Out: *ll_h; gmean = d(-ll)/d mean; gcov = d(-ll)/d cov through the
+ *   reverse-mode Cholesky (Phi = tril(L^T gL) with the diagonal halved, gS = sym(L^-T Phi L^-1), gcov = scale gS);
+ *   *gscale_h = d(-ll)/d scale = sum_c <gS_c, cov[c]>; *dfterm_h = sum gf[c,b,s] L_c[b,k] d xi[c,k,s]/d df (0 for df <= 0), the
+ *   pathwise part of d(-ll)/d df.  noise_d NULL, or [C,B,S] standard variates of `dtype` used instead of the generator, with
+ *   dnoise_d NULL (zeros) or their df-derivatives.  `dtype` selects the arithmetic of the variates and of the exponentials:
+ *   f_c - max_c f is rounded to `dtype` once and exp / log are `dtype`'s, so that every softmax entry is within a few units of
+ *   `dtype`'s roundoff of the exact one in ABSOLUTE terms, whatever the level of f.  The factors, the sums over k (f itself), s
+ *   and c, and every gradient are fp64, in a fixed order (no floating-point atomics): two calls give the same bits.  1 <= C <= SMN_SVSP_MAX_CLASSES; B > SMN_SVSP_MAX_BATCH: SMN_ENOTSUP.
+ *   A cov[c] that is not positive definite (a pivot non-positive or below B * 2^-52 * max_j cov_jj): *info_h > 0, NaN outputs,
+ *   SMN_OK.  Synchronises.
+ * smn_svsp_elbo_grad: k_d [I+B, I+B] (ld = ldk, full), q_mu_d, q_var_d [C,I], g_q_mu_d, g_q_var_d [C,I], gbar_d [I+B, I+B]
+ *   (ld = ldg) ALWAYS fp64; `dtype` is the head's.  Out: *nll_h = -ll, *kl_n_h = kl / N, g q_mu, g q_var (with respect to q_var,
+ *   not the raw q_sqrt), *g_eps_h, *gscale_h (as above), *g_s_h = d loss / d s, *dfterm_h, and Gbar = d loss / d K, symmetric
+ *   with both triangles filled, so that sum_ij Gbar_ij dK_ij/d theta is d loss / d theta for a kernel hyper-parameter:
+ *   smn_kernel_cnn_grad_terms over the I + B images with neg_kinv_d = Gbar, alpha_d = zeros, coef = 0 gives it for w_std, b_std
+ *   and last_w_std, and a reverse-mode conv kernel seeded with Gbar would give the inducing-image gradient (not part of this
+ *   library yet).  Three I x I factorisations (K_ZZ, K_abs, K_rel) through the library's Cholesky; *info_h > 0 (first bad
+ *   pivot of K_ZZ, K_abs, K_rel, then of the head) with NaN outputs and SMN_OK when one is not positive definite.  One
+ *   synchronisation, at the end. */
+#define SMN_SVSP_MAX_BATCH 256
+int smn_rng_variates_ddf(smn_ctx* ctx, int dtype, uint64_t seed, double df, int64_t point0, int64_t npoints, int64_t C,
+                         int64_t S, void* out_d, void* dout_d);
+int smn_svsp_head_grad(smn_ctx* ctx, int dtype, const void* mean_d, const void* cov_d, const int* labels_h,
+                       int64_t B, int64_t C, int64_t S, double df, double scale, uint64_t seed, int64_t point0,
+                       const void* noise_d, const void* dnoise_d, double* ll_h, void* gmean_d, void* gcov_d,
+                       double* gscale_h, double* dfterm_h, int* info_h);
+int smn_svsp_elbo_grad(smn_ctx* ctx, int dtype, const void* k_d, int64_t ldk, int64_t I, int64_t B, int64_t C,
+                       const void* q_mu_d, const void* q_var_d, double eps, double s, double num_train,
+                       const int* labels_h, int64_t S, double df, double scale, uint64_t seed, int64_t point0,
+                       const void* noise_d, const void* dnoise_d, double* nll_h, double* kl_n_h, void* g_q_mu_d,
+                       void* g_q_var_d, double* g_eps_h, double* gscale_h, double* g_s_h, double* dfterm_h,
+                       void* gbar_d, int64_t ldg, int* info_h);
+
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other
  * ranks by any host channel; every rank then calls smn_comm_init.  smn_allgather is an RCCL

@@ -1,6 +1,8 @@
-"""spax/models.py mirror — SPR (exact GP / Student-t process regression) and the EVALUATION half of SVSP (the sparse
-variational scale-mixture classifier: test_acc_nll / evaluate).  Training SVSP -- its loss needs reverse-mode gradients
-through the conv kernel with respect to the inducing images -- is not part of this engine: SVSP.loss raises."""
+"""spax/models.py mirror — SPR (exact GP / Student-t process regression) and SVSP (the sparse variational scale-mixture
+classifier): evaluation (test_acc_nll / evaluate) and the training loss with its analytic gradient (loss_and_grad) with
+respect to every trainable except the inducing images -- that one needs a reverse-mode pass through the conv kernel,
+which the engine does not have yet; loss_and_grad hands out its seed, d loss / d K.  SVSP.loss itself (a value for an
+autodiff framework to differentiate) still raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -231,8 +233,92 @@ class SVSP(Module):
         self._kzz_cache = None
 
     def loss(self, key, x_batch, y_batch, num_train, num_samples, aux=False):
-        raise NotImplementedError("SVSP.loss (the negative ELBO) needs gradients with respect to the inducing images; this "
-                                  "engine evaluates trained SVSP models only (test_acc_nll / evaluate)")
+        raise NotImplementedError("SVSP.loss is a value for an autodiff framework to differentiate; this engine returns the "
+                                  "negative ELBO together with its analytic gradient: SVSP.loss_and_grad")
+
+    def loss_and_grad(self, key, x_batch, y_batch, num_train, num_samples, *, kernel_grads=True, aux=False, return_gbar=False):
+        """(n_elbo, {variable name: d n_elbo / d RAW value}) of spax/models.py:30-56 -- the analytic counterpart of
+        objax.GradValues(model.loss, train_vars) in experiments/classification/train.py:61-75 -- for every trainable except
+        the inducing images: q_mu and q_sqrt (arrays [C,I]), eps, w_std, b_std, last_w_std and, for InverseGammaPrior, a, b.
+        `inducing_variable` never appears in the result.  aux=True appends (-ll, kl / num_train) as the reference's aux does.
+
+        One symmetric fp64 build of K over [Z; x_batch], one smn_svsp_elbo_grad (forward, correlated Monte-Carlo softmax
+        head, reverse pass; leaves d loss / d K on the device) and, with kernel_grads, one forward-mode tangent pass
+        (smn_kernel_cnn_grad_terms) that contracts d loss / d K with dK / d(w_std, b_std, last_w_std).  That pass exists for
+        get_cnn_kernel and images of up to 1024 pixels: anything else raises NotImplementedError with kernel_grads=True;
+        kernel_grads=False works for both conv kernels and omits the three kernel entries (the others are the same bits).
+        The closed-form inverse-gamma terms, (a, b) -> (df, scale, s) and the softplus chain rule are host arithmetic.
+        `key` as in test_acc_nll: an int seed or (seed, global index of the batch's first point).  The model's `dtype`
+        selects the arithmetic of the head's variates and exponentials; everything else is fp64.
+        return_gbar=True appends the device array d loss / d K [I+B, I+B] (what a reverse-mode conv kernel would consume).
+        A matrix that is not positive definite gives NaN for the loss and every gradient."""
+        seed, point0 = split_key(key)
+        kernel_fn = self.kernel.get_kernel_fn()
+        if not isinstance(kernel_fn, CnnKernelFn):
+            raise NotImplementedError("SVSP is wired for get_cnn_kernel / get_conv_resnet_kernel; got %s" % type(kernel_fn).__name__)
+        z_host = np.asarray(self.inducing_variable.value, dtype=np.float64)
+        x_host = x_batch.numpy() if isinstance(x_batch, DeviceArray) else np.asarray(x_batch)
+        x_host = np.asarray(x_host, dtype=np.float64)
+        if z_host.ndim != 4 or x_host.ndim != 4 or x_host.shape[1:] != z_host.shape[1:]:
+            raise ValueError("x_batch %s does not have the shape of the inducing images %s" % (x_host.shape, z_host.shape[1:]))
+        if kernel_grads and (kernel_fn.entry != "smn_kernel_cnn" or z_host.shape[1] * z_host.shape[2] > 1024):
+            raise NotImplementedError("kernel_grads=True needs get_cnn_kernel and images of at most 1024 pixels (the tangent "
+                                      "pass of smn_kernel_cnn_grad_terms); pass kernel_grads=False")
+        ctx = (x_batch.ctx if isinstance(x_batch, DeviceArray) else None) or kernel_fn.ctx or _lib.default_context()
+        n_i, n_b, c = self.num_inducing, x_host.shape[0], self.num_latent_gps
+        labels = np.ascontiguousarray(np.asarray(y_batch).reshape(-1), dtype=np.int32)
+        if labels.shape[0] != n_b:
+            raise ValueError("y_batch has %d labels for %d points" % (labels.shape[0], n_b))
+        q_mu = np.ascontiguousarray(self.q_mu.value, dtype=np.float64)
+        q_raw = np.asarray(self.q_sqrt.value, dtype=np.float64)
+        q_var = np.ascontiguousarray(self.q_sqrt.constraint(q_raw), dtype=np.float64)    # diag(q_sqrt) itself: not squared
+        if q_mu.shape != (c, n_i) or q_var.shape != (c, n_i):
+            raise ValueError("q_mu / q_sqrt must be [num_latent_gps, num_inducing] = %s" % ((c, n_i),))
+        pp = self.prior.elbo_params()
+        eps, n_train = self.eps.safe_value, float(num_train)
+        u = ctx.to_device(np.ascontiguousarray(np.concatenate([z_host, x_host])))         # fp64 whatever the model's dtype
+        k = kernel_fn(u, None, get="nngp")
+        n_u = n_i + n_b
+        q_mu_d, q_var_d = ctx.to_device(q_mu), ctx.to_device(q_var)
+        g_mu_d, g_var_d = ctx.empty((c, n_i), np.float64), ctx.empty((c, n_i), np.float64)
+        gbar = ctx.empty((n_u, n_u), np.float64)
+        nll, kl_n, g_eps, gscale, g_s, dfterm = (C.c_double() for _ in range(6))
+        info = C.c_int()
+        ctx.call("smn_svsp_elbo_grad", _lib.dtype_code(self.dtype), k.ptr, n_u, n_i, n_b, c, q_mu_d.ptr, q_var_d.ptr, eps, pp["s"],
+                 n_train, labels.ctypes.data_as(C.POINTER(C.c_int)), int(num_samples), pp["df"], pp["scale"], seed, point0, None,
+                 None, C.byref(nll), C.byref(kl_n), g_mu_d.ptr, g_var_d.ptr, C.byref(g_eps), C.byref(gscale), C.byref(g_s),
+                 C.byref(dfterm), gbar.ptr, n_u, C.byref(info))
+        names = {id(v): name for name, v in self.vars().items()}
+        grads = {}
+        nll_v, kl_v = nll.value, kl_n.value + pp["kl_extra"] / n_train
+        grads[names[id(self.q_mu)]] = g_mu_d.raw_numpy()
+        grads[names[id(self.q_sqrt)]] = g_var_d.raw_numpy() * self.q_sqrt.constraint.grad(q_raw)
+        d_con = {"eps": (self.eps, g_eps.value)}                                          # d loss / d constrained value
+        if pp["df"] > 0.0:
+            a, b = self.prior.a.safe_value, self.prior.b.safe_value                       # df = 2a, scale = b/a, s = a/b
+            d_con["a"] = (self.prior.a, 2.0 * dfterm.value - gscale.value * b / (a * a) + g_s.value / b + pp["d_extra"]["a"] / n_train)
+            d_con["b"] = (self.prior.b, gscale.value / a - g_s.value * a / (b * b) + pp["d_extra"]["b"] / n_train)
+        if kernel_grads:
+            terms = (C.c_double * 4)()
+            if info.value == 0:
+                act, depth, w, b_, lw = kernel_fn.params
+                zeros = ctx.to_device(np.zeros(n_u))
+                ctx.call("smn_kernel_cnn_grad_terms", _lib.F64, act, depth, w, b_, lw, u.ptr, n_u, u.shape[1], u.shape[2], u.shape[3],
+                         gbar.ptr, n_u, zeros.ptr, 0.0, terms)
+            for i, key_ in enumerate(("w_std", "b_std", "last_w_std")):
+                d_con[key_] = (getattr(self.kernel, key_), terms[i] if info.value == 0 else float("nan"))
+        for var, g in d_con.values():
+            grads[names[id(var)]] = float(g * var.constraint.grad(var.value))
+        value = nll_v + kl_v
+        if info.value != 0:
+            nan = float("nan")
+            value, nll_v, kl_v = nan, nan, nan
+        out = (value, grads)
+        if aux:
+            out += (nll_v, kl_v)
+        if return_gbar:
+            out += (gbar,)
+        return out
 
     # ---- device state that depends on the kernel hyper-parameters and the inducing images only
     def inducing_state(self, kernel_fn=None, ctx=None, refresh=False):

@@ -1,11 +1,14 @@
 """spax/priors.py mirror — the mixing priors of the sparse variational classifier (SVSP): `GaussianPrior` (svgp) and
 `InverseGammaPrior(alpha, beta)` (svtp), with the reference's names and trainables (a, b).
 
-Evaluation only.  `sample_f_iid` (spax/priors.py:28-34, :60-68) is served by the device generator of the library
+`sample_f_iid` (spax/priors.py:28-34, :60-68) is served by the device generator of the library
 (smn_rng_variates: Philox4x32-10, include/smnngp.h); SVSP.test_acc_nll does not even call it -- its head draws the same
 variates in registers -- but the method is kept so that code written against the reference runs.  `sample_f`
-(correlated draws from the full [B,B] covariance) and `kl_divergence` belong to training, which this engine does not
-do for SVSP: they raise NotImplementedError.
+(correlated draws from the full [B,B] covariance) and `kl_divergence` are the two halves of the training loss; the
+engine computes both, with their gradients, inside one device call (SVSP.loss_and_grad -> smn_svsp_elbo_grad), so as
+stand-alone methods they raise NotImplementedError.  `elbo_params` gives that call what it needs from the prior: df,
+scale, s = the weight of the q_mu quadratic form in the KL, and the closed-form inverse-gamma terms with their
+derivatives (priors.py:78-81 of the reference).
 
 `key` is an int seed or a pair (seed, point0), point0 being the global index of the first point of the batch: a variate
 is a function of (seed, global point index, class, draw, df) alone.  Bit parity with a JAX PRNG key is impossible and
@@ -60,17 +63,25 @@ class Prior(Module):
         return ctx.to_device(np.ascontiguousarray(f, dtype=dtype))
 
     def sample_f(self, key, mean, cov, num_samples):
-        raise NotImplementedError("sample_f draws correlated samples for the training loss of SVSP; this engine evaluates "
-                                  "trained SVSP models only (sample_f_iid / SVSP.test_acc_nll)")
+        raise NotImplementedError("sample_f draws correlated samples for the training loss of SVSP; the engine draws them "
+                                  "on the device inside SVSP.loss_and_grad (smn_svsp_head_grad), not as a separate array")
 
     def kl_divergence(self, k_ii, k_ii_inv, q_mu, q_sigma, num_inducing, num_class):
-        raise NotImplementedError("kl_divergence belongs to the training loss of SVSP; this engine evaluates trained SVSP "
-                                  "models only")
+        raise NotImplementedError("kl_divergence belongs to the training loss of SVSP; SVSP.loss_and_grad(..., aux=True) "
+                                  "returns it (divided by num_train) next to the likelihood term")
+
+    def elbo_params(self):
+        """dict(df, scale, s, kl_extra, d_extra) for SVSP.loss_and_grad: kl = kl_gaussian(s) + kl_extra, and d_extra maps a
+        trainable of the prior to d kl_extra / d constrained value."""
+        raise NotImplementedError
 
 
 class GaussianPrior(Prior):
     def head_params(self):
         return 0.0, 1.0
+
+    def elbo_params(self):
+        return dict(df=0.0, scale=1.0, s=1.0, kl_extra=0.0, d_extra={})
 
 
 class InverseGammaPrior(Prior):
@@ -84,3 +95,13 @@ class InverseGammaPrior(Prior):
     def head_params(self):
         a, b = self.a.safe_value, self.b.safe_value
         return 2.0 * a, b / a
+
+    def elbo_params(self):
+        import math
+        from .utils import digamma, trigamma
+        a, b = self.a.safe_value, self.b.safe_value
+        alpha, beta = float(self.alpha), float(self.beta)
+        extra = (alpha * math.log(b / beta) - math.lgamma(a) + math.lgamma(alpha) + (a - alpha) * digamma(a)
+                 + (beta - b) * a / b)                                             # priors.py:78-81
+        return dict(df=2.0 * a, scale=b / a, s=a / b, kl_extra=extra,
+                    d_extra=dict(a=(a - alpha) * trigamma(a) + (beta - b) / b, b=alpha / b - a * beta / (b * b)))

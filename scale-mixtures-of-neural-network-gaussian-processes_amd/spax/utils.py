@@ -79,3 +79,15 @@ def digamma(x):
     f = 1.0 / (x * x)
     return r + math.log(x) - 0.5 / x - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f / 132))))
 
+
+def trigamma(x):
+    """psi'(x) for x > 0: upward recurrence to x >= 10, then the asymptotic series (|error| < 1e-13)."""
+    x = float(x)
+    if not x > 0.0:
+        raise ValueError("trigamma: x must be positive")
+    r = 0.0
+    while x < 10.0:
+        r += 1.0 / (x * x)
+        x += 1.0
+    f = 1.0 / (x * x)
+    return r + 1.0 / x + 0.5 * f + (1.0 / x) * f * (1.0 / 6 - f * (1.0 / 30 - f * (1.0 / 42 - f * (1.0 / 30 - f * 5.0 / 66))))
