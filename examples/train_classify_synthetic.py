@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Training a sparse variational classifier (SVSP, svgp and svtp) on the synthetic image problem of classify_synthetic.py:
-class templates plus noise, inducing images = a subset of the training set (fixed: they have no analytic gradient yet),
-q_mu = 0, q_sqrt = 1 as the constructor leaves them.  Prints the mean nELBO of every epoch, validation NLL and accuracy
+class templates plus noise, inducing images = a subset of the training set (fixed by default; --train-inducing trains them
+too, as the reference does), q_mu = 0, q_sqrt = 1 as the constructor leaves them.  Prints the mean nELBO of every epoch, validation NLL and accuracy
 before and after, and the time of every phase of a step.
 
     python examples/train_classify_synthetic.py [--train 1024] [--valid 512] [--inducing 64] [--hw 8] [--classes 4]
                                                 [--epochs 6] [--batch 64] [--samples 32] [--lr 1e-2] [--dtype float64]
+                                                [--train-inducing]
     python examples/train_classify_synthetic.py --reference-shape [--out FILE]
         # the reference's training shape: I = 200, B = 100, C = 10, S = 100, 32x32x3, 4 layers; both priors, fp32 and fp64
-        # heads, kernel_grads on and off; per-phase and whole-step times (device events of the context's timer)
+        # heads, kernel_grads and inducing_grad on and off; per-phase and whole-step times (device events of the context's timer)
 """
 import argparse
 import ctypes as C
@@ -60,7 +61,8 @@ def device_ms(ctx, fn, repeats=5, warmup=2):
 
 
 def step_phases(model, x, y, num_train, num_samples, head_dtype, repeats=5):
-    """The device phases of one SVSP.loss_and_grad, timed one by one: union build, ELBO forward + reverse, tangent pass."""
+    """The device phases of one SVSP.loss_and_grad, timed one by one: union build, ELBO forward + reverse, tangent pass,
+    reverse pass for the inducing images."""
     ctx = _lib.default_context()
     kernel_fn = model.kernel.get_kernel_fn()
     n_i, c, n_b = model.num_inducing, model.num_latent_gps, len(y)
@@ -99,6 +101,13 @@ def step_phases(model, x, y, num_train, num_samples, head_dtype, repeats=5):
 
     if u.shape[1] * u.shape[2] <= 1024:
         out["tangent pass (3 kernel gradients)"] = device_ms(ctx, tangent, repeats)
+        gz = ctx.empty((n_i,) + tuple(u.shape[1:]), np.float64)
+
+        def reverse():
+            ctx.call("smn_kernel_cnn_input_grad", _lib.F64, act, depth, w, b, lw, u.ptr, n_u, u.shape[1], u.shape[2], u.shape[3],
+                     gbar.ptr, n_u, n_i, gz.ptr)
+
+        out["reverse pass (inducing-image gradient)"] = device_ms(ctx, reverse, repeats)
     return out, info.value, (k, gbar)
 
 
@@ -130,6 +139,8 @@ def reference_shape(args):
             for kg in (True, False):
                 med, mn = device_ms(ctx, lambda: model.loss_and_grad(1, x, y, n_train, s, kernel_grads=kg))
                 say("  %-44s %9.3f ms  [%.3f]" % ("step, kernel_grads=%s" % kg, med, mn))
+            med, mn = device_ms(ctx, lambda: model.loss_and_grad(1, x, y, n_train, s, inducing_grad=True))
+            say("  %-44s %9.3f ms  [%.3f]" % ("step, kernel_grads=True, inducing_grad=True", med, mn))
     # for scale: the same algebra in fp64 NumPy on the host (the rules of the tests, fed the device's K and variates), and what
     # central differences over every scalar trainable would cost in calls of the new path
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -173,6 +184,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--eps", type=float, default=1e-3)
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
+    ap.add_argument("--train-inducing", action="store_true", help="the inducing images are trained too (classification/train.py:205)")
     ap.add_argument("--reference-shape", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -183,11 +195,13 @@ def main():
     ok = True
     for method in ("svgp", "svtp"):
         model = build(method, xt[:args.inducing].copy(), args.classes, args.layers, dtype, args.eps)   # train.py:177-182
-        step = train_svsp.build_svsp_train_step(model, num_train=args.train, num_samples=args.samples)
+        step = train_svsp.build_svsp_train_step(model, train_svsp.svsp_train_vars(model, inducing=args.train_inducing),
+                                                num_train=args.train, num_samples=args.samples)
         sched = train_svsp.PlateauSchedule(args.lr)
         nll0, acc0 = model.evaluate(xv, yv, args.eval_samples)
-        print("%s: %d training images %dx%dx%d, %d inducing, %d classes, batches of %d, S = %d, %s head" %
-              (method, args.train, args.hw, args.hw, args.channels, args.inducing, args.classes, args.batch, args.samples, args.dtype))
+        print("%s: %d training images %dx%dx%d, %d inducing (%s), %d classes, batches of %d, S = %d, %s head" %
+              (method, args.train, args.hw, args.hw, args.channels, args.inducing, "trained" if args.train_inducing else "fixed",
+               args.classes, args.batch, args.samples, args.dtype))
         print("  before: validation NLL %.5f  ACC %.2f" % (nll0, acc0))
         for e in range(args.epochs):
             t0 = time.perf_counter()

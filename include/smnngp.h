@@ -382,7 +382,7 @@ int smn_debug_philox(smn_ctx* ctx, const uint32_t ctr[4], const uint32_t key[2],
 
 /* ---- sparse variational classifier, training (spax/models.py:30-56 SVSP.loss; spax/priors.py:21-26,36-42,52-58,70-82;
  *      experiments/classification/train.py:61-75) ----
- * The negative ELBO and its analytic gradient with respect to every trainable except the inducing images.  U = [Z; x] (I inducing
+ * The negative ELBO and its analytic gradient with respect to every trainable (the inducing images: smn_kernel_cnn_input_grad).  U = [Z; x] (I inducing
  * and B batch images), K = K(U,U), q_var = diag(q_sqrt) as above, scale = 1 / s = 1 (GaussianPrior) or b/a / a/b
  * (InverseGammaPrior), df = 2a, N = num_train:
  *     K_abs = K_ZZ + eps I     K_rel = K_ZZ + eps tr(K_ZZ)/I I     Kinv = K_abs^-1     A = K_xZ Kinv     P = K_rel^-1 K_Zx
@@ -413,8 +413,8 @@ int smn_debug_philox(smn_ctx* ctx, const uint32_t ctr[4], const uint32_t key[2],
  *   not the raw q_sqrt), *g_eps_h, *gscale_h (as above), *g_s_h = d loss / d s, *dfterm_h, and Gbar = d loss / d K, symmetric
  *   with both triangles filled, so that sum_ij Gbar_ij dK_ij/d theta is d loss / d theta for a kernel hyper-parameter:
  *   smn_kernel_cnn_grad_terms over the I + B images with neg_kinv_d = Gbar, alpha_d = zeros, coef = 0 gives it for w_std, b_std
- *   and last_w_std, and a reverse-mode conv kernel seeded with Gbar would give the inducing-image gradient (not part of this
- *   library yet).  Three I x I factorisations (K_ZZ, K_abs, K_rel) through the library's Cholesky; *info_h > 0 (first bad
+ *   and last_w_std, and smn_kernel_cnn_input_grad (below) over the same images with gbar_d = Gbar and n_grad = I gives it for the
+ *   inducing images.  Three I x I factorisations (K_ZZ, K_abs, K_rel) through the library's Cholesky; *info_h > 0 (first bad
  *   pivot of K_ZZ, K_abs, K_rel, then of the head) with NaN outputs and SMN_OK when one is not positive definite.  One
  *   synchronisation, at the end. */
 #define SMN_SVSP_MAX_BATCH 256
@@ -430,6 +430,24 @@ int smn_svsp_elbo_grad(smn_ctx* ctx, int dtype, const void* k_d, int64_t ldk, in
                        const void* noise_d, const void* dnoise_d, double* nll_h, double* kl_n_h, void* g_q_mu_d,
                        void* g_q_var_d, double* g_eps_h, double* gscale_h, double* g_s_h, double* dfterm_h,
                        void* gbar_d, int64_t ldg, int* info_h);
+
+/* ---- reverse mode of the conv-NNGP kernel with respect to its input images (spax/models.py:21,31: SVSP.inducing_variable is
+ *      a TrainVar; experiments/classification/train.py:205 puts model.vars() into the optimiser) ----
+ * smn_kernel_cnn_input_grad: gx_d [n_grad,H,W,C] = sum_ab gbar_ab dK_ab/dx_i for the first n_grad of the n images x_d [n,H,W,C],
+ *   K = smn_kernel_cnn(x, x) with its exact diagonal; the other images are partners only (in SVSP: the batch).  gbar_d [n,n] of
+ *   `dtype` (ld = ldg): only the lower triangle is read and it is taken as symmetric, the convention of
+ *   smn_kernel_cnn_grad_terms, so the Gbar of smn_svsp_elbo_grad goes in unchanged.  One reverse sweep per image pair, one wave
+ *   per (image, slice of its partners); per-element arithmetic in `dtype`, the sums over partners in fp64 and in a fixed order
+ *   (no floating-point atomics: two calls give the same bits).  Workspace: the per-image tables, one slab of forward values
+ *   per resident wave and one block of sums per slice; nothing of size n^2 H W.  fp32 / fp64, relu / erf.
+ *   Limit: H*W <= SMN_CNN_GRAD_MAX_PIXELS whatever the aspect ratio (1 x 1024 included), larger images return SMN_ENOTSUP; no
+ *   limit on num_hiddens (0: the Flatten + Dense of the raw pixel products alone).  b_std == 0 exactly and
+ *   images with all-zero neighbourhoods, or an image that also occurs among the partners, give finite values (zero-variance
+ *   pixels contribute no variance-side term, as above).  1 <= n_grad <= n, ldg >= n (SMN_EINVAL otherwise).  Synchronises. */
+int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                              double w_std, double b_std, double last_w_std,
+                              const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                              const void* gbar_d, int64_t ldg, int64_t n_grad, void* gx_d);
 
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other

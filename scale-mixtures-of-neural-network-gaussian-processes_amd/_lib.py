@@ -93,6 +93,7 @@ PROTOTYPES = {
     "smn_spr_loss_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _d, _d, _d, _pd, _pd, _pi, _pd],
     "smn_spr_loss_grad_batch": [_vp, _i, _i, _i, _i, _i, _pd, _pd, _pd, _vp, _i64, _i64, _i64, _vp, _pd, _pd, _pd, _pd, _pd, _pi, _pd],
     "smn_kernel_cnn_grad_terms": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _d, _pd],
+    "smn_kernel_cnn_input_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp],
     "smn_spr_cnn_loss_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _d, _d, _d, _pd, _pd, _pi, _pd],
     "smn_kernel_conv_diag": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp],
     "smn_svsp_moments": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _d, _vp, _vp, _pi, _pi64],

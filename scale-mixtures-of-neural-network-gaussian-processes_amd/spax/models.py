@@ -1,8 +1,7 @@
 """spax/models.py mirror — SPR (exact GP / Student-t process regression) and SVSP (the sparse variational scale-mixture
 classifier): evaluation (test_acc_nll / evaluate) and the training loss with its analytic gradient (loss_and_grad) with
-respect to every trainable except the inducing images -- that one needs a reverse-mode pass through the conv kernel,
-which the engine does not have yet; loss_and_grad hands out its seed, d loss / d K.  SVSP.loss itself (a value for an
-autodiff framework to differentiate) still raises."""
+respect to every trainable -- the inducing images through a reverse-mode pass of the conv kernel seeded with d loss / d K
+(inducing_grad=True).  SVSP.loss itself (a value for an autodiff framework to differentiate) still raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -206,7 +205,8 @@ class SPR(Module):
 
 class SVSP(Module):
     """spax/models.py:9-78: sparse variational GP / Student-t process classifier over `num_latent_gps` classes, with the
-    reference's constructor, trainables (inducing_variable, q_mu, q_sqrt, eps) and `test_acc_nll`.
+    reference's constructor, trainables (inducing_variable, q_mu, q_sqrt, eps), `test_acc_nll` and, in place of the
+    autodiff `loss`, `loss_and_grad` (every trainable, the inducing images included).
 
     Everything that grows with the data runs on the device: the cross kernel K(Z, x) and the per-image diagonal
     K(x_t, x_t) of the conv kernels, the posterior moments (smn_svsp_moments; the I x I side in fp64 whatever `dtype` is), and
@@ -236,21 +236,26 @@ class SVSP(Module):
         raise NotImplementedError("SVSP.loss is a value for an autodiff framework to differentiate; this engine returns the "
                                   "negative ELBO together with its analytic gradient: SVSP.loss_and_grad")
 
-    def loss_and_grad(self, key, x_batch, y_batch, num_train, num_samples, *, kernel_grads=True, aux=False, return_gbar=False):
+    def loss_and_grad(self, key, x_batch, y_batch, num_train, num_samples, *, kernel_grads=True, aux=False, return_gbar=False,
+                      inducing_grad=False):
         """(n_elbo, {variable name: d n_elbo / d RAW value}) of spax/models.py:30-56 -- the analytic counterpart of
-        objax.GradValues(model.loss, train_vars) in experiments/classification/train.py:61-75 -- for every trainable except
-        the inducing images: q_mu and q_sqrt (arrays [C,I]), eps, w_std, b_std, last_w_std and, for InverseGammaPrior, a, b.
-        `inducing_variable` never appears in the result.  aux=True appends (-ll, kl / num_train) as the reference's aux does.
+        objax.GradValues(model.loss, train_vars) in experiments/classification/train.py:61-75 -- for every trainable:
+        q_mu and q_sqrt (arrays [C,I]), eps, w_std, b_std, last_w_std, for InverseGammaPrior a and b, and, with
+        inducing_grad=True, `inducing_variable` (a float64 array [I,H,W,C]; the variable has no constraint, so the raw value
+        is the value).  aux=True appends (-ll, kl / num_train) as the reference's aux does.
 
         One symmetric fp64 build of K over [Z; x_batch], one smn_svsp_elbo_grad (forward, correlated Monte-Carlo softmax
         head, reverse pass; leaves d loss / d K on the device) and, with kernel_grads, one forward-mode tangent pass
         (smn_kernel_cnn_grad_terms) that contracts d loss / d K with dK / d(w_std, b_std, last_w_std).  That pass exists for
         get_cnn_kernel and images of up to 1024 pixels: anything else raises NotImplementedError with kernel_grads=True;
         kernel_grads=False works for both conv kernels and omits the three kernel entries (the others are the same bits).
+        inducing_grad=True adds one reverse pass of the conv kernel over the same images (smn_kernel_cnn_input_grad, fp64,
+        seeded with d loss / d K, n_grad = I); it has the tangent pass's limits (get_cnn_kernel, at most 1024 pixels, else
+        NotImplementedError), works with kernel_grads either way and leaves every other returned object the same bits.
         The closed-form inverse-gamma terms, (a, b) -> (df, scale, s) and the softplus chain rule are host arithmetic.
         `key` as in test_acc_nll: an int seed or (seed, global index of the batch's first point).  The model's `dtype`
         selects the arithmetic of the head's variates and exponentials; everything else is fp64.
-        return_gbar=True appends the device array d loss / d K [I+B, I+B] (what a reverse-mode conv kernel would consume).
+        return_gbar=True appends the device array d loss / d K [I+B, I+B] (what the two conv passes consume).
         A matrix that is not positive definite gives NaN for the loss and every gradient."""
         seed, point0 = split_key(key)
         kernel_fn = self.kernel.get_kernel_fn()
@@ -264,6 +269,9 @@ class SVSP(Module):
         if kernel_grads and (kernel_fn.entry != "smn_kernel_cnn" or z_host.shape[1] * z_host.shape[2] > 1024):
             raise NotImplementedError("kernel_grads=True needs get_cnn_kernel and images of at most 1024 pixels (the tangent "
                                       "pass of smn_kernel_cnn_grad_terms); pass kernel_grads=False")
+        if inducing_grad and (kernel_fn.entry != "smn_kernel_cnn" or z_host.shape[1] * z_host.shape[2] > 1024):
+            raise NotImplementedError("inducing_grad=True needs get_cnn_kernel and images of at most 1024 pixels (the reverse "
+                                      "pass of smn_kernel_cnn_input_grad)")
         ctx = (x_batch.ctx if isinstance(x_batch, DeviceArray) else None) or kernel_fn.ctx or _lib.default_context()
         n_i, n_b, c = self.num_inducing, x_host.shape[0], self.num_latent_gps
         labels = np.ascontiguousarray(np.asarray(y_batch).reshape(-1), dtype=np.int32)
@@ -309,6 +317,15 @@ class SVSP(Module):
                 d_con[key_] = (getattr(self.kernel, key_), terms[i] if info.value == 0 else float("nan"))
         for var, g in d_con.values():
             grads[names[id(var)]] = float(g * var.constraint.grad(var.value))
+        if inducing_grad:
+            if info.value == 0:
+                act, depth, w, b_, lw = kernel_fn.params
+                gz = ctx.empty(z_host.shape, np.float64)
+                ctx.call("smn_kernel_cnn_input_grad", _lib.F64, act, depth, w, b_, lw, u.ptr, n_u, u.shape[1], u.shape[2], u.shape[3],
+                         gbar.ptr, n_u, n_i, gz.ptr)
+                grads[names[id(self.inducing_variable)]] = gz.raw_numpy()
+            else:
+                grads[names[id(self.inducing_variable)]] = np.full(z_host.shape, np.nan)
         value = nll_v + kl_v
         if info.value != 0:
             nan = float("nan")

@@ -2,10 +2,11 @@
 (`objax.GradValues(model.loss, train_vars)` + `objax.optimizer.Adam`) and :77-110 (train / valid epochs) without autodiff.
 
 The gradient is SVSP.loss_and_grad: one fp64 kernel build over [inducing images; batch], one smn_svsp_elbo_grad, one
-tangent pass for the kernel's hyper-parameters.  The inducing images are never selected: their gradient needs a
-reverse-mode conv kernel the engine does not have yet, so they stay where they were initialised -- a subset of the
-training set is how the reference initialises them (train.py:177-182).  As there, svtp leaves `last_w_std` out
-(train.py:204-216).
+tangent pass for the kernel's hyper-parameters and, when the inducing images are among the variables, one reverse pass
+of the conv kernel for them (smn_kernel_cnn_input_grad).  The reference trains them (train.py:205 puts model.vars() into
+the optimiser) from a subset of the training set (train.py:177-182); here they are selected with
+svsp_train_vars(model, inducing=True) and stay where they were initialised otherwise.  As there, svtp leaves
+`last_w_std` out (train.py:204-216).
 """
 from __future__ import annotations
 
@@ -46,25 +47,28 @@ class ArrayAdam:
         return out
 
 
-def svsp_train_vars(model):
-    """The variables experiments/classification/train.py:204-216 trains, minus the inducing images: everything for svgp
-    (GaussianPrior); everything but last_w_std for svtp (InverseGammaPrior)."""
+def svsp_train_vars(model, inducing=False):
+    """The variables experiments/classification/train.py:204-216 trains: everything for svgp (GaussianPrior); everything
+    but last_w_std for svtp (InverseGammaPrior).  The inducing images are among them with inducing=True only."""
     from .spax.priors import InverseGammaPrior
-    skip = ("inducing_variable", "last_w_std") if isinstance(model.prior, InverseGammaPrior) else ("inducing_variable",)
+    skip = ("last_w_std",) if isinstance(model.prior, InverseGammaPrior) else ()
+    if not inducing:
+        skip += ("inducing_variable",)
     return {k: v for k, v in model.vars().items() if isinstance(v, TrainVar) and not any(s in k for s in skip)}
 
 
 def build_svsp_train_step(model, variables=None, optimizer=None, *, num_train, num_samples):
     """train_step(key, x_batch, y_batch, lr) -> n_elbo before the update (classification/train.py:61-75).
-    variables: name -> TrainVar to update (default: svsp_train_vars(model)); the inducing images are refused."""
+    variables: name -> TrainVar to update (default: svsp_train_vars(model)); with `inducing_variable` among them every step
+    also asks for the inducing-image gradient (loss_and_grad(inducing_grad=True))."""
     variables = variables if variables is not None else svsp_train_vars(model)
-    if any("inducing_variable" in k for k in variables):
-        raise NotImplementedError("the inducing images have no analytic gradient yet (SVSP.loss_and_grad); leave them out")
+    need_inducing = any("inducing_variable" in k for k in variables)
     optimizer = optimizer or ArrayAdam()
     need_kernel = any(k.split(".")[-1] in ("w_std", "b_std", "last_w_std") for k in variables)
 
     def train_step(key, x_batch, y_batch, lr):
-        value, grads = model.loss_and_grad(key, x_batch, y_batch, num_train, num_samples, kernel_grads=need_kernel)
+        value, grads = model.loss_and_grad(key, x_batch, y_batch, num_train, num_samples, kernel_grads=need_kernel,
+                                           inducing_grad=need_inducing)
         new = optimizer.step({k: v.value for k, v in variables.items()}, {k: g for k, g in grads.items() if k in variables}, lr)
         for k, v in variables.items():
             v.assign(new[k])
