@@ -11,6 +11,8 @@
 // pre-activation variance maps q~_l[n,h,w] (the same stencil recursion on the diagonal) are computed
 // once per image by conv_q_kernel and streamed from L2.  VALU-bound by construction (a 9-tap sum and
 // an asin per pixel, pair and layer); no MFMA: there is no GEMM here to find.
+// The wave's LDS map, the K0 phase, the activation step, the epilogue, the pair order and the per-image helpers are
+// cnn_pairs.hpp's, shared with the tangent, reverse-mode and WideResnet kernels.
 #include <type_traits>
 
 #include "cnn_pairs.hpp"
@@ -52,26 +54,18 @@ __global__ void __launch_bounds__(256) conv_q_kernel(const T* __restrict__ x, in
   const int64_t img = blockIdx.x;
   for (int i = threadIdx.x; i < 2 * PSZ; i += blockDim.x) m0[i] = 0.0;
   __syncthreads();
-  for (int px = threadIdx.x; px < HW; px += blockDim.x) {
-    const T* xp = x + (img * HW + px) * p.C;
-    double s = 0.0;
-    for (int c = 0; c < p.C; ++c) s += (double)xp[c] * (double)xp[c];
-    m0[(px / W + 1) * PW + px % W + 1] = s / p.C;
-  }
+  q0_into_map(x + img * HW * p.C, HW, W, PW, p.C, m0);
   __syncthreads();
   double* cur = m0;
   double* nxt = m1;
   for (int l = 0; l < p.layers; ++l) {
     for (int px = threadIdx.x; px < HW; px += blockDim.x) {
       const int h = px / W, w = px % W;
-      const double* c = cur + h * PW + w;   // top-left of the 3x3 window in the padded map
-      const double bs = c[0] + c[1] + c[2] + c[PW] + c[PW + 1] + c[PW + 2] + c[2 * PW] + c[2 * PW + 1] + c[2 * PW + 2];
-      const double qt = p.w2 * bs / 9.0 + p.b2;
+      const double qt = p.w2 * box9(cur + h * PW + w, PW) / 9.0 + p.b2;
+      const DiagAct d = diag_act(p.act, qt);
       const int64_t ti = (img * p.layers + l) * HW + (patch44 ? patch44_index<T>(px, 16 / (int)sizeof(T)) : (int64_t)px);
-      if (p.act == 0) R[ti] = qt > 0.0 ? (T)(1.0 / sqrt(qt)) : T(0);
-      else R[ti] = (T)(1.0 / sqrt(1.0 + 2.0 * qt));
-      const double qa = p.act == 0 ? 0.5 * qt : (2.0 / nngp::kPi) * asin(2.0 * qt / (1.0 + 2.0 * qt));
-      nxt[(h + 1) * PW + w + 1] = qa;
+      R[ti] = (T)d.ra;
+      nxt[(h + 1) * PW + w + 1] = d.qa;
     }
     __syncthreads();
     double* t = cur; cur = nxt; nxt = t;
@@ -87,31 +81,15 @@ __global__ void __launch_bounds__(256) conv_q_kernel(const T* __restrict__ x, in
       xperm[img * HW * C + ((int64_t)(r * XV + e / VEC) * 64 + lane) * VEC + e % VEC] = x[img * HW * C + i];
     }
   }
-  // mean over pixels (block tree reduction in the free map)
-  double s = 0.0;
-  for (int px = threadIdx.x; px < HW; px += blockDim.x) s += cur[(px / W + 1) * PW + px % W + 1];
-  double* red = m0 + 2 * PSZ;   // 256 doubles of scratch behind the two maps
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) diag[img] = (T)(p.lw2 * red[0] / HW);
+  const double k = block_mean(cur, H, W, PW, p.lw2, m0 + 2 * PSZ);   // 256 doubles of scratch behind the two maps
+  if (threadIdx.x == 0) diag[img] = (T)k;
 }
 
 constexpr int kMaxPix = 64;   // pixels per lane (H*W <= 4096)
 
-// 4 waves per workgroup, each wave walks its own list of image pairs: the map of a wave is private to it,
-// LDS operations of one wave execute in order, so the layers need no workgroup barrier (only a compiler fence).
-// ONE padded map per wave: a lane keeps the values of its NP pixels in registers, publishes them to the map,
-// reads the 9 taps of each of its pixels and overwrites the registers; the next layer's publish is issued after
-// every tap read of this one (same wave, in-order LDS), so no second map is needed -- half the LDS of a ping-pong
-// pair, twice the waves per CU to cover the latency of the table loads and of the f64 chains.
-// NP = pixels per lane (compile-time bound): padded-map offsets are computed once per kernel, not per layer.
-// Lanes whose pixel index runs past H*W are not branched around: they load from a clamped (valid) pixel, publish to
-// a dummy slot behind the map whose 3x3 neighbourhood is also behind the map, and are dropped from the final sum
-// (EXACT: H*W == 64*NP, there are none).
+// 4 waves per workgroup, each wave walks its own list of image pairs (PairWalk) with ONE padded map private to it
+// (WaveMap) -- half the LDS of a ping-pong pair, twice the waves per CU to cover the latency of the table loads and of
+// the f64 chains.  NP = pixels per lane (compile-time bound): padded-map offsets are computed once per kernel, not per layer.
 #ifndef SMN_CNN_K0_BATCH
 #define SMN_CNN_K0_BATCH 16   // pixels whose K0 channel loads are issued together: the phase is pure load latency
 #endif                        // (4 -> 16: fp64 +12 %, fp32 +5 %, profiles/r01f_cnn_k0_batch_ab.txt)
@@ -127,33 +105,14 @@ template <typename T>
 constexpr int pair_occ(int np, bool exact) {   // workgroups per CU a form is compiled for (and launched at)
   return np > 16 ? 1 : np <= 4 ? 4 : !exact ? 2 : sizeof(T) == 8 ? SMN_CNN_OCC_F64 : SMN_CNN_OCC_F32;
 }
-// Pair order.  Every pair streams two images' inputs and factor tables (56 KB in f64 for 32x32x3, 4 layers); in the plain
-// order the waves in flight touch ~8k different images, far beyond the 4 MB L2 of an XCD, and the f64 kernel spent 75 % of
-// its wave cycles waiting on those loads (VALU busy 49 %, rocprofv3 PMC).  Tiled order: the grid is exactly the resident
-// set, workgroup b runs on XCD b % 8 (round-robin dispatch), and the workgroups of one XCD walk tiles of tile_bn x 32
-// pairs together -- one pair per wave per tile -- so an XCD's L2 holds the tile_bn + 32 images its waves are reading.
 template <typename T, int ACT, int NP, bool EXACT>
 __global__ void __launch_bounds__(256, pair_occ<T>(NP, EXACT)) conv_pair_kernel(PairArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ConvProg& p = a.prog;
-  const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW;
+  const int HW = p.H * p.W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int MSZ = PSZ + 2 * PW + 3;                     // map + the dummy slot's neighbourhood
-  T* map = reinterpret_cast<T*>(smem) + (size_t)wave * MSZ;
-  for (int i = lane; i < MSZ; i += 64) map[i] = T(0);   // halo stays zero for the whole kernel
-  // centre of pixel lane + 64 i in the padded map.  EXACT forms (W divides 64 as well): pixel i sits 64 / W rows below
-  // pixel i - 1, so the offsets are off0 + i * rstep and no per-pixel table is kept in registers.
-  int off_tab[EXACT ? 1 : NP];
-  const int off0 = (lane / W + 1) * PW + lane % W + 1, rstep = (64 / W) * PW;
-  if (!EXACT) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int px = lane + 64 * i;
-      off_tab[i] = px < HW ? (px / W + 1) * PW + px % W + 1 : PSZ + PW + 1;
-    }
-  }
-  auto off = [&](int i) { return EXACT ? off0 + i * rstep : off_tab[EXACT ? 0 : i]; };
-  auto pix = [&](int i) { return EXACT ? lane + 64 * i : min(lane + 64 * i, HW - 1); };   // pixel a lane loads from
+  WaveMap<T, NP, EXACT> wm(smem, p.H, p.W, lane, wave);
+  auto pix = [&](int i) { return wm.pix(i); };
   const T w2_9 = (T)(p.w2 / 9.0), b2 = (T)p.b2;
   const T inv_c = (T)(1.0 / p.C);
   // (the fp64 16-pixel exact form lives on 128 VGPRs: a batch of 16 spills there and costs 20 %)
@@ -161,64 +120,22 @@ __global__ void __launch_bounds__(256, pair_occ<T>(NP, EXACT)) conv_pair_kernel(
   PairWalk<T> walk(a, wave);
   int64_t n, m;
   while (walk.next(n, m)) {
-    // K0 map: channel loop outside, pixel loop inside, so the 2 NP loads of one channel are in flight together
-    const T* xa = a.x1 + n * HW * p.C;
-    const T* xb = a.x2 + m * HW * p.C;
     T val[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) val[i] = T(0);
-    for (int c = 0; c < p.C; ++c) {
-#pragma unroll
-      for (int i0 = 0; i0 < NP; i0 += KB) {   // 2 KB loads in flight per batch
-        T va[KB], vb[KB];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-          va[j] = xa[pix(i0 + j) * p.C + c];
-          vb[j] = xb[pix(i0 + j) * p.C + c];
-        }
-#pragma unroll
-        for (int j = 0; j < KB; ++j) val[i0 + j] = fma(va[j], vb[j], val[i0 + j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) val[i] *= inv_c;
+    load_k0<KB, true>(a.x1 + n * HW * p.C, a.x2 + m * HW * p.C, p.C, inv_c, pix, val);
     for (int l = 0; l < p.layers; ++l) {
       const T* r1 = a.R1 + (n * p.layers + l) * HW;
       const T* r2 = a.R2 + (m * p.layers + l) * HW;
-      // publish this layer's input; the previous layer's tap reads were issued before (in-order LDS of one wave)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wm.publish(val);
 #pragma unroll
-      for (int i = 0; i < NP; ++i) map[off(i)] = val[i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
+      for (int i = 0; i < NP; ++i) {   // the taps fused with the activation, not wm.box(): one value per pixel to keep
         const T rr = r1[pix(i)] * r2[pix(i)];
-        const T* c = map + off(i);
-        const T bs = ((c[-PW - 1] + c[-PW]) + (c[-PW + 1] + c[-1])) + ((c[0] + c[1]) + (c[PW - 1] + c[PW])) + c[PW + 1];
-        const T kt = fma(w2_9, bs, b2);
-        if (ACT == 0) {
-          const T ss = rr > T(0) ? T(1.0 / (2.0 * nngp::kPi)) * rcp_any<T>(rr) : T(0);
-          val[i] = nngp::relu_map<T, false>(kt, rr, ss).k;
-        } else {
-          val[i] = nngp::erf_map<T, false>(kt, rr, T(0)).k;
-        }
+        val[i] = act_value<T, ACT>(fma(w2_9, wm.taps(i, wm.PW), b2), rr);
       }
     }
-    // Flatten (mean over pixels) + last Dense
     T s = T(0);
 #pragma unroll
-    for (int i = 0; i < NP; ++i) s += (EXACT || lane + 64 * i < HW) ? val[i] : T(0);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) {
-      T v = (T)p.lw2 * s / (T)HW;
-      if (a.symmetric && n == m) v = a.diag[n];
-      a.out[n * a.ldo + m] = v;
-      if (a.symmetric && a.mirror && n != m) a.out[m * a.ldo + n] = v;
-    }
+    for (int i = 0; i < NP; ++i) s += wm.own(i) ? val[i] : T(0);
+    store_pair(a, n, m, s, HW, lane);
   }
 }
 
@@ -277,27 +194,8 @@ __global__ void __launch_bounds__(256, SMN_CNN32_OCC) conv_pair32_kernel(PairArg
   PairWalk<T> walk(a, wave);
   int64_t n, m;
   while (walk.next(n, m)) {
-    const T* xa = a.x1 + n * HW * p.C;
-    const T* xb = a.x2 + m * HW * p.C;
     T val[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) val[i] = T(0);
-    for (int c = 0; c < p.C; ++c) {
-#pragma unroll
-      for (int i0 = 0; i0 < NP; i0 += KB) {   // 2 KB loads in flight per batch
-        T va[KB], vb[KB];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-          va[j] = xa[(lane + 64 * (i0 + j)) * p.C + c];
-          vb[j] = xb[(lane + 64 * (i0 + j)) * p.C + c];
-        }
-#pragma unroll
-        for (int j = 0; j < KB; ++j) val[i0 + j] = fma(va[j], vb[j], val[i0 + j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) val[i] *= inv_c;
+    load_k0<KB, true>(a.x1 + n * HW * p.C, a.x2 + m * HW * p.C, p.C, inv_c, [&](int i) { return lane + 64 * i; }, val);
     for (int l = 0; l < p.layers; ++l) {
       const T* r1 = a.R1 + (n * p.layers + l) * HW + lane;
       const T* r2 = a.R2 + (m * p.layers + l) * HW + lane;
@@ -313,26 +211,13 @@ __global__ void __launch_bounds__(256, SMN_CNN32_OCC) conv_pair32_kernel(PairArg
         const T below = i + 1 < NP ? e[i + 1] : T(0);   // row 2i + 2, for the upper lanes
         const T bs = (e[i] + o[i]) + (upper ? below : above);
         const T rr = r1[64 * i] * r2[64 * i];   // (all 32 loads of the layer issued up front: 5 % slower, registers)
-        const T kt = fma(w2_9, bs, b2);
-        if (ACT == 0) {
-          const T ss = rr > T(0) ? T(1.0 / (2.0 * nngp::kPi)) * rcp_any<T>(rr) : T(0);
-          val[i] = nngp::relu_map<T, false>(kt, rr, ss).k;
-        } else {
-          val[i] = nngp::erf_map<T, false>(kt, rr, T(0)).k;
-        }
+        val[i] = act_value<T, ACT>(fma(w2_9, bs, b2), rr);
       }
     }
     T s = T(0);
 #pragma unroll
     for (int i = 0; i < NP; ++i) s += val[i];
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2);
-    if (lane == 0) {
-      T v = (T)p.lw2 * s / (T)HW;
-      if (a.symmetric && n == m) v = a.diag[n];
-      a.out[n * a.ldo + m] = v;
-      if (a.symmetric && a.mirror && n != m) a.out[m * a.ldo + n] = v;
-    }
+    store_pair(a, n, m, s, HW, lane);
   }
 }
 
@@ -358,12 +243,6 @@ __device__ __forceinline__ float lane_fetch<float>(float v, int sb) {
 template <>
 __device__ __forceinline__ double lane_fetch<double>(double v, int sb) {
   return __hiloint2double(__builtin_amdgcn_ds_bpermute(sb, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(sb, __double2loint(v)));
-}
-
-__device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ double rcp_fast(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(fma(-x, r, 1.0), r, r);
 }
 
 template <typename T, int ACT, int C>
@@ -468,15 +347,7 @@ __global__ void __launch_bounds__(256, SMN_CNN32_OCC) conv_pair44_kernel(PairArg
         if (c == 0) { asm volatile("" : "+v"(bs[0])); CT(1); }
 #endif
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const T kt = fma(w2_9, bs[r], b2);
-          if (ACT == 0) {
-            const T ss = rr[r][c] > T(0) ? T(1.0 / (2.0 * nngp::kPi)) * rcp_fast(rr[r][c]) : T(0);
-            val[r][c] = nngp::relu_map<T, false>(kt, rr[r][c], ss).k;
-          } else {
-            val[r][c] = nngp::erf_map<T, false>(kt, rr[r][c], T(0)).k;
-          }
-        }
+        for (int r = 0; r < 4; ++r) val[r][c] = act_value<T, ACT, true>(fma(w2_9, bs[r], b2), rr[r][c]);
       }
     }
     asm volatile("" : "+v"(val[0][0]));
@@ -489,14 +360,7 @@ __global__ void __launch_bounds__(256, SMN_CNN32_OCC) conv_pair44_kernel(PairArg
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) s += val[r][c];
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2);
-    if (lane == 0) {
-      T v = (T)p.lw2 * s / (T)HW;
-      if (a.symmetric && n == m) v = a.diag[n];
-      a.out[n * a.ldo + m] = v;
-      if (a.symmetric && a.mirror && n != m) a.out[m * a.ldo + n] = v;
-    }
+    store_pair(a, n, m, s, HW, lane);
   }
 #ifdef SMN_CNN_TIMING
   if (threadIdx.x == 0 && blockIdx.x == 0 && npair > 0)
@@ -506,21 +370,12 @@ __global__ void __launch_bounds__(256, SMN_CNN32_OCC) conv_pair44_kernel(PairArg
 #undef CT
 }
 
-// Launch one form of the pair kernel.  Tiled pair order once there are >= 64 tiles per XCD: the grid is then exactly the
-// resident set (occupancy API; a multiple of 64 workgroups, so a tile is a whole number of 32-pair rows).
+// Launch one form of the pair kernel, in the tiled pair order where tiled_pair_grid takes it.
 template <typename T, typename K>
 int launch_pair_form(smn_ctx* ctx, K kern, PairArgs<T> a, int64_t blocks, size_t lds) {
   if (lds > 0)
     SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) == hipSuccess &&
-      per_cu > 0) {
-    const int64_t g = (int64_t)ctx->num_cu * per_cu / 64 * 64;
-    if (g >= 64 && a.npairs >= 64 * 8 * (g / 8) * 4) {
-      blocks = g;
-      a.tile_bn = (int)(g / 64);
-    }
-  }
+  tiled_pair_grid(resident_blocks(ctx, kern, lds), a.npairs, INT64_MAX, &blocks, &a.tile_bn);
   ProfScope ps(ctx, PROF_BUILD, ctx->stream);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
   return SMN_OK;
@@ -555,11 +410,11 @@ int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, cons
           const void* x2, int64_t n2, int64_t H, int64_t W, int64_t C, int fill, void* out, int64_t ldk) {
   const bool sym = x2 == nullptr;
   if (sym) n2 = n1;
-  ConvProg p{act, layers, (int)H, (int)W, (int)C, w * w, b * b, lw * lw};
+  const ConvProg p = make_prog(act, layers, H, W, C, w, b, lw);
   const int64_t HW = H * W;
   const size_t psz = (size_t)(H + 2) * (W + 2);
   const size_t lds_q = (2 * psz + 256) * sizeof(double);
-  const size_t lds_p = 4 * (psz + 2 * (W + 2) + 3) * sizeof(T);   // one padded map (+ dummy slot) per wave
+  const size_t lds_p = wave_map_lds_bytes<T>(H, W);
   if (lds_q > 160 * 1024 || lds_p > 160 * 1024)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn: image %lldx%lld too large for the on-chip pair map", (long long)H, (long long)W);
   // tables: R1 [n1][L][HW], diag1 [n1] (+ R2, diag2); patch order + patch-order copies of the inputs for conv_pair44_kernel
@@ -602,7 +457,7 @@ int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, cons
 template <typename T>
 int cnn_diag_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, const void* x, int64_t n, int64_t H, int64_t W,
                int64_t C, void* diag) {
-  ConvProg p{act, layers, (int)H, (int)W, (int)C, w * w, b * b, lw * lw};
+  const ConvProg p = make_prog(act, layers, H, W, C, w, b, lw);
   const size_t lds_q = (2 * (size_t)(H + 2) * (W + 2) + 256) * sizeof(double);
   if (lds_q > 160 * 1024)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: image %lldx%lld too large for the on-chip map", (long long)H, (long long)W);
@@ -622,7 +477,7 @@ int cnn_diag_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw,
 
 int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,
              int64_t H, int64_t W, int64_t C, void* diag_d) {
-  if (H * W > 64 * kMaxPix) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: H*W > %d", 64 * kMaxPix);
+  SMN_TRY(conv_check(ctx, "smn_kernel_conv_diag", dtype, act, layers, n, H, W, C, 64 * kMaxPix));
   if (dtype == SMN_F64) return cnn_diag_t<double>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
   return cnn_diag_t<float>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
 }
@@ -632,11 +487,8 @@ extern "C" int smn_kernel_cnn(smn_ctx* ctx, int dtype, int act, int num_hiddens,
                               int64_t W, int64_t C, int fill, void* nngp_d, int64_t ldk) {
   if (!ctx || !x1_d || !nngp_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype %d", dtype);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
-  if (n1 <= 0 || (x2_d && n2 <= 0) || H <= 0 || W <= 0 || C <= 0 || num_hiddens < 0)
-    return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn: bad sizes");
-  if (H * W > 64 * kMaxPix) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn: H*W > %d", 64 * kMaxPix);
+  SMN_TRY(conv_check(ctx, "smn_kernel_cnn", dtype, act, num_hiddens, n1, H, W, C, 64 * kMaxPix));
+  if (x2_d && n2 <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn: bad sizes");
   if (dtype == SMN_F64)
     return cnn_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
   return cnn_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);

@@ -16,7 +16,8 @@
 //   Erf:   phi_qi = -(2/pi) s / (sqrt(1 - s^2) (1 + 2 q_i))  = [-(2/pi) s / sqrt(1 - s^2)]       * ra_i^2
 // so phi_qi qw_n + phi_qj qw_m = [pair factor] * (ra_n^2 qw_n + ra_m^2 qw_m): THREE fields per image, layer and pixel --
 // ra, ra^2 qw, ra^2 qb -- where grad.hip keeps five per row.  The forward pair kernel is bound by streaming its one table
-// out of L2 (cnn.hip), so the fewer the better; sqrt(q_i q_j) is 1 / (ra_i ra_j), one reciprocal, as in the forward kernel.
+// out of L2 (cnn.hip), so the fewer the better; sqrt(q_i q_j) is 1 / (ra_i ra_j), one reciprocal, as in the forward kernel
+// (act_factors of cnn_pairs.hpp, which also holds the wave's LDS map, the K0 phase, the pair order and the per-image helpers).
 // A pixel whose variance is exactly zero (an all-zero neighbourhood with b_std = 0) has ra = 0 and so contributes no q-side
 // term: the map is not differentiable there, and 0 * inf must not reach the sums.
 #include <algorithm>
@@ -44,12 +45,7 @@ __global__ void __launch_bounds__(256) cgrad_q_kernel(const T* __restrict__ x, C
   const int64_t img = blockIdx.x;
   for (int i = threadIdx.x; i < 6 * PSZ; i += blockDim.x) maps[i] = 0.0;
   __syncthreads();
-  for (int px = threadIdx.x; px < HW; px += blockDim.x) {
-    const T* xp = x + (img * HW + px) * p.C;
-    double s = 0.0;
-    for (int c = 0; c < p.C; ++c) s += (double)xp[c] * (double)xp[c];
-    maps[(px / W + 1) * PW + px % W + 1] = s / p.C;
-  }
+  q0_into_map(x + img * HW * p.C, HW, W, PW, p.C, maps);
   __syncthreads();
   double* cur = maps;
   double* nxt = maps + 3 * PSZ;
@@ -58,52 +54,29 @@ __global__ void __launch_bounds__(256) cgrad_q_kernel(const T* __restrict__ x, C
       const int h = px / W, w = px % W;
       double bs[3];
 #pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        const double* c = cur + f * PSZ + h * PW + w;   // top-left of the 3x3 window in the padded map
-        bs[f] = c[0] + c[1] + c[2] + c[PW] + c[PW + 1] + c[PW + 2] + c[2 * PW] + c[2 * PW + 1] + c[2 * PW + 2];
-      }
+      for (int f = 0; f < 3; ++f) bs[f] = box9(cur + f * PSZ + h * PW + w, PW);
       const double qt = p.w2 * bs[0] / 9.0 + p.b2;
       const double qw = bs[0] / 9.0 + p.w2 * bs[1] / 9.0;
       const double qb = 1.0 + p.w2 * bs[2] / 9.0;
-      double ra, ra2, qa, dq;
-      if (p.act == 0) {
-        ra = qt > 0.0 ? 1.0 / sqrt(qt) : 0.0;
-        ra2 = qt > 0.0 ? 1.0 / qt : 0.0;
-        qa = 0.5 * qt;
-        dq = 0.5;
-      } else {
-        const double t = 1.0 + 2.0 * qt;
-        ra = 1.0 / sqrt(t);
-        ra2 = 1.0 / t;
-        qa = (2.0 / nngp::kPi) * asin(2.0 * qt / t);
-        dq = (4.0 / nngp::kPi) / (t * sqrt(1.0 + 4.0 * qt));   // d/dq (2/pi) asin(2q / (1 + 2q))
-      }
+      const DiagAct d = diag_act(p.act, qt);
+      const double ra2 = p.act == 0 ? (qt > 0.0 ? 1.0 / qt : 0.0) : 1.0 / (1.0 + 2.0 * qt);
       T* t = tab + ((img * p.layers + l) * kCgFields) * HW + px;
-      t[0] = (T)ra;
+      t[0] = (T)d.ra;
       t[HW] = (T)(ra2 * qw);
       t[2 * HW] = (T)(ra2 * qb);
       const int o = (h + 1) * PW + w + 1;
-      nxt[o] = qa;
-      nxt[PSZ + o] = dq * qw;
-      nxt[2 * PSZ + o] = dq * qb;
+      nxt[o] = d.qa;
+      nxt[PSZ + o] = d.dq * qw;
+      nxt[2 * PSZ + o] = d.dq * qb;
     }
     __syncthreads();
     double* t = cur; cur = nxt; nxt = t;
   }
-  // means over pixels (block tree reduction behind the maps)
-  double* red = maps + 6 * PSZ;   // 3 x 256 doubles
+  double* red = maps + 6 * PSZ;   // 3 x 256 doubles behind the maps
   for (int f = 0; f < 3; ++f) {
-    double s = 0.0;
-    for (int px = threadIdx.x; px < HW; px += blockDim.x) s += cur[f * PSZ + (px / W + 1) * PW + px % W + 1];
-    red[f * 256 + threadIdx.x] = s;
+    const double k = block_mean(cur + f * PSZ, H, W, PW, p.lw2, red + f * 256);
+    if (threadIdx.x == 0) dexact[img * 3 + f] = k;
   }
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int f = 0; f < 3; ++f) red[f * 256 + threadIdx.x] += red[f * 256 + threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) dexact[img * 3 + threadIdx.x] = p.lw2 * red[threadIdx.x * 256] / HW;
 }
 
 template <typename T>
@@ -130,56 +103,21 @@ constexpr int cgrad_occ(int np) {
 }
 
 // The general LDS-map form of conv_pair_kernel (cnn.hip) carrying (K, Kw, Kb): one wave per image pair of the lower triangle,
-// PairWalk order, ONE padded map per wave.  A layer publishes K, reads its nine taps into the registers that held K, then
-// reuses the map for Kw and for Kb -- LDS operations of one wave execute in order, which is what the forward kernel relies
-// on -- so the LDS footprint is the forward kernel's.  Per-element arithmetic in T, the four sums in double, one partial per wave.
+// PairWalk order, ONE padded map per wave (WaveMap).  A layer takes the box sum of K through the map, then reuses the map for
+// Kw and for Kb, so the LDS footprint is the forward kernel's.  Per-element arithmetic in T, the four sums in double, one
+// partial per wave.
 template <typename T, int ACT, int NP, bool EXACT>
 __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGradArgs<T> g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const PairArgs<T>& a = g.pa;
   const ConvProg& p = a.prog;
-  const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW;
+  const int HW = p.H * p.W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int MSZ = PSZ + 2 * PW + 3;                     // map + the dummy slot's neighbourhood
-  T* map = reinterpret_cast<T*>(smem) + (size_t)wave * MSZ;
-  for (int i = lane; i < MSZ; i += 64) map[i] = T(0);   // halo stays zero for the whole kernel
-  int off_tab[EXACT ? 1 : NP];
-  const int off0 = (lane / W + 1) * PW + lane % W + 1, rstep = (64 / W) * PW;
-  if (!EXACT) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int px = lane + 64 * i;
-      off_tab[i] = px < HW ? (px / W + 1) * PW + px % W + 1 : PSZ + PW + 1;
-    }
-  }
-  // vlane / voff0 are `lane` and `off0` re-read as opaque values once per pair and once per box sum: the per-pixel addresses
-  // derived from them are then recomputed where they are used (an integer add each) instead of staying alive -- about a
-  // hundred registers for 16 pixels -- beside the state for the whole kernel
-  int vlane = lane, voff0 = off0;
-  auto off = [&](int i) { return EXACT ? voff0 + i * rstep : off_tab[EXACT ? 0 : i]; };
-  auto pix = [&](int i) { return EXACT ? vlane + 64 * i : min(vlane + 64 * i, HW - 1); };   // pixel a lane loads from
-  // v <- 3x3 box sum of v: publish, then nine taps per owned pixel (the previous tap reads were issued before the publish)
-  auto box = [&](T (&v)[NP]) {
-    asm volatile("" : "+v"(voff0));
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < NP; ++i) map[off(i)] = v[i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // (the row stride is re-read as a scalar here: left loop-invariant, the compiler keeps three row addresses per owned pixel
-    // alive across the whole layer loop -- 48 registers for 16 pixels -- and spills the state instead)
-    int pw = PW;
-    asm volatile("" : "+s"(pw));
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const T* r1 = map + off(i) - 1;          // left neighbour; the rows above and below are one add each, the taps immediates
-      const T* r0 = r1 - pw;
-      const T* r2 = r1 + pw;
-      v[i] = ((r0[0] + r0[1]) + (r0[2] + r1[0])) + ((r1[1] + r1[2]) + (r2[0] + r2[1])) + r2[2];
-      if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // 36 taps in flight, not 144
-    }
-  };
+  WaveMap<T, NP, EXACT> wm(smem, p.H, p.W, lane, wave);
+  auto pix = [&](int i) { return wm.pix(i); };
+  // (off0 is re-read in the ragged forms too, where nothing uses it: without it the erf 1024-pixel ragged fp64 form spills 1508
+  // bytes per lane, with it 1500: profiles/r11_cnn_shared.txt)
+  auto box = [&](T (&v)[NP]) { wm.reread_off0(); wm.box(v); };
   const T w2_9 = (T)(p.w2 / 9.0), b2 = (T)p.b2, inv9 = (T)(1.0 / 9.0);
   const T inv_c = (T)(1.0 / p.C), lw2_hw = (T)(p.lw2 / HW), coef = (T)g.coef;
   constexpr int KB = NP < 4 ? NP : 4;
@@ -187,27 +125,11 @@ __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGrad
   PairWalk<T> walk(a, wave);
   int64_t n, m;
   while (walk.next(n, m)) {
-    const T* xa = a.x1 + n * HW * p.C;
-    const T* xb = a.x2 + m * HW * p.C;
-    asm volatile("" : "+v"(vlane));
+    wm.reread_lane();
     T k[NP], kw[NP], kb[NP];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) k[i] = kw[i] = kb[i] = T(0);
-    for (int c = 0; c < p.C; ++c) {
-#pragma unroll
-      for (int i0 = 0; i0 < NP; i0 += KB) {
-        T va[KB], vb[KB];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-          va[j] = xa[pix(i0 + j) * p.C + c];
-          vb[j] = xb[pix(i0 + j) * p.C + c];
-        }
-#pragma unroll
-        for (int j = 0; j < KB; ++j) k[i0 + j] = fma(va[j], vb[j], k[i0 + j]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) k[i] *= inv_c;
+    for (int i = 0; i < NP; ++i) kw[i] = kb[i] = T(0);
+    load_k0<KB, false>(a.x1 + n * HW * p.C, a.x2 + m * HW * p.C, p.C, inv_c, pix, k);
     for (int l = 0; l < p.layers; ++l) {
       const T* t1 = a.R1 + (n * p.layers + l) * kCgFields * HW;
       const T* t2 = a.R2 + (m * p.layers + l) * kCgFields * HW;
@@ -224,29 +146,10 @@ __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGrad
         const T kt = fma(w2_9, k[i], b2);
         const T kwt = fma(w2_9, kw[i], k[i] * inv9);
         const T kbt = fma(w2_9, kb[i], T(1));
-        if (ACT == 0) {
-          const T c = nngp::clamp1(kt * rr);
-          const T ca = fabs(c);
-          const T as = nngp::asin_abs(ca, c * c);
-          const T s1 = nngp::fast_sqrt((T(1) - ca) * (T(1) + ca));
-          const T pm = T(nngp::kPi / 2) + copysign(as, c);
-          const T sp = rr > T(0) ? rcp_any<T>(rr) : T(0);           // sqrt(q_n q_m)
-          const T dA = pm * T(1.0 / (2.0 * nngp::kPi));
-          const T tq = s1 * sp * T(1.0 / (4.0 * nngp::kPi));
-          k[i] = sp * fma(pm, c, s1) * T(1.0 / (2.0 * nngp::kPi));
-          kw[i] = fma(dA, kwt, tq * uw);
-          kb[i] = fma(dA, kbt, tq * ub);
-        } else {
-          const T sv = nngp::clamp1(T(2) * kt * rr);
-          const T sa = fabs(sv);
-          const T as = nngp::asin_abs(sa, sv * sv);
-          const T rden = nngp::fast_rsqrt(fmax((T(1) - sa) * (T(1) + sa), sizeof(T) == 8 ? T(1e-300) : T(1e-30)));
-          const T dA = T(4.0 / nngp::kPi) * rr * rden;
-          const T tq = T(-2.0 / nngp::kPi) * sv * rden;
-          k[i] = T(2.0 / nngp::kPi) * copysign(as, sv);
-          kw[i] = fma(dA, kwt, tq * uw);
-          kb[i] = fma(dA, kbt, tq * ub);
-        }
+        T dA, tq;
+        act_factors<T, ACT>(kt, rr, k[i], dA, tq);
+        kw[i] = fma(dA, kwt, tq * uw);
+        kb[i] = fma(dA, kbt, tq * ub);
         // the table loads of four pixels in flight at a time: hoisted for all sixteen they cost more registers than the state
         if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
@@ -255,7 +158,7 @@ __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGrad
     T s[3] = {T(0), T(0), T(0)};
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const bool ok = EXACT || lane + 64 * i < HW;
+      const bool ok = wm.own(i);
       s[0] += ok ? kw[i] : T(0);
       s[1] += ok ? kb[i] : T(0);
       s[2] += ok ? k[i] : T(0);
@@ -306,21 +209,13 @@ __global__ void __launch_bounds__(256) cgrad_reduce_kernel(const double* __restr
   if (tid < 4) out[tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
 }
 
-// Launch one form.  Tiled pair order as the forward kernel's launcher: from 256 pairs per resident workgroup on, the grid is
-// exactly the resident set g and the tile is (g / 64) x 32 image pairs, one pair per wave.  The tile height follows from the
-// occupancy this kernel compiles to (2 workgroups per CU for the 1024-pixel forms: 8 rows where the forward kernel has 16),
-// not from the forward kernel's.  *blocks_io: the grid asked for / launched (at most max_blocks, the size of the partials).
+// Launch one form, in the tiled pair order where tiled_pair_grid takes it.  The tile height follows from the occupancy this
+// kernel compiles to (2 workgroups per CU for the 1024-pixel forms: 8 rows where the forward kernel has 16), not from the
+// forward kernel's.  *blocks_io: the grid asked for / launched (at most max_blocks, the size of the partials).
 template <typename T, typename K>
 int cgrad_launch_form(smn_ctx* ctx, K kern, CGradArgs<T> g, int64_t* blocks_io, int64_t max_blocks, size_t lds) {
   SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) == hipSuccess && per_cu > 0) {
-    const int64_t r = (int64_t)ctx->num_cu * per_cu / 64 * 64;
-    if (r >= 64 && r <= max_blocks && g.pa.npairs >= 64 * 8 * (r / 8) * 4) {
-      *blocks_io = r;
-      g.pa.tile_bn = (int)(r / 64);
-    }
-  }
+  tiled_pair_grid(resident_blocks(ctx, kern, lds), g.pa.npairs, max_blocks, blocks_io, &g.pa.tile_bn);
   ProfScope ps(ctx, PROF_MISC, ctx->stream);
   hipLaunchKernelGGL(kern, dim3((unsigned)*blocks_io), dim3(256), lds, ctx->stream, g);
   return SMN_OK;
@@ -346,11 +241,11 @@ template <typename T>
 int cgrad_terms_t(smn_ctx* ctx, int act, int layers, double w_std, double b_std, double last_w_std, const void* x_d,
                   int64_t n, int64_t H, int64_t W, int64_t C, const void* nkinv, int64_t ldki, const void* alpha, double coef,
                   double out_h[4]) {
-  ConvProg p{act, layers, (int)H, (int)W, (int)C, w_std * w_std, b_std * b_std, last_w_std * last_w_std};
+  const ConvProg p = make_prog(act, layers, H, W, C, w_std, b_std, last_w_std);
   const int64_t HW = H * W;
   const size_t psz = (size_t)(H + 2) * (W + 2);
   const size_t lds_q = (6 * psz + 3 * 256) * sizeof(double);
-  const size_t lds_p = 4 * (psz + 2 * (W + 2) + 3) * sizeof(T);   // one padded map (+ dummy slot) per wave
+  const size_t lds_p = wave_map_lds_bytes<T>(H, W);
   if (lds_q > 160 * 1024 || lds_p > 160 * 1024)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms: image %lldx%lld too large for the on-chip maps", (long long)H,
                     (long long)W);
@@ -406,12 +301,8 @@ int cgrad_terms_t(smn_ctx* ctx, int act, int layers, double w_std, double b_std,
 
 int cgrad_check(smn_ctx* ctx, const char* who, int dtype, int act, int num_hiddens, double last_w_std, int64_t n, int64_t H,
                 int64_t W, int64_t C) {
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype %d", dtype);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
-  if (n <= 0 || H <= 0 || W <= 0 || C <= 0 || num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  SMN_TRY(conv_check(ctx, who, dtype, act, num_hiddens, n, H, W, C, kCgMaxHW));
   if (!(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: bad hyper-parameters", who);
-  if (H * W > kCgMaxHW)
-    return smn_fail(ctx, SMN_ENOTSUP, "%s: H*W = %lld > %d (SMN_CNN_GRAD_MAX_PIXELS)", who, (long long)(H * W), kCgMaxHW);
   return SMN_OK;
 }
 

@@ -6,8 +6,8 @@
 // Notation of cnn_grad.hip (box = 3x3 zero-padded box sum, self-adjoint).  Forward, per layer l = 1..L and pair (n, m):
 //   kt_l = w^2 box(k_{l-1})/9 + b^2,  k_l = phi(kt_l, qt_l^n, qt_l^m);   per image  qt_l = w^2 box(q_{l-1})/9 + b^2,  q_l = phi_diag(qt_l);
 //   k_0 = x_n.x_m / C,  q_0 = |x_n|^2 / C per pixel;   K_nm = lw^2 mean k_L,  K_nn = lw^2 mean q_L (the exact diagonal).
-// phi_A = d phi / d kt and phi_qi = [pair factor] * ra_i^2 are the factors cnn_grad.hip evaluates (same zero-variance rule:
-// ra = 0 gives no variance-side term, so 0 * inf never arises).
+// phi_A = d phi / d kt and phi_qi = [pair factor] * ra_i^2 are the factors cnn_grad.hip evaluates (act_factors of
+// cnn_pairs.hpp; same zero-variance rule: ra = 0 gives no variance-side term, so 0 * inf never arises).
 //
 // Pair pass (cig_pair_kernel), owner i < n_grad against a partner m != i:
 //   kbar_L = 2 g_im lw^2 / HW  (2: the mirror entry);  for l = L..1:  qtbar_i^l += phi_qi(l) kbar_l,  kbar_{l-1} = w^2 box(phi_A(l) kbar_l)/9;
@@ -16,8 +16,8 @@
 // Per-image pass (cig_finish_kernel):  r = g_ii lw^2 / HW;  for l = L..1:  r = w^2 box(dq_l r + qtbar^l)/9;  gx_i += 2 x_i r / C.
 //
 // Work layout.  One wave per (owner, slice of its partner list); the partner list of an owner is cut into nsplit slices so
-// that owners x nsplit fills the resident waves.  A lane owns NP pixels, as in cgrad_pair_kernel, with one padded LDS map per
-// wave for the box sums.  The forward sweep of a pair leaves (phi_A, pair factor) per layer and pixel in the wave's own slab
+// that owners x nsplit fills the resident waves.  A lane owns NP pixels, with one padded LDS map per wave for the box sums
+// (WaveMap of cnn_pairs.hpp).  The forward sweep of a pair leaves (phi_A, pair factor) per layer and pixel in the wave's own slab
 // of global memory (2 L x 64 NP elements, written and read back by the same lane: no fence), the reverse sweep reads them back.
 // The sums over partners (qtbar [L], gx [C] per pixel) are fp64 in the slice's own block of global memory, added to by the lane
 // that owns the pixel in the fixed order of the partner list; the per-image pass adds the slices in order.  No floating-point
@@ -51,35 +51,17 @@ __global__ void __launch_bounds__(256) cig_q_kernel(const T* __restrict__ x, Con
   const int64_t img = blockIdx.x;
   for (int i = threadIdx.x; i < 2 * PSZ; i += blockDim.x) maps[i] = 0.0;
   __syncthreads();
-  for (int px = threadIdx.x; px < HW; px += blockDim.x) {
-    const T* xp = x + (img * HW + px) * p.C;
-    double s = 0.0;
-    for (int c = 0; c < p.C; ++c) s += (double)xp[c] * (double)xp[c];
-    maps[(px / W + 1) * PW + px % W + 1] = s / p.C;
-  }
+  q0_into_map(x + img * HW * p.C, HW, W, PW, p.C, maps);
   __syncthreads();
   double* cur = maps;
   double* nxt = maps + PSZ;
   for (int l = 0; l < p.layers; ++l) {
     for (int px = threadIdx.x; px < HW; px += blockDim.x) {
       const int h = px / W, w = px % W;
-      const double* c = cur + h * PW + w;   // top-left of the 3x3 window in the padded map
-      const double bs = c[0] + c[1] + c[2] + c[PW] + c[PW + 1] + c[PW + 2] + c[2 * PW] + c[2 * PW + 1] + c[2 * PW + 2];
-      const double qt = p.w2 * bs / 9.0 + p.b2;
-      double ra, qa, dq;
-      if (p.act == 0) {
-        ra = qt > 0.0 ? 1.0 / sqrt(qt) : 0.0;
-        qa = 0.5 * qt;
-        dq = 0.5;
-      } else {
-        const double t = 1.0 + 2.0 * qt;
-        ra = 1.0 / sqrt(t);
-        qa = (2.0 / nngp::kPi) * asin(2.0 * qt / t);
-        dq = (4.0 / nngp::kPi) / (t * sqrt(1.0 + 4.0 * qt));   // d/dq (2/pi) asin(2q / (1 + 2q))
-      }
-      ra_tab[(img * p.layers + l) * HWP + px] = (T)ra;
-      if (img < n_grad) dq_tab[(img * p.layers + l) * HW + px] = dq;
-      nxt[(h + 1) * PW + w + 1] = qa;
+      const DiagAct d = diag_act(p.act, p.w2 * box9(cur + h * PW + w, PW) / 9.0 + p.b2);
+      ra_tab[(img * p.layers + l) * HWP + px] = (T)d.ra;
+      if (img < n_grad) dq_tab[(img * p.layers + l) * HW + px] = d.dq;
+      nxt[(h + 1) * PW + w + 1] = d.qa;
     }
     for (int px = HW + threadIdx.x; px < HWP; px += blockDim.x) ra_tab[(img * p.layers + l) * HWP + px] = T(0);
     __syncthreads();
@@ -101,7 +83,7 @@ struct CigArgs {
 
 // Waves per SIMD a form is compiled for: the second __launch_bounds__ argument is the minimum number of waves per execution
 // unit, and a workgroup of 256 threads puts one wave on each of a CU's four SIMDs, so here (and only for this block size) it
-// is also the number of workgroups per CU.  The state is ONE value per owned pixel (cgrad_pair_kernel carries three), so the
+// is also the number of workgroups per CU.  The state is ONE value per owned pixel (the tangent kernel carries three), so the
 // 1024-pixel form is 32 VGPRs of state in fp64; the LDS offsets and the temporaries of four pixels in flight come on top
 // (170 VGPRs, no scratch: profiles/r10_cnn_input_grad.txt).
 #ifndef SMN_CIG_OCC16
@@ -116,41 +98,13 @@ template <typename T, int ACT, int NP>
 __global__ void __launch_bounds__(256, cig_occ(NP)) cig_pair_kernel(CigArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ConvProg& p = a.prog;
-  const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW, L = p.layers, C = p.C;
+  const int HW = p.H * p.W, L = p.layers, C = p.C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int HWP = 64 * NP;                          // slots per row of the tables, the slab and the sums: lane + 64 i
-  // map + the dummy slot of the pixels past the image, in a row of its own below the map: its neighbourhood is the map's bottom
-  // halo row (read only, always zero), [PSZ, PSZ + 2] and [PSZ + PW, PSZ + PW + 2]; no pixel of the image reads at or past PSZ
-  const int MSZ = PSZ + PW + 3;
-  T* map = reinterpret_cast<T*>(smem) + (size_t)wave * MSZ;
-  for (int i = lane; i < MSZ; i += 64) map[i] = T(0);   // halo stays zero for the whole kernel
-  int off_tab[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int px = lane + 64 * i;
-    off_tab[i] = px < HW ? (px / W + 1) * PW + px % W + 1 : PSZ + 1;   // pixels past the image: the dummy slot
-  }
-  auto own = [&](int i) { return lane + 64 * i < HW; };
-  auto pix = [&](int i) { return min(lane + 64 * i, HW - 1); };   // pixel a lane loads from
-  // v <- 3x3 box sum of v: publish, then nine taps per owned pixel (cgrad_pair_kernel's: LDS operations of one wave execute in order)
-  auto box = [&](T (&v)[NP]) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < NP; ++i) map[off_tab[i]] = v[i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    int pw = PW;
-    asm volatile("" : "+s"(pw));   // the row stride re-read as a scalar: no three row addresses per pixel kept alive
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const T* r1 = map + off_tab[i] - 1;
-      const T* r0 = r1 - pw;
-      const T* r2 = r1 + pw;
-      v[i] = ((r0[0] + r0[1]) + (r0[2] + r1[0])) + ((r1[1] + r1[2]) + (r2[0] + r2[1])) + r2[2];
-      if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // 36 taps in flight, not 144
-    }
-  };
+  // one form per NP (never EXACT), and neither reread_lane() nor reread_off0(): either moves the 1024-pixel forms' registers
+  WaveMap<T, NP, false> wm(smem, p.H, p.W, lane, wave);
+  auto own = [&](int i) { return wm.own(i); };
+  auto pix = [&](int i) { return wm.pix(i); };
   const T w2_9 = (T)(p.w2 / 9.0), b2 = (T)p.b2;
   const T inv_c = (T)(1.0 / C), lw2_hw2 = (T)(2.0 * p.lw2 / HW);
   constexpr int KB = NP < 4 ? NP : 4;
@@ -169,53 +123,20 @@ __global__ void __launch_bounds__(256, cig_occ(NP)) cig_pair_kernel(CigArgs<T> a
       const T* xb = a.x + m * HW * C;
       const T gv = n > m ? a.g[n * a.ldg + m] : a.g[m * a.ldg + n];
       T k[NP];
+      load_k0<KB, false>(xa, xb, C, inv_c, pix, k);
 #pragma unroll
-      for (int i = 0; i < NP; ++i) k[i] = T(0);
-      for (int c = 0; c < C; ++c) {
-#pragma unroll
-        for (int i0 = 0; i0 < NP; i0 += KB) {
-          T va[KB], vb[KB];
-#pragma unroll
-          for (int jj = 0; jj < KB; ++jj) {
-            va[jj] = xa[pix(i0 + jj) * C + c];
-            vb[jj] = xb[pix(i0 + jj) * C + c];
-          }
-#pragma unroll
-          for (int jj = 0; jj < KB; ++jj) k[i0 + jj] = fma(va[jj], vb[jj], k[i0 + jj]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NP; ++i) k[i] = own(i) ? k[i] * inv_c : T(0);
+      for (int i = 0; i < NP; ++i) k[i] = own(i) ? k[i] : T(0);
       // forward sweep: (phi_A, pair factor) of every layer into the wave's slab
       for (int l = 0; l < L; ++l) {
         const T* t1 = a.ra + (n * L + l) * HWP + lane;
         const T* t2 = a.ra + (m * L + l) * HWP + lane;
         T* fl = fwd + l * 2 * HWP;
-        box(k);
+        wm.box(k);
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
           const T rr = t1[64 * i] * t2[64 * i];
-          const T kt = fma(w2_9, k[i], b2);
           T dA, tq;
-          if (ACT == 0) {
-            const T c = nngp::clamp1(kt * rr);
-            const T ca = fabs(c);
-            const T as = nngp::asin_abs(ca, c * c);
-            const T s1 = nngp::fast_sqrt((T(1) - ca) * (T(1) + ca));
-            const T pm = T(nngp::kPi / 2) + copysign(as, c);
-            const T sp = rr > T(0) ? rcp_any<T>(rr) : T(0);           // sqrt(q_n q_m)
-            dA = pm * T(1.0 / (2.0 * nngp::kPi));
-            tq = s1 * sp * T(1.0 / (4.0 * nngp::kPi));
-            k[i] = sp * fma(pm, c, s1) * T(1.0 / (2.0 * nngp::kPi));
-          } else {
-            const T sv = nngp::clamp1(T(2) * kt * rr);
-            const T sa = fabs(sv);
-            const T as = nngp::asin_abs(sa, sv * sv);
-            const T rden = nngp::fast_rsqrt(fmax((T(1) - sa) * (T(1) + sa), sizeof(T) == 8 ? T(1e-300) : T(1e-30)));
-            dA = T(4.0 / nngp::kPi) * rr * rden;
-            tq = T(-2.0 / nngp::kPi) * sv * rden;
-            k[i] = T(2.0 / nngp::kPi) * copysign(as, sv);
-          }
+          act_factors<T, ACT>(fma(w2_9, k[i], b2), rr, k[i], dA, tq);
           fl[64 * i] = dA;
           fl[HWP + 64 * i] = tq;
           if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // the table loads of four pixels in flight at a time
@@ -236,7 +157,7 @@ __global__ void __launch_bounds__(256, cig_occ(NP)) cig_pair_kernel(CigArgs<T> a
           k[i] *= fl[64 * i];
           if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
-        box(k);
+        wm.box(k);
 #pragma unroll
         for (int i = 0; i < NP; ++i) k[i] = own(i) ? k[i] * w2_9 : T(0);
       }
@@ -280,9 +201,7 @@ __global__ void __launch_bounds__(256) cig_finish_kernel(const T* __restrict__ x
     __syncthreads();
     for (int px = threadIdx.x; px < HW; px += blockDim.x) {
       const int h = px / W, w = px % W;
-      const double* c = cur + h * PW + w;
-      const double bs = c[0] + c[1] + c[2] + c[PW] + c[PW + 1] + c[PW + 2] + c[2 * PW] + c[2 * PW + 1] + c[2 * PW + 2];
-      nxt[(h + 1) * PW + w + 1] = p.w2 * bs / 9.0;
+      nxt[(h + 1) * PW + w + 1] = p.w2 * box9(cur + h * PW + w, PW) / 9.0;
     }
     __syncthreads();
     double* t = cur; cur = nxt; nxt = t;
@@ -309,14 +228,14 @@ CigKernel<T> cig_form(int act, int64_t hw) {
 template <typename T>
 int cig_run(smn_ctx* ctx, int act, int layers, double w_std, double b_std, double last_w_std, const void* x_d, int64_t n,
             int64_t H, int64_t W, int64_t C, const void* g_d, int64_t ldg, int64_t n_grad, void* gx_d) {
-  ConvProg p{act, layers, (int)H, (int)W, (int)C, w_std * w_std, b_std * b_std, last_w_std * last_w_std};
+  const ConvProg p = make_prog(act, layers, H, W, C, w_std, b_std, last_w_std);
   const int64_t HW = H * W;
   const int64_t HWP = HW <= 64 ? 64 : HW <= 256 ? 256 : 1024;   // 64 NP of the form cig_launch picks
   const size_t psz = (size_t)(H + 2) * (W + 2);
   const size_t lds_q = 2 * psz * sizeof(double);
-  // one padded map (+ the dummy slot's row) per wave.  H W <= 1024 bounds both: the padded map has at most 3 x 1026 elements
-  // (a 1 x 1024 image), so lds_p <= 4 x 4107 x 8 = 128.3 KB and lds_q <= 48.1 KB of the CU's 160 KB, whatever the aspect ratio
-  const size_t lds_p = 4 * (psz + (W + 2) + 3) * sizeof(T);
+  // H W <= 1024 bounds both: the padded map has at most 3 x 1026 elements (a 1 x 1024 image), so lds_p <= 4 x 4107 x 8 =
+  // 128.3 KB and lds_q <= 48.1 KB of the CU's 160 KB, whatever the aspect ratio
+  const size_t lds_p = wave_map_lds_bytes<T>(H, W);
   CigArgs<T> a;
   a.x = static_cast<const T*>(x_d);
   a.g = static_cast<const T*>(g_d); a.ldg = ldg;
@@ -324,9 +243,8 @@ int cig_run(smn_ctx* ctx, int act, int layers, double w_std, double b_std, doubl
   a.prog = p;
   const CigKernel<T> kern = cig_form<T>(act, HW);
   SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_p));
-  int per_cu = 0;   // the resident set this form compiles to decides how the partner lists are cut
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds_p) != hipSuccess || per_cu <= 0) per_cu = 1;
-  const int64_t resident = (int64_t)ctx->num_cu * per_cu * 4;
+  // the resident set this form compiles to decides how the partner lists are cut
+  const int64_t resident = std::max<int64_t>(resident_blocks(ctx, kern, lds_p), ctx->num_cu) * 4;
   // owners x slices fills the resident waves once; never more slices than partners
   int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(resident / n_grad, n - 1));
   const int64_t per = n > 1 ? (n - 1 + nsplit - 1) / nsplit : 0;
@@ -376,14 +294,10 @@ extern "C" int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int n
   if (!ctx || !x_d || !gbar_d || !gx_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   const char* who = "smn_kernel_cnn_input_grad";
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "%s: bad dtype %d", who, dtype);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "%s: Unsupported act %d", who, act);
-  if (n <= 0 || H <= 0 || W <= 0 || C <= 0 || num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  SMN_TRY(conv_check(ctx, who, dtype, act, num_hiddens, n, H, W, C, kCigMaxHW));
   if (ldg < n) return smn_fail(ctx, SMN_EINVAL, "%s: ldg = %lld < n = %lld", who, (long long)ldg, (long long)n);
   if (n_grad < 1 || n_grad > n)
     return smn_fail(ctx, SMN_EINVAL, "%s: n_grad = %lld outside [1, n = %lld]", who, (long long)n_grad, (long long)n);
-  if (H * W > kCigMaxHW)
-    return smn_fail(ctx, SMN_ENOTSUP, "%s: H*W = %lld > %d (SMN_CNN_GRAD_MAX_PIXELS)", who, (long long)(H * W), kCigMaxHW);
   if (dtype == SMN_F64)
     return cig_run<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, gbar_d, ldg, n_grad, gx_d);
   return cig_run<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, gbar_d, ldg, n_grad, gx_d);

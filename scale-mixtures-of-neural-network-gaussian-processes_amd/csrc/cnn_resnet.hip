@@ -11,10 +11,15 @@
 // a zero ring (three buffers: current, scratch, the block's saved input); the network is a short op list
 // interpreted by the kernel; the per-image factor tables r = 1/sqrt(q~) (ReLU) / 1/sqrt(1+2q~) (erf) of every
 // activation come from a per-image pass over the same op list on the diagonal.  VALU-bound, no MFMA.
+// The activation step, the epilogue, the triangular pair decode and the per-image helpers are cnn_pairs.hpp's; the maps
+// are this file's own (MapSet: three buffers, strided windows).
+#include "cnn_pairs.hpp"
 #include "internal.hpp"
 #include "nngp_math.hpp"
 
 namespace {
+
+using namespace smn_cnn;
 
 enum : unsigned char { OP_CONV = 0, OP_ACT = 1, OP_SAVE = 2, OP_SCONV = 3, OP_ADD = 4 };
 constexpr int kMaxOps = 160;   // 1 + 4 groups * 6 ops * block_size  ->  block_size <= 6
@@ -31,17 +36,6 @@ __host__ __device__ inline int same_lo(int in, int s) {
   const int out = same_out(in, s);
   const int pad = (out - 1) * s + 3 - in;
   return pad > 0 ? pad / 2 : 0;
-}
-
-template <typename T>
-__device__ __forceinline__ T rcp_t(T x);
-template <>
-__device__ __forceinline__ float rcp_t<float>(float x) { return __builtin_amdgcn_rcpf(x); }
-template <>
-__device__ __forceinline__ double rcp_t<double>(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
 }
 
 // A group of NT threads (a workgroup in the per-image pass, one wave in the pair pass) owns three padded maps.
@@ -117,12 +111,7 @@ __global__ void __launch_bounds__(256) resnet_q_kernel(const T* __restrict__ x, 
   for (int i = threadIdx.x; i < 3 * PSZ; i += 256) base[i] = 0.0;
   __syncthreads();
   int h = p.H, w = p.W, cur = 0, skip = -1, toff = 0;
-  for (int px = threadIdx.x; px < h * w; px += 256) {
-    const T* xp = x + (img * h * w + px) * p.C;
-    double s = 0.0;
-    for (int c = 0; c < p.C; ++c) s += (double)xp[c] * (double)xp[c];
-    ms.b(0)[(px / w + 1) * PW + px % w + 1] = s / p.C;
-  }
+  q0_into_map(x + img * h * w * p.C, h * w, w, PW, p.C, ms.b(0));
   __syncthreads();
   for (int o = 0; o < p.nops; ++o) {
     const int op = p.op[o], arg = p.arg[o];
@@ -135,17 +124,9 @@ __global__ void __launch_bounds__(256) resnet_q_kernel(const T* __restrict__ x, 
       const int dst = ms.free_of(cur, skip);
       for (int px = threadIdx.x; px < h * w; px += 256) {
         const int y = px / w, xx = px % w;
-        const double q = ms.b(cur)[(y + 1) * PW + xx + 1];
-        double r, qa;
-        if (p.act == 0) {
-          r = q > 0.0 ? 1.0 / sqrt(q) : 0.0;
-          qa = 0.5 * q;
-        } else {
-          r = 1.0 / sqrt(1.0 + 2.0 * q);
-          qa = (2.0 / nngp::kPi) * asin(2.0 * q / (1.0 + 2.0 * q));
-        }
-        R[img * p.tab_stride + toff + px] = (T)r;
-        ms.b(dst)[(y + 1) * PW + xx + 1] = qa;
+        const DiagAct d = diag_act(p.act, ms.b(cur)[(y + 1) * PW + xx + 1]);   // (the bias is the Conv op's)
+        R[img * p.tab_stride + toff + px] = (T)d.ra;
+        ms.b(dst)[(y + 1) * PW + xx + 1] = d.qa;
       }
       ms.zero_ring(ms.b(dst), h, w);
       toff += h * w;
@@ -165,15 +146,8 @@ __global__ void __launch_bounds__(256) resnet_q_kernel(const T* __restrict__ x, 
     }
     __syncthreads();
   }
-  double s = 0.0;
-  for (int px = threadIdx.x; px < h * w; px += 256) s += ms.b(cur)[(px / w + 1) * PW + px % w + 1];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) diag[img] = (T)(p.lw2 * red[0] / (h * w));
+  const double k = block_mean(ms.b(cur), h, w, PW, p.lw2, red);
+  if (threadIdx.x == 0) diag[img] = (T)k;
 }
 
 // ---------------------------------------------------------------- per pair
@@ -199,11 +173,7 @@ __global__ void __launch_bounds__(256) resnet_pair_kernel(RPairArgs<T> a) {
   for (int64_t pr = (int64_t)blockIdx.x * 4 + wave; pr < a.npairs; pr += stride) {
     int64_t n, m;
     if (a.symmetric) {
-      int64_t r = (int64_t)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
-      while ((r + 1) * (r + 2) / 2 <= pr) ++r;
-      while (r * (r + 1) / 2 > pr) --r;
-      n = r;
-      m = pr - r * (r + 1) / 2;
+      tri_decode(pr, n, m);
     } else {
       n = pr / a.n2;
       m = pr % a.n2;
@@ -251,14 +221,7 @@ __global__ void __launch_bounds__(256) resnet_pair_kernel(RPairArgs<T> a) {
           const int y = (int)(((float)px + 0.5f) * inv), xx = px - y * w;
           const T k = ms.b(cur)[(y + 1) * PW + xx + 1];
           const T rr = r1[toff + px] * r2[toff + px];
-          T kn;
-          if (ACT == 0) {
-            const T ss = rr > T(0) ? T(1.0 / (2.0 * nngp::kPi)) * rcp_t<T>(rr) : T(0);
-            kn = nngp::relu_map<T, false>(k, rr, ss).k;
-          } else {
-            kn = nngp::erf_map<T, false>(k, rr, T(0)).k;
-          }
-          ms.b(dst)[(y + 1) * PW + xx + 1] = kn;
+          ms.b(dst)[(y + 1) * PW + xx + 1] = act_value<T, ACT>(k, rr);
         }
         ms.zero_ring(ms.b(dst), h, w);
         toff += h * w;
@@ -280,14 +243,7 @@ __global__ void __launch_bounds__(256) resnet_pair_kernel(RPairArgs<T> a) {
     }
     T s = T(0);
     for (int px = lane; px < h * w; px += 64) s += ms.b(cur)[(px / w + 1) * PW + px % w + 1];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) {
-      T v = (T)p.lw2 * s / (T)(h * w);
-      if (a.symmetric && n == m) v = a.diag[n];
-      a.out[n * a.ldo + m] = v;
-      if (a.symmetric && a.mirror && n != m) a.out[m * a.ldo + n] = v;
-    }
+    store_pair(a, n, m, s, h * w, lane);
   }
 }
 

@@ -17,6 +17,10 @@ HYP = dict(w_std=1.3, b_std=0.4, last_w_std=0.9, eps=5e-2, alpha=1.7, beta=2.4)
 # exact; 16 pixels per lane, ragged)
 SHAPES = [(24, 6, 6, 2, 3), (20, 5, 7, 3, 2), (12, 8, 8, 1, 4), (12, 32, 32, 3, 2), (12, 32, 32, 1, 4),
           (12, 12, 12, 1, 2), (12, 16, 16, 2, 2), (10, 20, 20, 1, 2)]
+# for the contraction alone: a ragged 4-per-lane image whose row stride does not divide 64 (the dummy slot of the wave's LDS
+# map), and the two most elongated images the pixel limit admits, whose padded maps are the largest (the per-image pass
+# needs 153 888 bytes of LDS there)
+MAP_SHAPES = [(6, 3, 50, 1, 2), (5, 1, 1024, 1, 2), (5, 1024, 1, 2, 2)]
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +115,7 @@ def device_terms(L, ctx, x, layers, act, hyp, nkinv, al, coef, dtype=np.float64)
 
 @pytest.mark.parametrize("method", ["gp", "tp"])
 @pytest.mark.parametrize("act", ["relu", "erf"])
-@pytest.mark.parametrize("n,h,w,c,layers", SHAPES)
+@pytest.mark.parametrize("n,h,w,c,layers", SHAPES + MAP_SHAPES)
 def test_contraction_alone_against_the_numpy_rules(L, ctx, n, h, w, c, layers, act, method):
     """smn_kernel_cnn_grad_terms fed -K~^-1 and alpha computed in NumPy, fp64: each term within 1e-9 * sum |G| |dK/d theta|
     -- the forward conv kernel's per-entry bound (1e-9 relative, tests/test_golden.py:108) carried through a sum whose

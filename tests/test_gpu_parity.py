@@ -353,7 +353,10 @@ def test_rccl_communicator_in_a_process_that_also_holds_torch(torch_first):
                                           ((3, 28, 28, 1), 2),      # 784 px: ragged 16-per-lane form (dummy-slot lanes)
                                           ((3, 20, 20, 2), 3),      # 400 px: ragged, most of the last rounds empty
                                           ((2, 40, 40, 1), 2),      # 1600 px: ragged 64-per-lane form
-                                          ((2, 64, 64, 1), 1)])     # 4096 px: the largest image, exact
+                                          ((2, 64, 64, 1), 1),      # 4096 px: the largest image, exact
+                                          ((3, 3, 50, 1), 2),       # 150 px: ragged 4-per-lane, a row stride that does not divide 64
+                                          ((3, 1, 1024, 1), 2),     # the largest padded maps: 3 x 1026 ...
+                                          ((3, 1024, 1, 2), 2)])    # ... and 1026 x 3 elements
 def test_cnn_kernel(dtype, act, shape, layers):
     """get_cnn_kernel (nt_kernels.py:34-45): symmetric, cross and odd image shapes vs the oracle."""
     from smnngp import nt_kernels
