@@ -327,6 +327,60 @@ int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
                           double eps_abs, double df, double scale,
                           double* quad_h, double* logdet_h, int* info_h, double terms_h[4]);
 
+/* ---- C target columns that share one kernel matrix: the exact multi-output GP / Student-t process (MultiSPR) ----
+ * A network with C outputs whose last-layer variance carries ONE inverse-gamma scale has a jointly multivariate-t prior over all
+ * N C outputs: vec(Y) ~ MVT_{NC}(nu = 2a, 0, s (I_C x K~)), s = b/a, K~ = K + eps I -- not C independent Student-t processes.
+ * With y_d [n,c] row-major, A = K~^-1 Y, Q = tr(Y^T K~^-1 Y) and ld = logdet K~:
+ *     Gaussian (df <= 0):  log p = -Q/2 - (n c / 2) log 2 pi - (c/2) ld        (the sum of c multivariate_normal.logpdf)
+ *     Student-t (df > 0):  the multivariate_t_logpdf of spax/utils.py:160-183 in dimension n c with quadratic form Q / scale
+ *                          and log-determinant c ld + n c log scale
+ *     d log p / d theta = 1/2 sum_ij G_ij dK~_ij/d theta,   G = coef A A^T - c K~^-1,
+ *     coef = 1 (Gaussian) or (df + n c) / ((df + Q/scale) scale) (Student-t)
+ * The c columns ride through ONE factorisation as c appended rows Y^T (n_total = n_pad + round_up(n + c, 128) for the gradient
+ * entries): K~, its factor, -K~^-1 and the tangent pass over the pairs are shared.  1 <= c <= 48 (the limit smn_predict has);
+ * c > 48 returns SMN_ENOTSUP.  At c = 1 every entry returns what its single-column counterpart returns.  A matrix that is
+ * not positive definite gives info > 0, NaN outputs and SMN_OK.  None of these entries reads or writes the Gram cache of
+ * smn_spr_loss.
+ * smn_lml_multi: smn_lml for y_d [n,c]: k_d [n,n] lower (destroyed) -> *logpdf_h (joint), *quad_h = Q, quad_cols_h [c] (may be
+ *   NULL) = y_k^T K~^-1 y_k per column, *logdet_h = ld, *info_h.  With smn_kernel_cnn in front: the conv build + joint LML.
+ * smn_spr_loss_multi: smn_spr_loss for y_d [n,c]: the fused build of the MLP / dense-ResNet kernel, same outputs.
+ * smn_lml_grad_terms_multi / smn_kernel_cnn_grad_terms_multi: the rank-c contraction alone, the counterparts of
+ *   smn_lml_grad_terms / smn_kernel_cnn_grad_terms: alpha_d [n,c] row-major = A, neg_kinv_d = -K~^-1;
+ *   terms_h[0..3] = sum_ij (coef sum_k A_ik A_jk + c (-K~^-1)_ij) dK~_ij/d{w_std, b_std, last_w_std, eps}.  Per entry (per image
+ *   pair) the c-term sum is formed once, behind the layer loop; the sums and the reduction tree are those of the single-column
+ *   kernels, so two calls give the same bits.
+ * smn_spr_loss_grad_multi / smn_spr_cnn_loss_grad_multi: everything from x and Y, the counterparts of smn_spr_loss_grad /
+ *   smn_spr_cnn_loss_grad: *quad_h = Q, quad_cols_h [c] (may be NULL), *logdet_h, *info_h, terms_h[4]; the host forms the
+ *   log-pdf and the (a, b) derivatives from them.  The conv entries keep the limit H*W <= SMN_CNN_GRAD_MAX_PIXELS. */
+int smn_lml_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
+                  double eps_abs, double df, double scale, double* logpdf_h, double* quad_h, double* quad_cols_h,
+                  double* logdet_h, int* info_h);
+int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                       double w_std, double b_std, double last_w_std,
+                       const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                       double eps_abs, double df, double scale,
+                       double* logpdf_h, double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h);
+int smn_lml_grad_terms_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                             double w_std, double b_std, double last_w_std,
+                             const void* k0_d, int64_t n, int64_t ldk0, const void* q_d,
+                             const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, int64_t c,
+                             double coef, double terms_h[4]);
+int smn_kernel_cnn_grad_terms_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                                    double w_std, double b_std, double last_w_std,
+                                    const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                                    const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, int64_t c,
+                                    double coef, double terms_h[4]);
+int smn_spr_loss_grad_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                            double w_std, double b_std, double last_w_std,
+                            const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                            double eps_abs, double df, double scale,
+                            double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]);
+int smn_spr_cnn_loss_grad_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                                double w_std, double b_std, double last_w_std,
+                                const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c,
+                                double eps_abs, double df, double scale,
+                                double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]);
+
 /* ---- sparse variational classifier, evaluation (spax/models.py:58-78 SVSP.test_acc_nll; experiments/classification/test.py) ----
  * With inducing images Z [I], q_mu [C,I], q_var [C,I] = diag(q_sqrt) as the reference uses it (NOT squared) and K the NNGP kernel:
  *     K_rel = K_ZZ + eps tr(K_ZZ)/I I   (NNGPKernel.predict: relative ridge)      K_abs = K_ZZ + eps I   (models.py:68)

@@ -95,6 +95,13 @@ PROTOTYPES = {
     "smn_kernel_cnn_grad_terms": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _d, _pd],
     "smn_kernel_cnn_input_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp],
     "smn_spr_cnn_loss_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _d, _d, _d, _pd, _pd, _pi, _pd],
+    "smn_lml_multi": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pd, _pi],
+    "smn_spr_loss_multi": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pd, _pi],
+    "smn_lml_grad_terms_multi": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _d, _pd],
+    "smn_kernel_cnn_grad_terms_multi": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _d, _pd],
+    "smn_spr_loss_grad_multi": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pi, _pd],
+    "smn_spr_cnn_loss_grad_multi": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd,
+                                    _pi, _pd],
     "smn_kernel_conv_diag": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp],
     "smn_svsp_moments": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _d, _vp, _vp, _pi, _pi64],
     "smn_mc_softmax": [_vp, _i, _vp, _vp, _pi, _i64, _i64, _i64, _d, C.c_uint64, _i64, _vp, _vp, _vp, _vp],

@@ -1069,6 +1069,52 @@ __global__ void __launch_bounds__(256) rows_dot_kernel(const T* __restrict__ x, 
   }
 }
 
+// The same for c right-hand sides (MultiSPR): z [c, kcols] with ld = ldz, alpha [n, c] row-major, quad [c].  A wave reads its
+// row of x once per group of CB columns; each column's sum runs in rows_dot_kernel's order (c = 1 gives its bits), and block k
+// < c leaves quad[k] by the same tree.  The grid has at least c blocks.
+template <typename T, int CB>
+__global__ void __launch_bounds__(256) rows_dot_multi_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ z, int64_t ldz,
+                                                             int64_t kcols, int64_t n, int c, T* __restrict__ alpha,
+                                                             double* __restrict__ quad) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < n) {
+    for (int c0 = 0; c0 < c; c0 += CB) {
+      double s[CB];
+#pragma unroll
+      for (int e = 0; e < CB; ++e) s[e] = 0.0;
+      for (int64_t k = row / kTile * kTile + lane; k < kcols; k += 64) {
+        const double xv = (double)x[row * ldx + k];
+#pragma unroll
+        for (int e = 0; e < CB; ++e) {
+          const int ce = c0 + e < c ? c0 + e : c - 1;
+          s[e] += xv * (double)z[(int64_t)ce * ldz + k];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        double v = s[e];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0 && c0 + e < c) alpha[row * c + c0 + e] = (T)v;
+      }
+    }
+  }
+  if ((int)blockIdx.x < c) {
+    __shared__ double red[256];
+    const T* zk = z + (int64_t)blockIdx.x * ldz;
+    double s = 0.0;
+    for (int64_t k = threadIdx.x; k < kcols; k += 256) s += (double)zk[k] * (double)zk[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) quad[blockIdx.x] = red[0];
+  }
+}
+
 template <typename T>
 __global__ void diag_trace_kernel(const T* __restrict__ a, int64_t lda, int64_t n, double* __restrict__ out) {
   // single block; deterministic tree
@@ -1457,7 +1503,7 @@ int cholesky_t(smn_ctx* ctx, const FactorCall& f) {
 
 // K~^-1 and alpha from the appended rows of a no-Schur factorisation of [[K~], [I], [y^T]] (internal.hpp).
 int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const void* z, int64_t kcols, int64_t n,
-                      void* neg_inv, int64_t ldo, void* alpha, double* quad_dev) {
+                      void* neg_inv, int64_t ldo, void* alpha, double* quad_dev, int64_t c, int64_t ldz) {
   const int64_t t = (n + kTile - 1) / kTile, ntiles = t * (t + 1) / 2;
   if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx)); else SMN_TRY(set_lds_attrs<float>(ctx));
   {
@@ -1475,6 +1521,17 @@ int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const
   }
   SMN_CHECK_LAUNCH(ctx);
   const unsigned gb = (unsigned)((n + 3) / 4);
+  if (c > 1) {   // c right-hand sides: alpha [n, c], quad_dev [c]
+    const unsigned gm = gb > (unsigned)c ? gb : (unsigned)c;
+    if (dtype == SMN_F64)
+      hipLaunchKernelGGL((rows_dot_multi_kernel<double, 8>), dim3(gm), dim3(256), 0, ctx->stream, static_cast<const double*>(x), ldx,
+                         static_cast<const double*>(z), ldz, kcols, n, (int)c, static_cast<double*>(alpha), quad_dev);
+    else
+      hipLaunchKernelGGL((rows_dot_multi_kernel<float, 8>), dim3(gm), dim3(256), 0, ctx->stream, static_cast<const float*>(x), ldx,
+                         static_cast<const float*>(z), ldz, kcols, n, (int)c, static_cast<float*>(alpha), quad_dev);
+    SMN_CHECK_LAUNCH(ctx);
+    return SMN_OK;
+  }
   if (dtype == SMN_F64)
     hipLaunchKernelGGL(rows_dot_kernel<double>, dim3(gb), dim3(256), 0, ctx->stream, static_cast<const double*>(x), ldx,
                        static_cast<const double*>(z), kcols, n, static_cast<double*>(alpha), quad_dev);

@@ -87,6 +87,7 @@ struct CGradArgs {
   const T* alpha;
   double coef;
   double* partial;         // [gridDim.x * 4 waves][4]
+  int nc;                  // MULTI forms: alpha is [n, nc] row-major
 };
 
 // Workgroups per CU a form is compiled for.  The state is three values per owned pixel: 16 pixels in fp64 are 96 VGPRs
@@ -106,7 +107,10 @@ constexpr int cgrad_occ(int np) {
 // PairWalk order, ONE padded map per wave (WaveMap).  A layer takes the box sum of K through the map, then reuses the map for
 // Kw and for Kb, so the LDS footprint is the forward kernel's.  Per-element arithmetic in T, the four sums in double, one
 // partial per wave.
-template <typename T, int ACT, int NP, bool EXACT>
+// MULTI (the rank-C form, MultiSPR): G_nm = coef sum_c A_nc A_mc + C (-K~^-1)_nm with A = alpha [n, nc], formed once per pair
+// BEHIND the layer loop from wave-uniform rows of A, so nothing is added to what lives across the loop; nc = 1 gives the
+// single-column form's bits.
+template <typename T, int ACT, int NP, bool EXACT, bool MULTI = false>
 __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGradArgs<T> g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const PairArgs<T>& a = g.pa;
@@ -175,7 +179,15 @@ __global__ void __launch_bounds__(256, cgrad_occ<T>(NP)) cgrad_pair_kernel(CGrad
       s[1] = (T)g.dexact[n * 3 + 2];
       s[2] = (T)g.dexact[n * 3 + 0];
     }
-    const T gv = fma(coef * g.alpha[n], g.alpha[m], g.nkinv[n * g.ldki + m]);
+    T gv;
+    if (MULTI) {
+      gv = (T)g.nc * g.nkinv[n * g.ldki + m];
+      const T* rn = g.alpha + n * g.nc;
+      const T* rm = g.alpha + m * g.nc;
+      for (int c = 0; c < g.nc; ++c) gv = fma(coef * rn[c], rm[c], gv);
+    } else {
+      gv = fma(coef * g.alpha[n], g.alpha[m], g.nkinv[n * g.ldki + m]);
+    }
     const T gm = dg ? gv : T(2) * gv;   // the upper triangle is the mirror image
     acc[0] += (double)(gm * s[0]);
     acc[1] += (double)(gm * s[1]);
@@ -222,9 +234,14 @@ int cgrad_launch_form(smn_ctx* ctx, K kern, CGradArgs<T> g, int64_t* blocks_io, 
 }
 
 template <typename T, int ACT>
-int cgrad_launch(smn_ctx* ctx, const CGradArgs<T>& g, int64_t* blocks_io, int64_t max_blocks, size_t lds, int64_t hw) {
+int cgrad_launch(smn_ctx* ctx, const CGradArgs<T>& g, int64_t* blocks_io, int64_t max_blocks, size_t lds, int64_t hw, bool multi) {
   const bool w64 = 64 % g.pa.prog.W == 0;
 #define CGRAD_CASE(NP)                                                                                               \
+  if (hw <= 64 * NP && multi) {                                                                                      \
+    if (hw == 64 * NP && w64)                                                                                        \
+      return cgrad_launch_form<T>(ctx, cgrad_pair_kernel<T, ACT, NP, true, true>, g, blocks_io, max_blocks, lds);    \
+    return cgrad_launch_form<T>(ctx, cgrad_pair_kernel<T, ACT, NP, false, true>, g, blocks_io, max_blocks, lds);     \
+  }                                                                                                                  \
   if (hw <= 64 * NP) {                                                                                               \
     if (hw == 64 * NP && w64)                                                                                        \
       return cgrad_launch_form<T>(ctx, cgrad_pair_kernel<T, ACT, NP, true>, g, blocks_io, max_blocks, lds);          \
@@ -240,7 +257,7 @@ int cgrad_launch(smn_ctx* ctx, const CGradArgs<T>& g, int64_t* blocks_io, int64_
 template <typename T>
 int cgrad_terms_t(smn_ctx* ctx, int act, int layers, double w_std, double b_std, double last_w_std, const void* x_d,
                   int64_t n, int64_t H, int64_t W, int64_t C, const void* nkinv, int64_t ldki, const void* alpha, double coef,
-                  double out_h[4]) {
+                  double out_h[4], int nc = 0) {   // nc > 0: the rank-C form, alpha [n, nc]
   const ConvProg p = make_prog(act, layers, H, W, C, w_std, b_std, last_w_std);
   const int64_t HW = H * W;
   const size_t psz = (size_t)(H + 2) * (W + 2);
@@ -282,10 +299,11 @@ int cgrad_terms_t(smn_ctx* ctx, int act, int layers, double w_std, double b_std,
   g.dexact = dexact;
   g.nkinv = static_cast<const T*>(nkinv); g.ldki = ldki;
   g.alpha = static_cast<const T*>(alpha);
+  g.nc = nc > 0 ? nc : 1;
   g.coef = coef;
   g.partial = partial;
-  SMN_TRY(act == SMN_ACT_RELU ? (cgrad_launch<T, 0>(ctx, g, &blocks, max_blocks, lds_p, HW))
-                              : (cgrad_launch<T, 1>(ctx, g, &blocks, max_blocks, lds_p, HW)));
+  SMN_TRY(act == SMN_ACT_RELU ? (cgrad_launch<T, 0>(ctx, g, &blocks, max_blocks, lds_p, HW, nc > 0))
+                              : (cgrad_launch<T, 1>(ctx, g, &blocks, max_blocks, lds_p, HW, nc > 0)));
   SMN_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(cgrad_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, partial, blocks * 4, out_d);
   SMN_CHECK_LAUNCH(ctx);
@@ -357,4 +375,62 @@ extern "C" int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_h
   if (df > 0.0) coef = (df + (double)n) / ((df + quad / scale) * scale);
   return smn_kernel_cnn_grad_terms(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, alpha,
                                    coef, terms_h);
+}
+
+// The rank-C contraction alone: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1.
+extern "C" int smn_kernel_cnn_grad_terms_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                                               double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                                               const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, int64_t c,
+                                               double coef, double terms_h[4]) {
+  if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms_multi", dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (ldkinv < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms_multi: bad sizes");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms_multi: more than 48 output columns");
+  if (dtype == SMN_F64)
+    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                                 coef, terms_h, (int)c);
+  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                              coef, terms_h, (int)c);
+}
+
+// smn_spr_cnn_loss_grad for c target columns that share K~: the forward build, one factorisation of [[K~], [I], [Y^T]], one
+// rank-C contraction over the image pairs.
+extern "C" int smn_spr_cnn_loss_grad_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                                           double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                                           const void* y_d, int64_t c, double eps_abs, double df, double scale, double* quad_h,
+                                           double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, "smn_spr_cnn_loss_grad_multi", dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad_multi: bad sizes");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_cnn_loss_grad_multi: more than 48 output columns");
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad_multi: scale must be > 0");
+  const size_t es = dtype_size(dtype);
+  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
+  void* post = nullptr;
+  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
+  void* ninv = post;
+  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
+  double quad[48], logdet = 0.0, tot = 0.0;
+  int info = 0;
+  const KernelInto build = [&](void* k_d, int64_t ldk) {
+    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER,
+                          k_d, ldk);
+  };
+  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, quad, &logdet, &info, c));
+  for (int64_t k = 0; k < c; ++k) tot += quad[k];
+  if (info != 0) tot = std::nan("");
+  if (quad_h) *quad_h = tot;
+  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = quad[k];
+  if (logdet_h) *logdet_h = logdet;
+  if (info_h) *info_h = info;
+  if (info != 0) {
+    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
+    return SMN_OK;
+  }
+  double coef = 1.0;
+  if (df > 0.0) coef = (df + (double)n * (double)c) / ((df + tot / scale) * scale);
+  return smn_kernel_cnn_grad_terms_multi(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, alpha,
+                                         c, coef, terms_h);
 }

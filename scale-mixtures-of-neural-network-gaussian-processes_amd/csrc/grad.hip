@@ -158,6 +158,7 @@ struct GradArgs {
   const T* k0; int64_t ldk0;
   const T* nkinv; int64_t ldki;      // -K~^-1
   const T* alpha;
+  int nc;                            // MULTI forms: alpha is [n, nc] row-major (one row of coefficients per point)
   int64_t n;
   const R* tab;                      // grad_tables_kernel output
   int nsets;
@@ -172,7 +173,10 @@ constexpr int GT = 64;               // tile edge of the contraction
 // layer, the row-side ones are wave-uniform (scalar loads).  Products in R, the four sums in double.
 // INPLACE (the batched form): -K~^-1 and alpha are read where the joint factorisation left them -- the lower triangle of the
 // Schur block (what extract_posterior mirrors into the serial call's copy) and the NEGATED right-hand-side row.
-template <typename T, int NET, int ACT, bool INPLACE>
+// MULTI (the rank-C form, MultiSPR): g = coef sum_c A_ic A_jc + C (-K~^-1)_ij with A = alpha [n, nc], formed once per entry
+// BEHIND the layer loop, so the loop's live state is the single-column form's; the sums and the reduction tree are the same, and
+// nc = 1 gives the single-column form's bits.
+template <typename T, int NET, int ACT, bool INPLACE, bool MULTI = false>
 __device__ __forceinline__ void grad_contract_tile(const GradArgs<T>& a, double* __restrict__ partial) {
   using R = typename GradArgs<T>::R;
   int tr, tc;
@@ -226,15 +230,33 @@ __device__ __forceinline__ void grad_contract_tile(const GradArgs<T>& a, double*
     }
   }
   double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum G dK/dw2, sum G dK/db2, sum G K, tr G
-  const R aj = INPLACE ? -(R)a.alpha[jc] : (R)a.alpha[jc], coef = (R)a.coef, lw2 = (R)a.lw2;
+  const R coef_r = (R)a.coef;
+  R gc[MULTI ? NR : 1];   // MULTI: C (-K~^-1)_ij + coef sum_c A_ic A_jc, column by column (the thread's row of A is read once)
+  if (MULTI) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int64_t i = row0 + w + 4 * r, ic = i < n ? i : n - 1;
+      gc[r] = R(a.nc) * (R)a.nkinv[ic * a.ldki + jc];
+    }
+    const T* rj = a.alpha + jc * a.nc;
+    for (int c = 0; c < a.nc; ++c) {
+      const R ajc = (R)rj[c];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int64_t i = row0 + w + 4 * r, ic = i < n ? i : n - 1;   // wave-uniform
+        gc[r] = fma(coef_r * (R)a.alpha[ic * a.nc + c], ajc, gc[r]);
+      }
+    }
+  }
+  const R aj = MULTI ? R(0) : (INPLACE ? -(R)a.alpha[jc] : (R)a.alpha[jc]), coef = (R)a.coef, lw2 = (R)a.lw2;
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int64_t i = row0 + w + 4 * r, ic = i < n ? i : n - 1;
     const bool valid = i < n && j < n && j <= i;
-    const R ai = INPLACE ? -(R)a.alpha[ic] : (R)a.alpha[ic];
+    const R ai = MULTI ? R(0) : (INPLACE ? -(R)a.alpha[ic] : (R)a.alpha[ic]);
     const int64_t hi = ic > jc ? ic : jc, lo = ic > jc ? jc : ic;
     const R ninv = INPLACE ? (R)a.nkinv[hi * a.ldki + lo] : (R)a.nkinv[ic * a.ldki + jc];
-    const R g = fma(coef * ai, aj, ninv);
+    const R g = MULTI ? gc[r] : fma(coef * ai, aj, ninv);
     const R m = !valid ? R(0) : (i == j ? R(1) : R(2));   // the upper triangle is the mirror image
     const R gm = m * g * lw2;
     acc[0] += (double)(gm * dw[r]);
@@ -257,6 +279,11 @@ __device__ __forceinline__ void grad_contract_tile(const GradArgs<T>& a, double*
 template <typename T, int NET, int ACT>
 __global__ void __launch_bounds__(256) grad_contract_kernel(GradArgs<T> a) {
   grad_contract_tile<T, NET, ACT, false>(a, a.partial);
+}
+
+template <typename T, int NET, int ACT>
+__global__ void __launch_bounds__(256) grad_contract_multi_kernel(GradArgs<T> a) {
+  grad_contract_tile<T, NET, ACT, false, true>(a, a.partial);
 }
 
 // Second stage: fixed-order sum of the per-tile partials (bitwise reproducible).
@@ -331,7 +358,7 @@ __global__ void __launch_bounds__(256) grad_contract_batch_kernel(GradBatchArgs<
   a.k0 = b.k0; a.ldk0 = b.ldk0;
   a.nkinv = m + b.aug0 * b.lda + b.aug0; a.ldki = b.lda;
   a.alpha = m + (b.aug0 + b.n) * b.lda + b.aug0;
-  a.n = b.n; a.tab = b.tab + y * b.tab_bs; a.nsets = b.nsets;
+  a.nc = 1; a.n = b.n; a.tab = b.tab + y * b.tab_bs; a.nsets = b.nsets;
   a.w2 = p.w2; a.b2 = p.b2; a.lw2 = p.lw2;
   a.coef = grad_coef(p.df, p.scale, -(double)m[(b.aug0 + b.n) * b.lda + b.aug0 + b.n], b.n);
   a.partial = nullptr;
@@ -399,13 +426,14 @@ __global__ void cast_q_kernel(const T* __restrict__ s, double* __restrict__ d, i
 }
 
 template <typename T, int NET, int ACT>
-int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t ntiles, double* out_d) {
+int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t ntiles, double* out_d, bool multi) {
   hipLaunchKernelGGL((grad_tables_kernel<NET, ACT, T>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream,
                      q64, a.n, a.nsets, a.w2, a.b2, const_cast<T*>(a.tab));
   SMN_CHECK_LAUNCH(ctx);
   {
     ProfScope ps(ctx, PROF_MISC, ctx->stream);
-    hipLaunchKernelGGL((grad_contract_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
+    if (multi) hipLaunchKernelGGL((grad_contract_multi_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((grad_contract_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
   }
   SMN_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, a.partial, ntiles, out_d);
@@ -416,7 +444,8 @@ int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t
 template <typename T>
 int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
                  const void* k0, int64_t n, int64_t ldk0, const void* q, const void* nkinv, int64_t ldki,
-                 const void* alpha, double coef, double out_h[4]) {
+                 const void* alpha, double coef, double out_h[4], int nc = 0) {   // nc > 0: the rank-C form, alpha [n, nc]
+  const bool multi = nc > 0;
   const int nsets = net == SMN_NET_MLP ? num_hiddens : num_hiddens + 1;
   if (nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "num_hiddens too large (max %d activation layers)", kMaxSets);
   const int64_t t = (n + GT - 1) / GT, ntiles = t * (t + 1) / 2;
@@ -435,14 +464,15 @@ int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, 
   a.k0 = static_cast<const T*>(k0); a.ldk0 = ldk0;
   a.nkinv = static_cast<const T*>(nkinv); a.ldki = ldki;
   a.alpha = static_cast<const T*>(alpha);
+  a.nc = multi ? nc : 1;
   a.n = n; a.tab = reinterpret_cast<const T*>(tabd); a.nsets = nsets;
   a.w2 = w_std * w_std; a.b2 = b_std * b_std; a.lw2 = last_w_std * last_w_std; a.coef = coef;
   a.partial = partial;
   int rc;
-  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_MLP, ACT_RELU>(ctx, a, q64, ntiles, out_d);
-  else if (net == SMN_NET_MLP) rc = grad_terms_na<T, NET_MLP, ACT_ERF>(ctx, a, q64, ntiles, out_d);
-  else if (act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_RESNET, ACT_RELU>(ctx, a, q64, ntiles, out_d);
-  else rc = grad_terms_na<T, NET_RESNET, ACT_ERF>(ctx, a, q64, ntiles, out_d);
+  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_MLP, ACT_RELU>(ctx, a, q64, ntiles, out_d, multi);
+  else if (net == SMN_NET_MLP) rc = grad_terms_na<T, NET_MLP, ACT_ERF>(ctx, a, q64, ntiles, out_d, multi);
+  else if (act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_RESNET, ACT_RELU>(ctx, a, q64, ntiles, out_d, multi);
+  else rc = grad_terms_na<T, NET_RESNET, ACT_ERF>(ctx, a, q64, ntiles, out_d, multi);
   SMN_TRY(rc);
   double s[4];
   SMN_HIP(ctx, hipMemcpyAsync(s, out_d, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
@@ -602,6 +632,68 @@ extern "C" int smn_lml_grad_terms(smn_ctx* ctx, int dtype, int net, int act, int
                                 ldkinv, alpha_d, coef, terms_h);
   return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
                              alpha_d, coef, terms_h);
+}
+
+// The rank-C contraction alone: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1.
+extern "C" int smn_lml_grad_terms_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
+                                        double b_std, double last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
+                                        const void* q_d, const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d,
+                                        int64_t c, double coef, double terms_h[4]) {
+  if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || ldk0 < n || ldkinv < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad sizes");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_grad_terms_multi: more than 48 output columns");
+  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
+  if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad hyper-parameters");
+  if (dtype == SMN_F64)
+    return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
+                                ldkinv, alpha_d, coef, terms_h, (int)c);
+  return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
+                             alpha_d, coef, terms_h, (int)c);
+}
+
+// smn_spr_loss_grad for c target columns that share K~: one factorisation of [[K~], [I], [Y^T]] (heads.hip), one rank-C
+// contraction.  coef of the joint Student-t head: (df + n c) / ((df + Q / s) s), Q = the sum of the c quadratic forms.
+extern "C" int smn_spr_loss_grad_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
+                                       double b_std, double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d,
+                                       const void* y_d, int64_t c, double eps_abs, double df, double scale, double* quad_h,
+                                       double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: empty");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_grad_multi: more than 48 output columns");
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: scale must be > 0");
+  const size_t es = dtype_size(dtype);
+  const int64_t al = 16 / (int64_t)es;
+  const int64_t ld0 = round_up(n, al);
+  void *k0 = nullptr, *post = nullptr;
+  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
+  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
+  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
+  void* ninv = post;
+  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
+  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));
+  double quad[48], logdet = 0.0, tot = 0.0;
+  int info = 0;
+  SMN_TRY(factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, ld0, q, n, y_d, eps_abs, alpha,
+                               ninv, ld0, quad, &logdet, &info, c));
+  for (int64_t k = 0; k < c; ++k) tot += quad[k];
+  if (info != 0) tot = std::nan("");
+  if (quad_h) *quad_h = tot;
+  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = quad[k];
+  if (logdet_h) *logdet_h = logdet;
+  if (info_h) *info_h = info;
+  if (info != 0) {
+    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
+    return SMN_OK;
+  }
+  double coef = 1.0;
+  if (df > 0.0) coef = (df + (double)n * (double)c) / ((df + tot / scale) * scale);
+  return smn_lml_grad_terms_multi(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, n, ld0, q, ninv, ld0, alpha, c,
+                                  coef, terms_h);
 }
 
 // Fused: K0 = X X^T / d and its diagonal, K by the stand-alone recursion straight into the factorisation workspace

@@ -38,6 +38,8 @@ int aug_alloc(smn_ctx* ctx, int dtype, int64_t n, int64_t t, int64_t c, Aug* g) 
   return smn_workspace(ctx, 2, g->es * (size_t)g->n_total * (size_t)g->n_total, &g->a);
 }
 
+}  // namespace
+
 // Gaussian / multivariate-t log-pdf from (quad = y^T cov^-1 y, logdet = log det cov).
 double logpdf_from(double quad, double logdet, int64_t n, double df, double scale, int info) {
   if (info != 0 || std::isnan(quad) || std::isnan(logdet)) return std::nan("");
@@ -51,6 +53,8 @@ double logpdf_from(double quad, double logdet, int64_t n, double df, double scal
   return -t * std::log1p(quad_s / df) - 0.5 * nn * std::log(df * M_PI) + std::lgamma(t) - std::lgamma(0.5 * df) -
          0.5 * logdet_s;
 }
+
+namespace {
 
 // Fused build of the augmented matrix straight from the inputs.
 // out: the caller goes on to aug_finish with it.  Under the look-ahead the bottom-right corner of the matrix is then built
@@ -248,6 +252,43 @@ extern "C" int smn_lml(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ld
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
   if (info_h) *info_h = info;
+  return SMN_OK;
+}
+
+namespace {
+// the joint head of c target columns from their quadratic forms: total quad, log-pdf in dimension n c with logdet c logdet K~
+void multi_head(const double* quad, int64_t c, double ld, int info, int64_t n, double df, double scale, double* logpdf_h,
+                double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h) {
+  double tot = 0.0;
+  for (int64_t k = 0; k < c; ++k) tot += quad[k];
+  if (info != 0) tot = std::nan("");
+  if (logpdf_h) *logpdf_h = logpdf_from(tot, (double)c * ld, n * c, df, scale, info);
+  if (quad_h) *quad_h = tot;
+  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = info != 0 ? std::nan("") : quad[k];
+  if (logdet_h) *logdet_h = ld;
+  if (info_h) *info_h = info;
+}
+}  // namespace
+
+// smn_lml for c target columns that share K: one factorisation carrying the c rows Y^T.
+extern "C" int smn_lml_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
+                             double eps_abs, double df, double scale, double* logpdf_h, double* quad_h, double* quad_cols_h,
+                             double* logdet_h, int* info_h) {
+  if (!ctx || !k_d || !y_d) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || ldk < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: bad sizes");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_multi: more than 48 output columns");
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: scale must be > 0");
+  Aug g;
+  SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
+  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
+  SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, k_d, ldk, n, n, 1));
+  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
+  double quad[48], ld = 0.0;
+  int info = 0;
+  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
+  multi_head(quad, c, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
 }
 
@@ -505,11 +546,15 @@ bool grad_uses_rectangle(int64_t n) { return round_up(n, kTile) >= kGradRectFrom
 
 // `build` writes the lower triangle of K (n rows, exact diagonal, no jitter) into the matrix it is handed: the layer recursion of
 // a Gram matrix for the MLP family (factor_with_identity below), the conv pair build for smn_spr_cnn_loss_grad (cnn_grad.hip).
+// c target columns (y_d [n, c] row-major): c rows Y^T behind the identity block, n_total = n_pad + round_up(n + c, 128);
+// alpha_d [n, c] row-major and one quadratic form per column in quad_h [c].
 int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
-                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h) {
+                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h,
+                               int64_t c) {
+  if (c < 1 || c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");   // the mailbox holds 62 doubles
   if (round_up(n, kTile) < kGradRectFromN) {
     Aug g;
-    SMN_TRY(aug_alloc(ctx, dtype, n, n, 1, &g));
+    SMN_TRY(aug_alloc(ctx, dtype, n, n, c, &g));
     SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
     SMN_TRY(build(g.a, g.lda));
     if (dtype == SMN_F64)
@@ -520,10 +565,10 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
                          reinterpret_cast<float*>(g.at(g.n_pad, 0)), g.lda, n);
     SMN_CHECK_LAUNCH(ctx);
     SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-    return aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, true);
+    return aug_finish(ctx, dtype, g, {}, y_d, c, n, eps_abs, 0.0, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, true);
   }
   const size_t es = dtype_size(dtype);
-  const int64_t n_pad = round_up(n, kTile), n_app = round_up(n + 1, kTile), n_total = n_pad + n_app, lda = n_pad;
+  const int64_t n_pad = round_up(n, kTile), n_app = round_up(n + c, kTile), n_total = n_pad + n_app, lda = n_pad;
   void* av = nullptr;
   SMN_TRY(smn_workspace(ctx, 2, es * (size_t)n_total * (size_t)lda, &av));
   char* a = static_cast<char*>(av);
@@ -538,20 +583,21 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
                        reinterpret_cast<float*>(xrows), lda, n);
   SMN_CHECK_LAUNCH(ctx);
   SMN_TRY(fill_identity_pad(ctx, dtype, a, lda, n_pad, n));
-  // y^T in the row behind the identity block, the absolute jitter on the diagonal, logdet / info reset: one launch
-  SMN_TRY(aug_prep(ctx, dtype, a, lda, n_pad + n, n_pad, y_d, n, 1, 1, eps_abs != 0.0 ? n : 0, eps_abs));
+  // Y^T in the rows behind the identity block, the absolute jitter on the diagonal, logdet / info reset: one launch
+  SMN_TRY(aug_prep(ctx, dtype, a, lda, n_pad + n, n_pad, y_d, n, c, c, eps_abs != 0.0 ? n : 0, eps_abs));
   FactorCall f{dtype, a, n_total, n_pad, lda, n, eps_abs, 0.0, false};
   f.id0 = n_pad;
   f.id1 = n_pad + n / kTile * kTile;
   f.prepped = f.noschur = true;
   SMN_TRY(cholesky_padded(ctx, f));
   double* quad_dev = ctx->d_scal + 8;
-  SMN_TRY(inverse_from_rows(ctx, dtype, xrows, lda, xrows + es * (size_t)n * (size_t)lda, n_pad, n, ninv_d, ldinv, alpha_d, quad_dev));
-  double ld = 0.0, quad = 0.0;
+  SMN_TRY(inverse_from_rows(ctx, dtype, xrows, lda, xrows + es * (size_t)n * (size_t)lda, n_pad, n, ninv_d, ldinv, alpha_d, quad_dev,
+                            c, lda));
+  double ld = 0.0, quad[48];
   int info = 0;
-  SMN_TRY(fetch_results(ctx, quad_dev, 1, &quad, &ld, &info));
-  if (info != 0) ld = quad = std::nan("");
-  if (quad_h) *quad_h = quad;
+  SMN_TRY(fetch_results(ctx, quad_dev, (int)c, quad, &ld, &info));
+  if (info != 0) ld = std::nan("");
+  for (int64_t k = 0; k < c && quad_h; ++k) quad_h[k] = info != 0 ? std::nan("") : quad[k];
   if (logdet_h) *logdet_h = ld;
   if (info_h) *info_h = info;
   return SMN_OK;
@@ -560,12 +606,12 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
 int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
                          double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
                          double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h) {
+                         int* info_h, int64_t c) {
   const KernelInto build = [&](void* k_d, int64_t ldk) {
     return smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
                          SMN_GET_NNGP, k_d, nullptr, ldk);
   };
-  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h);
+  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, c);
 }
 
 int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,
@@ -620,6 +666,29 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
   if (info_h) *info_h = info;
+  return SMN_OK;
+}
+
+// smn_spr_loss for c target columns: the fused build (no Gram cache: workspace slot 0), one factorisation carrying Y^T.
+extern "C" int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                                  double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
+                                  int64_t c, double eps_abs, double df, double scale, double* logpdf_h, double* quad_h,
+                                  double* quad_cols_h, double* logdet_h, int* info_h) {
+  if (!ctx || !x_d || !y_d) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_multi: empty");
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_multi: more than 48 output columns");
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_multi: scale must be > 0");
+  Aug g;
+  SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
+  BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
+  BuildOut built;
+  double quad[48], ld = 0.0;
+  int info = 0;
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built));
+  SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
+  multi_head(quad, c, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
 }
 

@@ -123,14 +123,19 @@ int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int
                   double* logdet_h, int* info_h);
 // alpha = K~^-1 y and -K~^-1 for the analytic gradients: a no-Schur factorisation of the rectangle [[K~], [I], [y^T]] (K from
 // the Gram matrix k0 by the layer recursion, in place), then -L^-T L^-1 as one launch (heads.hip)
+// c target columns (y_d [n, c] row-major, 1 <= c <= 48): [[K~], [I], [Y^T]] with n_total = n_pad + round_up(n + c, 128);
+// alpha_d [n, c] row-major, quad_h [c] (one quadratic form per column).
 int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
                          double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
                          double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h);
+                         int* info_h, int64_t c = 1);
 // the same with K written by the caller: build(k_d, ldk) fills the lower triangle of K (n rows) in the factorisation workspace
 using KernelInto = std::function<int(void* k_d, int64_t ldk)>;
 int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
-                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h);
+                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h,
+                               int64_t c = 1);
+// Gaussian / multivariate-t log-pdf from (quad = y^T cov^-1 y, logdet = log det cov) in dimension n (heads.hip)
+double logpdf_from(double quad, double logdet, int64_t n, double df, double scale, int info);
 // true from the size on at which the gradient takes the rectangle route instead of the joint factorisation (heads.hip)
 bool grad_uses_rectangle(int64_t n);
 int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info);
@@ -144,9 +149,10 @@ int recursion_lower_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hid
                           const double* b_std, const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
                           const void* q_d, void* out_d, int64_t ldo, int64_t out_bs, std::vector<char>& stage);
 // -x x^T (lower, into neg_inv [n, n] ld = ldo) and alpha = x z from the rows x [n, kcols] (ld = ldx, row i zero left of its
-// 128-column tile) and the vector z [kcols]; *quad_dev = z^T z.  cholesky.hip.
+// 128-column tile) and the vector z [kcols]; *quad_dev = z^T z.  c > 1: z [c, kcols] (ld = ldz) holds c vectors, alpha is
+// [n, c] row-major and quad_dev [c].  cholesky.hip.
 int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const void* z, int64_t kcols, int64_t n,
-                      void* neg_inv, int64_t ldo, void* alpha, double* quad_dev);
+                      void* neg_inv, int64_t ldo, void* alpha, double* quad_dev, int64_t c = 1, int64_t ldz = 0);
 // logdet, info and nq device doubles (quadratic forms) through the pinned mailbox: one tiny kernel + ONE synchronisation
 int fetch_results(smn_ctx* ctx, const double* quad_dev, int nq, double* quad_h, double* logdet, int* info);
 

@@ -1,4 +1,5 @@
-"""spax/models.py mirror — SPR (exact GP / Student-t process regression) and SVSP (the sparse variational scale-mixture
+"""spax/models.py mirror — SPR (exact GP / Student-t process regression), MultiSPR (the same for C outputs that share
+one kernel matrix: exact multi-class classification on one-hot targets) and SVSP (the sparse variational scale-mixture
 classifier): evaluation (test_acc_nll / evaluate) and the training loss with its analytic gradient (loss_and_grad) with
 respect to every trainable -- the inducing images through a reverse-mode pass of the conv kernel seeded with d loss / d K
 (inducing_grad=True).  SVSP.loss itself (a value for an autodiff framework to differentiate) still raises."""
@@ -13,10 +14,11 @@ from .._lib import DeviceArray, as_device
 from ..nt_kernels import CnnKernelFn, KernelFn
 from .base import ConstraintTrainVar, Module, TrainVar
 from .bijectors import positive
+from .likelihoods import _norm_logpdf, _t_logpdf
 from .priors import split_key
 from .utils import jitter
 
-__all__ = ["SPR", "SVSP", "grad_route", "lml_value_and_grads"]
+__all__ = ["SPR", "MultiSPR", "SVSP", "grad_route", "multi_grad_route", "lml_value_and_grads"]
 
 
 def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
@@ -201,6 +203,191 @@ class SPR(Module):
         )
         ll = np.mean(log_prob)
         return -ll
+
+
+def multi_grad_route(kernel_fn, likelihood):
+    """grad_route for MultiSPR: "smn_spr_loss_grad_multi" (MLP / dense ResNet) or "smn_spr_cnn_loss_grad_multi"
+    (get_cnn_kernel); anything else raises NotImplementedError, as grad_route does."""
+    return grad_route(kernel_fn, likelihood) + "_multi"
+
+
+class MultiSPR(Module):
+    """Exact GP / Student-t process with C outputs over ONE kernel matrix: y_data [N,C], K~ = K(x,x) + eps I.
+
+    Gaussian likelihood: the C columns are independent GPs that share K~ (the log-pdf is the sum of C
+    multivariate_normal.logpdf).  Student-t likelihood: sigma^2 ~ IG(a, b) is shared by all outputs, so the prior over
+    all N C outputs is ONE multivariate t, vec(Y) ~ MVT_{NC}(2a, 0, (b/a) (I_C x K~)) -- the model of a C-output network
+    whose last-layer variance carries one inverse-gamma scale, and not C one-vs-rest Student-t processes.  Everything that
+    is expensive -- the build of K~, its factorisation, -K~^-1 and the tangent pass over the pairs -- is done once for the
+    C columns (include/smnngp.h, the *_multi entries); 1 <= C <= 48.
+
+    Trainables and their names are SPR's (kernel.w_std, kernel.b_std, kernel.last_w_std, eps, likelihood.a / .b), so
+    train.train_vars, train.build_train_step and the checkpoint reader work on it unchanged.  Classification: targets
+    onehot(labels) - 1/C (from_labels), the predicted class is the arg-max of the posterior mean (classify, accuracy)."""
+
+    def __init__(self, kernel, likelihood, x_data, y_data, y_mean=0., y_std=1., *, eps: float = 1e-6):
+        super().__init__()
+        self.kernel = kernel
+        self.likelihood = likelihood
+        self.x_data = as_device(x_data)
+        self.num_data = self.x_data.shape[0]
+        y = np.asarray(y_data, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.num_data or y.shape[1] < 1:
+            raise ValueError("y_data must be [N,C] with N = %d rows, got %s" % (self.num_data, y.shape))
+        self.y_host = np.ascontiguousarray(y)
+        self.num_outputs = y.shape[1]
+        self.y_data = as_device(self.y_host, self.x_data.ctx, dtype=self.x_data.dtype)
+        self.y_mean = float(np.asarray(y_mean))
+        self.y_std = float(np.asarray(y_std))
+        self.eps = ConstraintTrainVar(eps, constraint=positive())
+
+    @classmethod
+    def from_labels(cls, kernel, likelihood, x_data, labels, num_classes, y_mean=0., y_std=1., *, eps: float = 1e-6):
+        """The classifier: targets onehot(labels) - 1/num_classes (every row sums to zero, its arg-max is the label)."""
+        return cls(kernel, likelihood, x_data, cls.label_targets(labels, num_classes), y_mean, y_std, eps=eps)
+
+    @staticmethod
+    def label_targets(labels, num_classes):
+        labels = np.asarray(labels).reshape(-1)
+        c = int(num_classes)
+        if labels.size and (labels.min() < 0 or labels.max() >= c or np.any(labels != np.floor(labels))):
+            raise ValueError("labels must be integers in [0, %d)" % c)
+        y = np.full((labels.shape[0], c), -1.0 / c)
+        y[np.arange(labels.shape[0]), labels.astype(np.int64)] += 1.0
+        return y
+
+    def _head(self):
+        if not hasattr(self.likelihood, "lml_params"):
+            raise NotImplementedError("MultiSPR needs a Gaussian or Student-t likelihood")
+        return self.likelihood.lml_params()
+
+    def _f64_data(self):
+        if self.x_data.dtype == np.float64:
+            return self.x_data, self.y_data
+        if getattr(self, "_x64", None) is None:
+            ctx = self.x_data.ctx
+            self._x64 = ctx.to_device(self.x_data.numpy().astype(np.float64))
+            self._y64 = ctx.to_device(self.y_host)
+        return self._x64, self._y64
+
+    def _joint_lml(self, kernel_fn, x, y, eps, df, scale):
+        """(log-pdf, total quadratic form, info) of y [N,C] under K(x,x) + eps I: the fused build for the MLP family, the
+        conv build followed by smn_lml_multi for the conv kernels."""
+        ctx, n, c = x.ctx, self.num_data, self.num_outputs
+        lp, quad, info = C.c_double(), C.c_double(), C.c_int()
+        if isinstance(kernel_fn, KernelFn):
+            net, act, L, w, b, lw = kernel_fn.params
+            ctx.call("smn_spr_loss_multi", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1], y.ptr, c,
+                     eps, df, scale, C.byref(lp), C.byref(quad), None, None, C.byref(info))
+        elif isinstance(kernel_fn, CnnKernelFn):
+            k = kernel_fn(x, None, get="nngp", fill="lower")
+            ctx.call("smn_lml_multi", x.dcode, k.ptr, n, n, y.ptr, c, eps, df, scale, C.byref(lp), C.byref(quad), None,
+                     None, C.byref(info))
+        else:
+            raise NotImplementedError("MultiSPR is wired for the nt_kernels factories; got %s" % type(kernel_fn).__name__)
+        return lp.value, quad.value, info.value
+
+    def loss(self):
+        """-log p(Y) / N; at C = 1 this is SPR.loss."""
+        df, scale = self._head()
+        lp, _, _ = self._joint_lml(self.kernel.get_kernel_fn(), self.x_data, self.y_data, self.eps.safe_value, df, scale)
+        return -lp / self.num_data
+
+    def loss_and_grad(self):
+        """(loss, {variable name: d loss / d RAW value}), the analytic counterpart of SPR.loss_and_grad for C columns: one
+        factorisation of [[K~], [I], [Y^T]] gives A = K~^-1 Y, -K~^-1, the C quadratic forms and logdet K~, one pass contracts
+        G = coef A A^T - C K~^-1 with the forward-mode dK/d(w_std, b_std, last_w_std) (csrc/grad.hip, csrc/cnn_grad.hip), and
+        lml_value_and_grads supplies the head in dimension N C with log-determinant C logdet K~.  The conv ResNet, a
+        likelihood without lml_params and images above 1024 pixels raise NotImplementedError."""
+        kernel_fn = self.kernel.get_kernel_fn()
+        mlp = multi_grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad_multi"
+        eps = self.eps.safe_value
+        df, scale = self.likelihood.lml_params()
+        x, ctx = self.x_data, self.x_data.ctx
+        n, c = self.num_data, self.num_outputs
+        quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
+        terms = (C.c_double * 4)()
+        if mlp:
+            net, act, L, w, b, lw = kernel_fn.params
+            ctx.call("smn_spr_loss_grad_multi", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1],
+                     self.y_data.ptr, c, eps, df, scale, C.byref(quad), None, C.byref(logdet), C.byref(info), terms)
+        else:
+            if len(x.shape) != 4:
+                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+            act, L, w, b, lw = kernel_fn.params
+            try:
+                ctx.call("smn_spr_cnn_loss_grad_multi", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2],
+                         x.shape[3], self.y_data.ptr, c, eps, df, scale, C.byref(quad), None, C.byref(logdet),
+                         C.byref(info), terms)
+            except _lib.SmnError as e:
+                if e.code == _lib.ENOTSUP and c <= 48:        # images above the tangent kernel's limit
+                    raise NotImplementedError(str(e)) from e
+                raise
+        nan = float("nan")
+        if info.value != 0:
+            return nan, {k: nan for k in self.vars()}
+        student = df > 0.0
+        lp, dlp = lml_value_and_grads(terms, quad.value, c * logdet.value, n * c, df, scale,
+                                      self.likelihood.a.safe_value if student else None,
+                                      self.likelihood.b.safe_value if student else None)
+        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
+                  "eps": self.eps}
+        if student:
+            owners.update(a=self.likelihood.a, b=self.likelihood.b)
+        names = {id(v): k for k, v in self.vars().items()}
+        grads = {}
+        for key, g in dlp.items():
+            var = owners[key]
+            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
+        return -lp / n, grads
+
+    def predict(self, x):
+        """(mean [T,C], cov [T,T]) of NNGPKernel.predict (relative ridge eps): one covariance shared by the outputs."""
+        return self.kernel.predict(self.kernel.get_kernel_fn(), self.x_data, self.y_data, x, eps=self.eps.safe_value)
+
+    def _student_quad_f64(self, kernel_fn, scale):
+        """tr(Y^T (scale K + 1e-6 I)^-1 Y) with K WITHOUT eps, always in fp64 (SPR._student_quad_f64 for C columns); the
+        value of the last parameter setting is kept."""
+        key = (type(kernel_fn).__name__, getattr(kernel_fn, "entry", None), tuple(kernel_fn.params), float(scale))
+        hit = getattr(self, "_quad64_cache", None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        xd, yd = self._f64_data()
+        _, quad, info = self._joint_lml(kernel_fn, xd, yd, 1e-6 / scale, 0.0, 1.0)
+        val = float("nan") if info else quad / scale
+        self._quad64_cache = (key, val)
+        return val
+
+    def test_nll(self, x, y):
+        """-mean_t sum_c log p(y_tc) under the predictive marginals in de-normalised units: N(mean_tc, sqrt(cov_tt)), or
+        Student-t with nu + N C degrees of freedom and sigma_t = sqrt(d / (nu + N C) (b/a) cov_tt),
+        d = nu + tr(Y^T ((b/a) K + 1e-6 I)^-1 Y) (spax/likelihoods.py:52-65 in dimension N C).  At C = 1: SPR.test_nll."""
+        df, scale = self._head()
+        mean, cov = self.predict(x)
+        t, c = mean.shape
+        y = np.asarray(y, dtype=np.float64).reshape(t, c)
+        ys = y * self.y_std + self.y_mean
+        ms = np.asarray(mean, dtype=np.float64).reshape(t, c) * self.y_std + self.y_mean
+        var = np.asarray(cov.diagonal(), dtype=np.float64) * self.y_std ** 2
+        if df > 0.0:
+            cond_df = df + self.num_data * c
+            d = df + self._student_quad_f64(self.kernel.get_kernel_fn(), scale)
+            sigma = np.sqrt(d / cond_df * scale * var)
+            lp = _t_logpdf(ys, cond_df, ms, sigma[:, None])
+        else:
+            lp = _norm_logpdf(ys, ms, np.sqrt(var)[:, None])
+        return -float(np.mean(np.sum(lp, axis=1)))
+
+    def classify(self, x):
+        """Predicted labels: argmax_c of the posterior mean (first maximum)."""
+        mean, _ = self.predict(x)
+        return np.argmax(np.asarray(mean, dtype=np.float64), axis=1)
+
+    def accuracy(self, x, labels):
+        """Fraction of x classified as `labels`."""
+        return float(np.mean(self.classify(x) == np.asarray(labels).reshape(-1)))
 
 
 class SVSP(Module):
