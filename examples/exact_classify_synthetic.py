@@ -2,10 +2,13 @@
 """Exact multi-class classification with MultiSPR (gp and tp) on the synthetic image problem of classify_synthetic.py:
 class templates plus noise, targets onehot(label) - 1/C, ALL C outputs carried through one factorisation of the conv-NNGP
 kernel matrix.  A few Adam steps on the hyper-parameters with the analytic gradient (smn_spr_cnn_loss_grad_multi), then
-the loss, the test NLL of the targets and the accuracy of argmax_c mean.
+the loss, the test NLL of the targets and the accuracy of argmax_c mean.  --objective loo trains on the leave-one-out
+predictive log-probability of the training set instead of the log-marginal likelihood (smn_spr_cnn_loo_grad) and prints the
+leave-one-out accuracy and NLL of the training points beside the test figures.
 
     python examples/exact_classify_synthetic.py [--train 400] [--test 400] [--classes 10] [--hw 8] [--channels 1]
                                                 [--layers 2] [--steps 5] [--lr 0.05] [--dtype float64|float32]
+                                                [--objective lml|loo]
 """
 import argparse
 import os
@@ -45,7 +48,9 @@ def main():
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--eps", type=float, default=1e-2)
+    ap.add_argument("--objective", default="lml", choices=["lml", "loo"])
     args = ap.parse_args()
+    loo = args.objective == "loo"
     dtype = np.dtype(args.dtype).type
     x, lab, xt, labt = problem(args.train, args.test, args.classes, args.hw, args.channels)
     x, xt = x.astype(dtype), xt.astype(dtype)
@@ -57,15 +62,19 @@ def main():
                                                                       last_w_std=l), 1.2, 0.1, 1.0)
         lik = GaussianLikelihood() if method == "gp" else StudentTLikelihood(2.0, 2.0)
         model = MultiSPR.from_labels(kernel, lik, x, lab, args.classes, eps=args.eps)
-        step = train.build_train_step(model, method="auto")
-        print("%s: start  loss %.6f  test NLL %.6f  accuracy %.2f %%"
-              % (method, model.loss(), model.test_nll(xt, yt), 100.0 * model.accuracy(xt, labt)))
+        step = train.build_train_step(model, method="auto", objective=args.objective)
+
+        def loo_report():
+            return "  LOO accuracy %.2f %%  LOO NLL %.6f" % (100.0 * model.loo_accuracy(lab), model.loo_loss()) if loo else ""
+
+        print("%s: start  loss %.6f  test NLL %.6f  accuracy %.2f %%%s"
+              % (method, model.loss(), model.test_nll(xt, yt), 100.0 * model.accuracy(xt, labt), loo_report()))
         t0 = time.perf_counter()
         for it in range(args.steps):
             print("%s: step %d  loss %.6f" % (method, it, step(args.lr)))
         dt = time.perf_counter() - t0
-        print("%s: end    loss %.6f  test NLL %.6f  accuracy %.2f %%   (%.1f ms per step)"
-              % (method, model.loss(), model.test_nll(xt, yt), 100.0 * model.accuracy(xt, labt),
+        print("%s: end    loss %.6f  test NLL %.6f  accuracy %.2f %%%s   (%.1f ms per step)"
+              % (method, model.loss(), model.test_nll(xt, yt), 100.0 * model.accuracy(xt, labt), loo_report(),
                  1e3 * dt / max(args.steps, 1)))
 
 

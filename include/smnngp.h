@@ -381,6 +381,54 @@ int smn_spr_cnn_loss_grad_multi(smn_ctx* ctx, int dtype, int act, int num_hidden
                                 double eps_abs, double df, double scale,
                                 double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]);
 
+/* ---- leave-one-out cross-validation of the exact models (Rasmussen & Williams 5.4.2; nothing in the reference to mirror: it
+ *      selects hyper-parameters on a held-out split, experiments/regression/train.py, find.py) ----
+ * Leaving out point i leaves out all c outputs of that point.  With P = K~^-1, A = P Y, p_i = P_ii, Q = sum_ic Y_ic A_ic and
+ * e_i = sum_c A_ic^2 / p_i the leave-one-out predictive of point i has mean Y_ic - A_ic / p_i and
+ *     Gaussian (df <= 0):  variance 1 / p_i,  log p_i = -(c/2) log 2 pi + (c/2) log p_i - e_i / 2
+ *     Student-t (df > 0):  a c-variate t with df + (n-1) c degrees of freedom and shape sigma_i^2 I,
+ *                          sigma_i^2 = (df + (Q - e_i) / scale) / (df + (n-1) c) * scale / p_i  (the matrix-t prior of MultiSPR)
+ * Lambda = sum_i log p_i; G is its seed: d Lambda = sum_ij G_ij dK~_ij over all i, j (csrc/loo.hip has the closed form), so
+ * smn_lml_grad_terms / smn_kernel_cnn_grad_terms with neg_kinv_d = G, alpha_d = zeros and coef = 0 return d Lambda / d(w_std,
+ * b_std, last_w_std, eps).  1 <= c <= 48 (SMN_ENOTSUP above), fp32 and fp64.  Per-point arithmetic and every sum over points
+ * are fp64 in a fixed order: two calls give the same bits.
+ * smn_loo_head: the head alone.  neg_kinv_d [n,n] = -K~^-1 (ld = ldkinv; only the LOWER triangle is read, which is what both
+ *   routes of the gradient entries leave), alpha_d [n,c] = A and y_d [n,c] row-major.  Out: *loo_logpdf_h = Lambda, loo_mean_d
+ *   [n,c], loo_scale2_d [n] (1 / p_i, or sigma_i^2), dhead_h[2] = d Lambda / d(df, scale) (zeros for df <= 0), and, when g_d is
+ *   not NULL, the lower triangle of G in g_d [n,n] (ld = ldg; may be neg_kinv_d itself; the 64 x 64 blocks on the diagonal are
+ *   written whole, nothing else above the diagonal is touched).  loo_mean_d and loo_scale2_d may be NULL.  The seed costs one n^3-flop product -(-K~^-1) diag(d) (-K~^-1) over the lower 128 x 128 tiles on the MFMA tile engine
+ *   and a workspace of 2 n_pad^2 elements (n_pad = n rounded up to 128): the mirrored, zero-padded operand and its column-
+ *   scaled copy.  Synchronises.
+ * smn_loo_multi: the counterpart of smn_lml_multi: k_d [n,n] lower (may be overwritten), factorisation with identity, the
+ *   head; also *logdet_h and *info_h.  With a kernel build in front this serves every kernel, the conv ResNet included.
+ * smn_spr_loo_grad / smn_spr_cnn_loo_grad: everything from x and Y [n,c], the counterparts of smn_spr_loss_grad_multi /
+ *   smn_spr_cnn_loss_grad_multi (the conv entry keeps H*W <= SMN_CNN_GRAD_MAX_PIXELS): terms_h[0..3] = d Lambda / d(w_std,
+ *   b_std, last_w_std, eps), *loo_logpdf_h, dhead_h[2], *info_h and, when not NULL, loo_mean_d / loo_scale2_d.
+ * A matrix that is not positive definite gives info > 0, NaN outputs and SMN_OK. */
+int smn_loo_head(smn_ctx* ctx, int dtype, const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, const void* y_d,
+                 int64_t n, int64_t c, double df, double scale, double* loo_logpdf_h, void* loo_mean_d, void* loo_scale2_d,
+                 double dhead_h[2], void* g_d, int64_t ldg);
+int smn_loo_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c, double eps_abs,
+                  double df, double scale, double* loo_logpdf_h, void* loo_mean_d, void* loo_scale2_d, double dhead_h[2],
+                  double* logdet_h, int* info_h, void* g_d, int64_t ldg);
+int smn_spr_loo_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                     double w_std, double b_std, double last_w_std,
+                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                     double eps_abs, double df, double scale, double* loo_logpdf_h, double dhead_h[2], int* info_h,
+                     double terms_h[4], void* loo_mean_d, void* loo_scale2_d);
+/* smn_spr_kinv: -K~^-1 (neg_kinv_d [n,n], ld = ldkinv a multiple of 16 bytes; the lower triangle is valid) and A = K~^-1 Y
+ * (alpha_d [n,c]) exactly as the gradient entries form them from x and Y -- the joint factorisation below n_pad = 8192, the
+ * rectangle route from there on -- i.e. what smn_spr_loo_grad hands to the head; also logdet K~ and info. */
+int smn_spr_kinv(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                 double w_std, double b_std, double last_w_std,
+                 const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs,
+                 void* neg_kinv_d, int64_t ldkinv, void* alpha_d, double* logdet_h, int* info_h);
+int smn_spr_cnn_loo_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                         double w_std, double b_std, double last_w_std,
+                         const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c,
+                         double eps_abs, double df, double scale, double* loo_logpdf_h, double dhead_h[2], int* info_h,
+                         double terms_h[4], void* loo_mean_d, void* loo_scale2_d);
+
 /* ---- sparse variational classifier, evaluation (spax/models.py:58-78 SVSP.test_acc_nll; experiments/classification/test.py) ----
  * With inducing images Z [I], q_mu [C,I], q_var [C,I] = diag(q_sqrt) as the reference uses it (NOT squared) and K the NNGP kernel:
  *     K_rel = K_ZZ + eps tr(K_ZZ)/I I   (NNGPKernel.predict: relative ridge)      K_abs = K_ZZ + eps I   (models.py:68)

@@ -102,6 +102,13 @@ PROTOTYPES = {
     "smn_spr_loss_grad_multi": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pi, _pd],
     "smn_spr_cnn_loss_grad_multi": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd,
                                     _pi, _pd],
+    "smn_loo_head": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i64, _d, _d, _pd, _vp, _vp, _pd, _vp, _i64],
+    "smn_loo_multi": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _vp, _vp, _pd, _pd, _pi, _vp, _i64],
+    "smn_spr_loo_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pi, _pd,
+                         _vp, _vp],
+    "smn_spr_cnn_loo_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pi, _pd,
+                             _vp, _vp],
+    "smn_spr_kinv": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _vp, _i64, _vp, _pd, _pi],
     "smn_kernel_conv_diag": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp],
     "smn_svsp_moments": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _d, _vp, _vp, _pi, _pi64],
     "smn_mc_softmax": [_vp, _i, _vp, _vp, _pi, _i64, _i64, _i64, _d, C.c_uint64, _i64, _vp, _vp, _vp, _vp],

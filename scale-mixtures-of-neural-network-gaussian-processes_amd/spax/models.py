@@ -61,7 +61,103 @@ def grad_route(kernel_fn, likelihood):
                               "a Gaussian or Student-t likelihood; use train.value_and_grad_fd")
 
 
-class SPR(Module):
+class _LooMixin:
+    """Leave-one-out cross-validation (Rasmussen & Williams 5.4.2) for the exact models: how would the model have predicted
+    training point i had it not seen it?  Closed forms on K~^-1 and A = K~^-1 Y, which every gradient call already leaves on
+    the device (csrc/loo.hip); leaving out a point leaves out all its C outputs.  Gaussian likelihood: N(mu_i, 1/p_i I_C);
+    Student-t likelihood: a C-variate t with nu + (N-1) C degrees of freedom.  SPR is the C = 1 case of the same entries."""
+
+    def _loo_shape(self):
+        return self.num_data, getattr(self, "num_outputs", 1)
+
+    def _loo_head_params(self):
+        if not hasattr(self.likelihood, "lml_params"):
+            raise NotImplementedError("leave-one-out needs a Gaussian or Student-t likelihood")
+        return self.likelihood.lml_params()
+
+    def _loo_value(self, want_pred):
+        """(Lambda, mean, scale2, info) through smn_loo_multi: any kernel factory, no gradient."""
+        df, scale = self._loo_head_params()
+        kernel_fn = self.kernel.get_kernel_fn()
+        if not isinstance(kernel_fn, (KernelFn, CnnKernelFn)):
+            raise NotImplementedError("leave-one-out is wired for the nt_kernels factories; got %s" % type(kernel_fn).__name__)
+        x, ctx = self.x_data, self.x_data.ctx
+        n, c = self._loo_shape()
+        k = kernel_fn(x, None, get="nngp", fill="lower")
+        mean = ctx.empty((n, c), x.dtype) if want_pred else None
+        scale2 = ctx.empty((n,), x.dtype) if want_pred else None
+        lam, info = C.c_double(), C.c_int()
+        ctx.call("smn_loo_multi", x.dcode, k.ptr, n, n, self.y_data.ptr, c, self.eps.safe_value, df, scale, C.byref(lam),
+                 mean.ptr if want_pred else None, scale2.ptr if want_pred else None, None, None, C.byref(info), None, 0)
+        return lam.value, mean, scale2, info.value
+
+    def loo_loss(self):
+        """-Lambda / N with Lambda = sum_i log p(Y_i | Y_-i): the leave-one-out predictive log-probability of the training
+        set, same divisor as loss().  Works for every kernel factory."""
+        lam, _, _, info = self._loo_value(False)
+        return float("nan") if info else -lam / self.num_data
+
+    def loo_predict(self):
+        """(mean, scale2 [N], df') of the leave-one-out predictive of every training point in normalised units: mean [N]
+        (SPR) or [N,C] (MultiSPR); Gaussian: variance scale2 and df' = None; Student-t: shape scale2 (shared by the C outputs)
+        and df' = 2a + (N-1) C degrees of freedom."""
+        df, _ = self._loo_head_params()
+        _, mean, scale2, _ = self._loo_value(True)
+        n, c = self._loo_shape()
+        m = np.asarray(mean.raw_numpy(), dtype=np.float64)
+        if not hasattr(self, "num_outputs"):
+            m = m.reshape(-1)
+        return m, np.asarray(scale2.raw_numpy(), dtype=np.float64), (df + (n - 1) * c if df > 0.0 else None)
+
+    def loo_loss_and_grad(self):
+        """(loo_loss, {variable name: d loo_loss / d RAW value}) with the names, the softplus chain rule and the NaN-on-non-PD
+        convention of loss_and_grad.  One factorisation with identity, the leave-one-out head with its seed G
+        (d Lambda = sum_ij G_ij dK~_ij; one N^3 product on the MFMA tile engine) and the tangent pass of loss_and_grad over G
+        (smn_spr_loo_grad / smn_spr_cnn_loo_grad).  Follows grad_route: the conv ResNet, a likelihood without lml_params and
+        images above 1024 pixels raise NotImplementedError."""
+        kernel_fn = self.kernel.get_kernel_fn()
+        mlp = grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad"
+        eps = self.eps.safe_value
+        df, scale = self.likelihood.lml_params()
+        x, ctx = self.x_data, self.x_data.ctx
+        n, c = self._loo_shape()
+        lam, info = C.c_double(), C.c_int()
+        terms, dhead = (C.c_double * 4)(), (C.c_double * 2)()
+        if mlp:
+            net, act, L, w, b, lw = kernel_fn.params
+            ctx.call("smn_spr_loo_grad", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1], self.y_data.ptr, c,
+                     eps, df, scale, C.byref(lam), dhead, C.byref(info), terms, None, None)
+        else:
+            if len(x.shape) != 4:
+                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+            act, L, w, b, lw = kernel_fn.params
+            try:
+                ctx.call("smn_spr_cnn_loo_grad", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2], x.shape[3],
+                         self.y_data.ptr, c, eps, df, scale, C.byref(lam), dhead, C.byref(info), terms, None, None)
+            except _lib.SmnError as e:
+                if e.code == _lib.ENOTSUP and c <= 48:        # images above the tangent kernel's limit
+                    raise NotImplementedError(str(e)) from e
+                raise
+        nan = float("nan")
+        if info.value != 0:
+            return nan, {k: nan for k in self.vars()}
+        dlam = dict(zip(("w_std", "b_std", "last_w_std", "eps"), terms))   # d Lambda / d constrained value
+        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
+                  "eps": self.eps}
+        if df > 0.0:
+            a_, b_ = self.likelihood.a.safe_value, self.likelihood.b.safe_value
+            dlam["a"] = 2.0 * dhead[0] - dhead[1] * b_ / (a_ * a_)      # df = 2a, scale = b/a
+            dlam["b"] = dhead[1] / a_
+            owners.update(a=self.likelihood.a, b=self.likelihood.b)
+        names = {id(v): k for k, v in self.vars().items()}
+        grads = {}
+        for key, g in dlam.items():
+            var = owners[key]
+            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
+        return -lam.value / n, grads
+
+
+class SPR(_LooMixin, Module):
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, eps: float = 1e-6):
         super().__init__()
         self.kernel = kernel
@@ -211,7 +307,7 @@ def multi_grad_route(kernel_fn, likelihood):
     return grad_route(kernel_fn, likelihood) + "_multi"
 
 
-class MultiSPR(Module):
+class MultiSPR(_LooMixin, Module):
     """Exact GP / Student-t process with C outputs over ONE kernel matrix: y_data [N,C], K~ = K(x,x) + eps I.
 
     Gaussian likelihood: the C columns are independent GPs that share K~ (the log-pdf is the sum of C
@@ -388,6 +484,15 @@ class MultiSPR(Module):
     def accuracy(self, x, labels):
         """Fraction of x classified as `labels`."""
         return float(np.mean(self.classify(x) == np.asarray(labels).reshape(-1)))
+
+    def loo_classify(self):
+        """Leave-one-out labels of the training points: argmax_c of the leave-one-out mean (first maximum)."""
+        return np.argmax(self.loo_predict()[0], axis=1)
+
+    def loo_accuracy(self, labels=None):
+        """Fraction of the training points whose leave-one-out label is `labels` (default: the arg-max of y_host)."""
+        labels = np.argmax(self.y_host, axis=1) if labels is None else np.asarray(labels).reshape(-1)
+        return float(np.mean(self.loo_classify() == labels))
 
 
 class SVSP(Module):

@@ -72,27 +72,36 @@ class Adam:
             self.vars[k].assign(float(self.vars[k].value) - lr_t * self.m[k] / (math.sqrt(self.v[k]) + self.eps))
 
 
-def build_train_step(model, variables=None, optimizer=None, h=1e-4, method="auto"):
+def build_train_step(model, variables=None, optimizer=None, h=1e-4, method="auto", objective="lml"):
     """train_step(learning_rate) -> loss before the update  (regression/train.py:61-67).
     method: "analytic" (SPR.loss_and_grad), "fd" (central differences) or "auto" (analytic when the model's
     kernel / likelihood support it -- MLP, dense-ResNet and get_cnn_kernel kernels with images of up to 1024 pixels --
-    else finite differences: the conv ResNet, larger images)."""
+    else finite differences: the conv ResNet, larger images).
+    objective: "lml" (the negative log-marginal likelihood: model.loss / model.loss_and_grad) or "loo" (the negative
+    leave-one-out predictive log-probability: model.loo_loss / model.loo_loss_and_grad)."""
     if method not in ("auto", "analytic", "fd"):
         raise ValueError("method must be 'auto', 'analytic' or 'fd'")
+    if objective not in ("lml", "loo"):
+        raise ValueError("objective must be 'lml' or 'loo'")
+    loo = objective == "loo"
     variables = variables if variables is not None else train_vars(model)
     optimizer = optimizer or Adam(variables)
-    state = {"analytic": method != "fd" and hasattr(model, "loss_and_grad")}
+    state = {"analytic": method != "fd" and hasattr(model, "loo_loss_and_grad" if loo else "loss_and_grad")}
 
     def train_step(learning_rate):
         if state["analytic"]:
             try:
-                value, grads = value_and_grad(model, variables)
+                if loo:
+                    value, grads = model.loo_loss_and_grad()
+                    grads = {k: g for k, g in grads.items() if k in variables}
+                else:
+                    value, grads = value_and_grad(model, variables)
             except NotImplementedError:
                 if method == "analytic":
                     raise
                 state["analytic"] = False
         if not state["analytic"]:
-            value, grads = value_and_grad_fd(model.loss, variables, h=h)
+            value, grads = value_and_grad_fd(model.loo_loss if loo else model.loss, variables, h=h)
         optimizer(learning_rate, grads)
         return value
 
