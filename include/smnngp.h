@@ -10,7 +10,17 @@
  * Conventions
  *   - every function returns int status: SMN_OK (0) or a negative SMN_E* code; the message is
  *     kept per context and read with smn_last_error().  Nothing throws across the ABI.
- *   - matrices are dense row-major with an explicit leading dimension (elements, not bytes).
+ *   - matrices are dense row-major with an explicit leading dimension (elements, not bytes).  A matrix may be a
+ *     window into a larger allocation: an entry reads and writes only the rows x cols elements it is given, never the
+ *     ld - cols elements between two rows nor anything before the first or after the last row.  Every leading
+ *     dimension must be at least the number of elements of a row it strides (ldx >= d, ldk >= the columns of the
+ *     kernel block, ldk >= n + t for the joint kernel of smn_predict, ldcov >= t, ldb >= nrhs, ...): a smaller one
+ *     would make rows alias each other and is refused with SMN_EINVAL and a message that names the argument, before
+ *     anything is allocated or launched.  No alignment is required of pointers or leading dimensions except where
+ *     an entry says so: smn_recursion (k0_d and both outputs 16-byte aligned, ldk0 and ldk multiples of 16 bytes:
+ *     SMN_EINVAL otherwise), smn_spr_kinv (ldkinv a multiple of 16 bytes), and smn_cholesky, which factors in place
+ *     when n_total and n_factor are multiples of 128, a_d is 16-byte aligned and lda a multiple of 16 bytes, and
+ *     through a padded copy otherwise (same contract, another schedule: not the same bits).
  *   - "d" pointers are DEVICE pointers obtained from smn_malloc(); "h" pointers are host memory
  *     borrowed for the duration of the call.  dtype: SMN_F32 / SMN_F64.
  *   - calls are stream-ordered on the context's stream; functions that return host scalars
@@ -120,7 +130,8 @@ int smn_kernel_mlp_shard(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
 /* The two halves of the build, exposed separately for sweeps that reuse K0 across (w_std,b_std)
  * (experiments/regression/find.py:134-138) and for roofline measurement of the recursion alone.
  * smn_gram: k0_d = x1 x2^T / d (+ q1_d [n1], q2_d [n2] diagonals ||x||^2/d).
- * smn_recursion: applies the layer stack elementwise to k0 (HBM-streaming kernel). */
+ * smn_recursion: applies the layer stack elementwise to k0 (HBM-streaming kernel, 16-byte vector accesses: k0_d, nngp_d and
+ *   ntk_d must be 16-byte aligned and ldk0, ldk multiples of 16 bytes; SMN_EINVAL otherwise). */
 int smn_gram(smn_ctx* ctx, int dtype, const void* x1_d, int64_t n1, int64_t ldx1,
              const void* x2_d, int64_t n2, int64_t ldx2, int64_t d,
              void* k0_d, int64_t ldk, void* q1_d, void* q2_d);

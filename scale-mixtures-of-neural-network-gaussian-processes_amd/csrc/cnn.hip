@@ -489,6 +489,8 @@ extern "C" int smn_kernel_cnn(smn_ctx* ctx, int dtype, int act, int num_hiddens,
   SMN_ENTER(ctx);
   SMN_TRY(conv_check(ctx, "smn_kernel_cnn", dtype, act, num_hiddens, n1, H, W, C, 64 * kMaxPix));
   if (x2_d && n2 <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn: bad sizes");
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_cnn", ldk, n2);
+  else SMN_CHECK_LD(ctx, "smn_kernel_cnn", ldk, n1);
   if (dtype == SMN_F64)
     return cnn_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
   return cnn_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);

@@ -333,7 +333,7 @@ extern "C" int smn_kernel_cnn_grad_terms(smn_ctx* ctx, int dtype, int act, int n
   if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  if (ldkinv < n) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_kernel_cnn_grad_terms", ldkinv, n);
   if (dtype == SMN_F64)
     return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
                                  coef, terms_h);
@@ -385,7 +385,8 @@ extern "C" int smn_kernel_cnn_grad_terms_multi(smn_ctx* ctx, int dtype, int act,
   if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms_multi", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  if (ldkinv < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms_multi: bad sizes");
+  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms_multi: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_kernel_cnn_grad_terms_multi", ldkinv, n);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms_multi: more than 48 output columns");
   if (dtype == SMN_F64)
     return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,

@@ -295,7 +295,7 @@ extern "C" int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int n
   SMN_ENTER(ctx);
   const char* who = "smn_kernel_cnn_input_grad";
   SMN_TRY(conv_check(ctx, who, dtype, act, num_hiddens, n, H, W, C, kCigMaxHW));
-  if (ldg < n) return smn_fail(ctx, SMN_EINVAL, "%s: ldg = %lld < n = %lld", who, (long long)ldg, (long long)n);
+  SMN_CHECK_LD(ctx, who, ldg, n);
   if (n_grad < 1 || n_grad > n)
     return smn_fail(ctx, SMN_EINVAL, "%s: n_grad = %lld outside [1, n = %lld]", who, (long long)n_grad, (long long)n);
   if (dtype == SMN_F64)

@@ -370,6 +370,8 @@ extern "C" int smn_kernel_conv_resnet(smn_ctx* ctx, int dtype, int act, int bloc
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (n1 <= 0 || (x2_d && n2 <= 0) || H <= 0 || W <= 0 || C <= 0 || block_size <= 0)
     return smn_fail(ctx, SMN_EINVAL, "smn_kernel_conv_resnet: bad sizes");
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_conv_resnet", ldk, n2);
+  else SMN_CHECK_LD(ctx, "smn_kernel_conv_resnet", ldk, n1);
   if (dtype == SMN_F64)
     return resnet_t<double>(ctx, act, block_size, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
   return resnet_t<float>(ctx, act, block_size, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);

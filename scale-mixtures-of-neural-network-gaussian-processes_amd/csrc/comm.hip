@@ -180,10 +180,10 @@ extern "C" int smn_unpack_lower_blocks(smn_ctx* ctx, int dtype, const void* stag
   if (!ctx || !stage_d || !k_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || nranks <= 0 || block_rows <= 0 || block_rows % kTile || ldk < n ||
-      2 * (int64_t)nranks * block_rows < n)
+  if (n <= 0 || nranks <= 0 || block_rows <= 0 || block_rows % kTile || 2 * (int64_t)nranks * block_rows < n)
     return smn_fail(ctx, SMN_EINVAL, "smn_unpack_lower_blocks: bad geometry (n=%lld ranks=%d block_rows=%lld ldk=%lld)",
                     (long long)n, nranks, (long long)block_rows, (long long)ldk);
+  SMN_CHECK_LD(ctx, "smn_unpack_lower_blocks", ldk, n);
   const int64_t chunk = block_rows * block_rows * (2 * (int64_t)nranks + 1);
   const size_t es = dtype_size(dtype);
   const int vec = (int)(16 / es);

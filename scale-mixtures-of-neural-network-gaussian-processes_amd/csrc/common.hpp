@@ -140,6 +140,15 @@ inline int smn_fail(smn_ctx* ctx, int code, const char* fmt, ...) {
 
 #define SMN_CHECK_LAUNCH(ctx) SMN_HIP(ctx, hipGetLastError())
 
+// A leading dimension below the extent it strides makes rows alias each other: refused by name (include/smnngp.h,
+// Conventions), before the entry allocates or launches anything.
+#define SMN_CHECK_LD(ctx, who, ld, extent)                                                                     \
+  do {                                                                                                         \
+    if ((ld) < (extent))                                                                                       \
+      return smn_fail((ctx), SMN_EINVAL, "%s: " #ld " = %lld is smaller than the %lld elements of a row (" #extent ")", \
+                      (who), (long long)(ld), (long long)(extent));                                            \
+  } while (0)
+
 // The current HIP device is a property of the calling host THREAD (default 0), not of the context: allocations,
 // function attributes, events and plain launches all go to it.  Every C-ABI entry that takes a context therefore opens
 // with SMN_ENTER(ctx): it makes ctx->device current for the duration of the call and puts the caller's device back on

@@ -623,7 +623,9 @@ extern "C" int smn_lml_grad_terms(smn_ctx* ctx, int dtype, int net, int act, int
   if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || ldk0 < n || ldkinv < n) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms: bad sizes");
+  if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_lml_grad_terms", ldk0, n);
+  SMN_CHECK_LD(ctx, "smn_lml_grad_terms", ldkinv, n);
   if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms: bad hyper-parameters");
@@ -642,7 +644,9 @@ extern "C" int smn_lml_grad_terms_multi(smn_ctx* ctx, int dtype, int net, int ac
   if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || ldk0 < n || ldkinv < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad sizes");
+  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_lml_grad_terms_multi", ldk0, n);
+  SMN_CHECK_LD(ctx, "smn_lml_grad_terms_multi", ldkinv, n);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_grad_terms_multi: more than 48 output columns");
   if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
@@ -666,6 +670,7 @@ extern "C" int smn_spr_loss_grad_multi(smn_ctx* ctx, int dtype, int net, int act
   if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: empty");
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_grad_multi: more than 48 output columns");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: scale must be > 0");
+  SMN_CHECK_LD(ctx, "smn_spr_loss_grad_multi", ldx, d);
   const size_t es = dtype_size(dtype);
   const int64_t al = 16 / (int64_t)es;
   const int64_t ld0 = round_up(n, al);
@@ -708,6 +713,7 @@ extern "C" int smn_spr_loss_grad(smn_ctx* ctx, int dtype, int net, int act, int 
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad: empty");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad: scale must be > 0");
+  SMN_CHECK_LD(ctx, "smn_spr_loss_grad", ldx, d);
   const size_t es = dtype_size(dtype);
   const int64_t al = 16 / (int64_t)es;
   const int64_t ld0 = round_up(n, al);
@@ -749,6 +755,7 @@ extern "C" int smn_spr_loss_grad_batch(smn_ctx* ctx, int dtype, int net, int act
   if (nprob <= 0 || !w_std || !b_std || !last_w_std || !eps_abs)
     return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty batch or null parameter array");
   if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty");
+  SMN_CHECK_LD(ctx, "smn_spr_loss_grad_batch", ldx, d);
   if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "num_hiddens < 0");

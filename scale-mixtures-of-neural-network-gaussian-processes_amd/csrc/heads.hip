@@ -160,8 +160,9 @@ extern "C" int smn_cholesky(smn_ctx* ctx, int dtype, void* a_d, int64_t n_total,
   if (!ctx || !a_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n_factor <= 0 || n_factor > n_total || lda < n_total || n_shift < 0 || n_shift > n_factor)
+  if (n_factor <= 0 || n_factor > n_total || n_shift < 0 || n_shift > n_factor)
     return smn_fail(ctx, SMN_EINVAL, "smn_cholesky: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_cholesky", lda, n_total);
   const size_t es = dtype_size(dtype);
   const bool inplace = n_total % kTile == 0 && n_factor % kTile == 0 && lda % (16 / (int64_t)es) == 0 &&
                        (reinterpret_cast<uintptr_t>(a_d) & 15) == 0;
@@ -200,6 +201,8 @@ extern "C" int smn_trsm(smn_ctx* ctx, int dtype, const void* l_d, int64_t n, int
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || nrhs <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_trsm: empty");
   if (trans != 0 && trans != 1) return smn_fail(ctx, SMN_EINVAL, "smn_trsm: trans must be 0 or 1");
+  SMN_CHECK_LD(ctx, "smn_trsm", ldl, n);
+  SMN_CHECK_LD(ctx, "smn_trsm", ldb, nrhs);
   // X = L^-1 B  <=>  X^T = B^T L^-T: the columns of B ride through the panel sweep as appended rows.
   // trans = 1: L^T X = B  <=>  L' (J X) = J B with L' = J L^T J lower triangular (J reverses the order),
   // so the same forward sweep serves the backward substitution.
@@ -227,7 +230,9 @@ extern "C" int smn_transpose(smn_ctx* ctx, int dtype, void* dst_d, int64_t ldd, 
   if (!ctx || !dst_d || !src_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (rows < 0 || cols < 0 || lds < cols || ldd < rows) return smn_fail(ctx, SMN_EINVAL, "smn_transpose: bad sizes");
+  if (rows < 0 || cols < 0) return smn_fail(ctx, SMN_EINVAL, "smn_transpose: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_transpose", lds, cols);
+  SMN_CHECK_LD(ctx, "smn_transpose", ldd, rows);
   return transpose_matrix(ctx, dtype, dst_d, ldd, src_d, lds, rows, cols);
 }
 
@@ -237,6 +242,7 @@ extern "C" int smn_lml(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ld
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_lml: empty");
+  SMN_CHECK_LD(ctx, "smn_lml", ldk, n);
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml: scale must be > 0");
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
@@ -277,7 +283,8 @@ extern "C" int smn_lml_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int6
   if (!ctx || !k_d || !y_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || ldk < n || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: bad sizes");
+  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_lml_multi", ldk, n);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_multi: more than 48 output columns");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: scale must be > 0");
   Aug g;
@@ -435,7 +442,8 @@ extern "C" int smn_shard_exchange_cols_to(smn_ctx* ctx, int dtype, const void* m
                                           int npieces, const int64_t* piece_cols, int piece, void* k_d, int64_t ldk) {
   if (!ctx || !mine_d || !stage_d || !k_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
-  if (n <= 0 || ldk < n) return smn_fail(ctx, SMN_EINVAL, "smn_shard_exchange_cols_to: bad sizes");
+  if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_shard_exchange_cols_to: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_shard_exchange_cols_to", ldk, n);
   return exchange_piece(ctx, "smn_shard_exchange_cols_to", dtype, mine_d, stage_d, n, nranks, npieces, piece_cols, piece, k_d, ldk);
 }
 
@@ -450,8 +458,8 @@ extern "C" int smn_shard_scatter_cols(smn_ctx* ctx, int dtype, const void* stage
     if (!ctx->shard_a || ctx->shard_n != n || ctx->shard_dtype != dtype)
       return smn_fail(ctx, SMN_EINVAL, "smn_shard_scatter_cols: smn_shard_begin(dtype, n, eps) first");
     if (ctx->ws[2] != ctx->shard_a) return smn_fail(ctx, SMN_EINVAL, "smn_shard_scatter_cols: the workspace moved since smn_shard_begin");
-  } else if (ldk < n) {
-    return smn_fail(ctx, SMN_EINVAL, "smn_shard_scatter_cols: ldk < n");
+  } else {
+    SMN_CHECK_LD(ctx, "smn_shard_scatter_cols", ldk, n);
   }
   ColPieces cp;
   SMN_TRY(col_pieces_make(ctx, n, nranks, npieces, piece_cols, &cp));
@@ -621,6 +629,8 @@ int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || t < 0 || c <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_predict: bad sizes");
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");
+  SMN_CHECK_LD(ctx, "smn_predict", ldk, n + t);
+  if (cov_d) SMN_CHECK_LD(ctx, "smn_predict", ldcov, t);
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
   const char* kb = static_cast<const char*>(kj_d);
@@ -650,6 +660,7 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss: empty");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss: scale must be > 0");
+  SMN_CHECK_LD(ctx, "smn_spr_loss", ldx, d);
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
@@ -680,6 +691,7 @@ extern "C" int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int
   if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_multi: empty");
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_multi: more than 48 output columns");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_multi: scale must be > 0");
+  SMN_CHECK_LD(ctx, "smn_spr_loss_multi", ldx, d);
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
@@ -774,7 +786,9 @@ int spr_batch(smn_ctx* ctx, const char* who, int dtype, int net, int act, int nu
   if (nprob <= 0 || !w_std || !b_std || !last_w_std || !shift_abs) return smn_fail(ctx, SMN_EINVAL, "%s: empty batch or null parameter array", who);
   if (n <= 0 || d <= 0 || t < 0 || c <= 0) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");
-  if (cov_d && ldcov < t) return smn_fail(ctx, SMN_EINVAL, "%s: ldcov < t", who);
+  SMN_CHECK_LD(ctx, who, ldx, d);
+  if (t > 0) SMN_CHECK_LD(ctx, who, ldxt, d);
+  if (cov_d) SMN_CHECK_LD(ctx, who, ldcov, t);
   const size_t es = dtype_size(dtype);
   Aug g;
   g.n = n; g.t = t; g.c = c;
@@ -937,6 +951,9 @@ extern "C" int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int nu
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || d <= 0 || t < 0 || c <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_predict: bad sizes");
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");
+  SMN_CHECK_LD(ctx, "smn_spr_predict", ldx, d);
+  if (t > 0) SMN_CHECK_LD(ctx, "smn_spr_predict", ldxt, d);
+  if (cov_d) SMN_CHECK_LD(ctx, "smn_spr_predict", ldcov, t);
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};

@@ -1320,6 +1320,10 @@ extern "C" int smn_kernel_mlp(smn_ctx* ctx, int dtype, int net, int act, int num
   if (!(get_mask & (SMN_GET_NNGP | SMN_GET_NTK))) return smn_fail(ctx, SMN_EINVAL, "empty get mask");
   if (((get_mask & SMN_GET_NNGP) && !nngp_d) || ((get_mask & SMN_GET_NTK) && !ntk_d))
     return smn_fail(ctx, SMN_EINVAL, "requested output pointer is NULL");
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp", ldx1, d);
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_mlp", ldx2, d);
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_mlp", ldk, n2);
+  else SMN_CHECK_LD(ctx, "smn_kernel_mlp", ldk, n1);
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   return build_public(ctx, s, x1_d, n1, ldx1, x2_d, n2, ldx2, d, get_mask, fill, 0, 0, nngp_d, ntk_d, ldk, nullptr, nullptr);
 }
@@ -1332,6 +1336,8 @@ extern "C" int smn_kernel_mlp_rows(smn_ctx* ctx, int dtype, int net, int act, in
   SMN_ENTER(ctx);
   if (row_begin < 0 || row_end > n || row_end <= row_begin)
     return smn_fail(ctx, SMN_EINVAL, "bad row range [%lld,%lld)", (long long)row_begin, (long long)row_end);
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_rows", ldx, d);
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_rows", ldk, n);
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   return build_public(ctx, s, x_d, n, ldx, nullptr, 0, 0, d, get_mask, SMN_FILL_FULL, row_begin, row_end,
                       nngp_rows_d, ntk_rows_d, ldk, nullptr, nullptr);
@@ -1345,7 +1351,8 @@ extern "C" int smn_kernel_mlp_lower_rows(smn_ctx* ctx, int dtype, int net, int a
   SMN_ENTER(ctx);
   if (row_begin < 0 || row_end > n || row_end <= row_begin)
     return smn_fail(ctx, SMN_EINVAL, "bad row range [%lld,%lld)", (long long)row_begin, (long long)row_end);
-  if (ldk < row_end) return smn_fail(ctx, SMN_EINVAL, "ldk %lld < row_end %lld", (long long)ldk, (long long)row_end);
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_lower_rows", ldx, d);
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_lower_rows", ldk, row_end);
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   return build_public(ctx, s, x_d, n, ldx, nullptr, 0, 0, d, get_mask, SMN_FILL_FULL, row_begin, row_end,
                       nngp_rows_d, ntk_rows_d, ldk, nullptr, nullptr, true);
@@ -1365,6 +1372,7 @@ extern "C" int smn_kernel_mlp_shard(smn_ctx* ctx, int dtype, int net, int act, i
                     (long long)n, nranks, rank, (long long)block_rows);
   if (!x_d || ((get_mask & SMN_GET_NNGP) && !nngp_chunk_d) || ((get_mask & SMN_GET_NTK) && !ntk_chunk_d))
     return smn_fail(ctx, SMN_EINVAL, "smn_kernel_mlp_shard: null pointer");
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_shard", ldx, d);
   const size_t es = dtype_size(dtype);
   const int64_t kp = k_pad(dtype, d), r1 = round_up(n, kTile), h = block_rows;
   void* xs = nullptr;
@@ -1426,6 +1434,7 @@ extern "C" int smn_kernel_mlp_shard_cols(smn_ctx* ctx, int dtype, int net, int a
   if (!x_d || !(get_mask & (SMN_GET_NNGP | SMN_GET_NTK)) || ((get_mask & SMN_GET_NNGP) && !nngp_chunk_d) ||
       ((get_mask & SMN_GET_NTK) && !ntk_chunk_d))
     return smn_fail(ctx, SMN_EINVAL, "smn_kernel_mlp_shard_cols: null pointer or empty get mask");
+  SMN_CHECK_LD(ctx, "smn_kernel_mlp_shard_cols", ldx, d);
   ColPieces cp;
   SMN_TRY(col_pieces_make(ctx, n, nranks, npieces, piece_cols, &cp));
   const size_t es = dtype_size(dtype);
@@ -1462,6 +1471,10 @@ extern "C" int smn_gram(smn_ctx* ctx, int dtype, const void* x1_d, int64_t n1, i
                         int64_t n2, int64_t ldx2, int64_t d, void* k0_d, int64_t ldk, void* q1_d, void* q2_d) {
   SMN_TRY(check_common(ctx, dtype, n1, x2_d ? n2 : 1, d));
   SMN_ENTER(ctx);
+  SMN_CHECK_LD(ctx, "smn_gram", ldx1, d);
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_gram", ldx2, d);
+  if (x2_d) SMN_CHECK_LD(ctx, "smn_gram", ldk, n2);
+  else SMN_CHECK_LD(ctx, "smn_gram", ldk, n1);
   BuildSpec s{dtype, NET_NONE, SMN_ACT_RELU, 0, 1.0, 0.0, 1.0};
   return build_public(ctx, s, x1_d, n1, ldx1, x2_d, n2, ldx2, d, SMN_GET_NNGP, SMN_FILL_FULL, 0, 0, k0_d, nullptr,
                       ldk, q1_d, q2_d);
@@ -1473,6 +1486,8 @@ extern "C" int smn_recursion(smn_ctx* ctx, int dtype, int net, int act, int num_
                              void* ntk_d, int64_t ldk) {
   SMN_TRY(check_common(ctx, dtype, n1, n2, 1));
   SMN_ENTER(ctx);
+  SMN_CHECK_LD(ctx, "smn_recursion", ldk0, n2);
+  SMN_CHECK_LD(ctx, "smn_recursion", ldk, n2);
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   if (dtype == SMN_F64)
     return recursion_t<double>(ctx, s, k0_d, n1, n2, ldk0, q1_d, q2_d, symmetric, get_mask, nngp_d, ntk_d, ldk);

@@ -454,7 +454,8 @@ extern "C" int smn_loo_head(smn_ctx* ctx, int dtype, const void* neg_kinv_d, int
   if (!ctx || !neg_kinv_d || !alpha_d || !y_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(loo_check(ctx, "smn_loo_head", dtype, n, c, df, scale));
-  if (ldkinv < n || (g_d && ldg < n)) return smn_fail(ctx, SMN_EINVAL, "smn_loo_head: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_loo_head", ldkinv, n);
+  if (g_d) SMN_CHECK_LD(ctx, "smn_loo_head", ldg, n);
   return loo_head(ctx, dtype, neg_kinv_d, ldkinv, alpha_d, y_d, n, c, df, scale, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h,
                   g_d, ldg);
 }
@@ -465,7 +466,8 @@ extern "C" int smn_loo_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int6
   if (!ctx || !k_d || !y_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(loo_check(ctx, "smn_loo_multi", dtype, n, c, df, scale));
-  if (ldk < n || (g_d && ldg < n)) return smn_fail(ctx, SMN_EINVAL, "smn_loo_multi: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_loo_multi", ldk, n);
+  if (g_d) SMN_CHECK_LD(ctx, "smn_loo_multi", ldg, n);
   const size_t es = dtype_size(dtype);
   const int64_t ld0 = round_up(n, 16 / (int64_t)es);
   void* post = nullptr;
@@ -491,7 +493,8 @@ extern "C" int smn_spr_loo_grad(smn_ctx* ctx, int dtype, int net, int act, int n
   if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(loo_check(ctx, "smn_spr_loo_grad", dtype, n, c, df, scale));
-  if (d <= 0 || ldx < d) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loo_grad: bad sizes");
+  if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loo_grad: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_spr_loo_grad", ldx, d);
   const size_t es = dtype_size(dtype);
   const int64_t ld0 = round_up(n, 16 / (int64_t)es);
   void *k0 = nullptr, *post = nullptr;
@@ -560,7 +563,11 @@ extern "C" int smn_spr_kinv(smn_ctx* ctx, int dtype, int net, int act, int num_h
   SMN_ENTER(ctx);
   SMN_TRY(loo_check(ctx, "smn_spr_kinv", dtype, n, c, 0.0, 1.0));
   const size_t es = dtype_size(dtype);
-  if (d <= 0 || ldx < d || ldkinv < n || ldkinv % (16 / (int64_t)es)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_kinv: bad sizes");
+  if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_kinv: bad sizes");
+  SMN_CHECK_LD(ctx, "smn_spr_kinv", ldx, d);
+  SMN_CHECK_LD(ctx, "smn_spr_kinv", ldkinv, n);
+  if (ldkinv % (16 / (int64_t)es))
+    return smn_fail(ctx, SMN_EINVAL, "smn_spr_kinv: ldkinv = %lld is not a multiple of 16 bytes", (long long)ldkinv);
   const int64_t ld0 = round_up(n, 16 / (int64_t)es);
   void* k0 = nullptr;
   SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));

@@ -739,8 +739,10 @@ extern "C" int smn_svsp_elbo_grad(smn_ctx* ctx, int dtype, const void* k_d, int6
   if (!ctx || !k_d || !q_mu_d || !q_var_d || !labels_h || !g_q_mu_d || !g_q_var_d || !gbar_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   SMN_TRY(head_check(ctx, "smn_svsp_elbo_grad", dtype, labels_h, B, C, S, df, scale, point0));
-  if (I <= 0 || I + B > 65535 || ldk < I + B || ldg < I + B || !(eps >= 0.0) || !(num_train > 0.0) || !(s > 0.0))
+  if (I <= 0 || I + B > 65535 || !(eps >= 0.0) || !(num_train > 0.0) || !(s > 0.0))
     return smn_fail(ctx, SMN_EINVAL, "smn_svsp_elbo_grad: bad sizes (at most 65535 inducing points), eps < 0, or num_train, s not > 0");
+  SMN_CHECK_LD(ctx, "smn_svsp_elbo_grad", ldk, I + B);
+  SMN_CHECK_LD(ctx, "smn_svsp_elbo_grad", ldg, I + B);
   if (dnoise_d && !noise_d) return smn_fail(ctx, SMN_EINVAL, "smn_svsp_elbo_grad: dnoise_d without noise_d");
   double res[7] = {};
   const double* k = static_cast<const double*>(k_d);
