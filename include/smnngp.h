@@ -476,6 +476,12 @@ int smn_spr_cnn_loo_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
  *                (r2, r3) -> (u, v) = (r + 1/2) 2^-31 - 1; the first try with w = u^2 + v^2 <= 1 gives
  *                t = u sqrt(df (w^(-2/df) - 1) / w).  64 tries at most (a loop of fixed trip count; 1e-43 of the variates
  *                find none and are 0).
+ *     chi-square ctr = (s, 0, 0, 0xC0000000 | k), k = 0 .. 31: the mixing variate g_s ~ chi2(df) of draw s (smn_rng_chi2,
+ *                smn_mvn_draws below), chi2(df) = 2 Gamma(df / 2) by Marsaglia & Tsang: a = df / 2 (a + 1 and the boost U^(1/a)
+ *                if a < 1), d = a - 1/3, c = 1 / sqrt(9 d); try k: (r0, r1) -> x by Box-Muller (cos branch), v = (1 + c x)^3,
+ *                rejected if 1 + c x <= 0; r2 -> u, accepted if ln u < x^2 / 2 + d - d v + d ln v; r3 -> the boost uniform.
+ *                32 tries at most (fixed trip count; a draw that finds none is df, probability below 1e-40).  Always fp64.
+ *                Word 3 collides with neither the normal stream (0) nor the Student-t stream (0x80000000 | k, k < 32).
  * fp32 evaluates the same formulas in fp32 on the top 23 bits of a word for u in (0, 1) ((r >> 9) 2^-23 + 2^-24) and the top 24
  * for (u, v) in (-1, 1) ((r >> 8) 2^-23 + 2^-24 - 1): odd multiples of 2^-24, exact in fp32, never 0 or +-1.
  * smn_debug_philox: test hook, one raw block: out = Philox4x32-10(ctr, key), computed on the device. */
@@ -543,6 +549,28 @@ int smn_svsp_elbo_grad(smn_ctx* ctx, int dtype, const void* k_d, int64_t ldk, in
                        const void* noise_d, const void* dnoise_d, double* nll_h, double* kl_n_h, void* g_q_mu_d,
                        void* g_q_var_d, double* g_eps_h, double* gscale_h, double* g_s_h, double* dfterm_h,
                        void* gbar_d, int64_t ldg, int* info_h);
+
+/* ---- joint posterior function draws of the exact models (SPR / MultiSPR.sample_posterior) ----
+ * From the posterior mean [T,C] and a finished lower Cholesky factor L [T,T] of the (ridged) posterior covariance:
+ *     out[s,t,c] = mean[t,c] + r_s sum_{k<=t} L[t,k] xi[k,c,s]
+ * xi[k,c,s] is the NORMAL variate of (seed, point point0 + k, class c, draw s) of the generator above -- the value
+ * smn_rng_variates(df = 0) returns, whatever df is here -- or noise_d[k,c,s] when noise_d [T,C,S] of `dtype` is given (the
+ * seam the product is tested through; its strided loads are not meant to be fast).  r_s = 1 for df <= 0 (a Gaussian draw;
+ * shape is ignored).  For df > 0, r_s = sqrt(shape df / g_s) with ONE g_s ~ chi2(df) per draw, shared by all its points and
+ * outputs -- which makes draw s a multivariate t with df degrees of freedom and shape matrix shape (I_C x L L^T), not T C
+ * independent ones: g_s = mix_d[s] (fp64 [S]) when mix_d is given, else the variate smn_rng_chi2 returns for (seed, s); r_s is
+ * formed in fp64 and rounded to `dtype` once.
+ * The product runs on the MFMA tile engine (f32 / f64 16x16x4) in `dtype`; its operand xi is generated tile by tile into the
+ * LDS image and never stored.  Only the lower triangle of l_d (ld = ldl >= T, no alignment asked) is read, and only the
+ * K-steps at or left of a column tile's last row are run.  The order of the sum over k depends on T alone -- not on S, C or
+ * the grid --, there are no floating-point atomics: two calls give the same bits, and noise_d = smn_rng_variates(df = 0),
+ * mix_d = smn_rng_chi2 give the bits of noise_d = mix_d = NULL.  out_d [S,T,C] of `dtype`.
+ * SMN_EINVAL: null pointers, bad dtype, T, C or S < 1, df > 0 without shape > 0, point0 < 0, point0 + T > 2^32, S > 2^32,
+ * ldl < T (by name); SMN_ENOTSUP: C > SMN_SVSP_MAX_CLASSES.  Synchronises.
+ * smn_rng_chi2: out_d [S] fp64 = the chi-square mixing variates of (seed, s), s < S (layout above); df > 0. */
+int smn_rng_chi2(smn_ctx* ctx, uint64_t seed, double df, int64_t S, void* out_d);
+int smn_mvn_draws(smn_ctx* ctx, int dtype, const void* mean_d, const void* l_d, int64_t ldl, int64_t T, int64_t C, int64_t S,
+                  double df, double shape, uint64_t seed, int64_t point0, const void* noise_d, const void* mix_d, void* out_d);
 
 /* ---- reverse mode of the conv-NNGP kernel with respect to its input images (spax/models.py:21,31: SVSP.inducing_variable is
  *      a TrainVar; experiments/classification/train.py:205 puts model.vars() into the optimiser) ----

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "smn_svsp_head_grad": [_vp, _i, _vp, _vp, _pi, _i64, _i64, _i64, _d, _d, C.c_uint64, _i64, _vp, _vp, _pd, _vp, _vp, _pd, _pd, _pi],
     "smn_svsp_elbo_grad": [_vp, _i, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _d, _d, _d, _pi, _i64, _d, _d, C.c_uint64, _i64, _vp, _vp,
                            _pd, _pd, _vp, _vp, _pd, _pd, _pd, _pd, _vp, _i64, _pi],
+    "smn_rng_chi2": [_vp, C.c_uint64, _d, _i64, _vp],
+    "smn_mvn_draws": [_vp, _i, _vp, _vp, _i64, _i64, _i64, _i64, _d, _d, C.c_uint64, _i64, _vp, _vp, _vp],
     "smn_debug_philox": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "smn_comm_init": [_vp, _i, _i, C.c_char_p],
     "smn_comm_destroy": [_vp],

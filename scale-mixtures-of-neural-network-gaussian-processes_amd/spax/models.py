@@ -2,7 +2,7 @@
 one kernel matrix: exact multi-class classification on one-hot targets) and SVSP (the sparse variational scale-mixture
 classifier): evaluation (test_acc_nll / evaluate) and the training loss with its analytic gradient (loss_and_grad) with
 respect to every trainable -- the inducing images through a reverse-mode pass of the conv kernel seeded with d loss / d K
-(inducing_grad=True).  SVSP.loss itself (a value for an autodiff framework to differentiate) still raises."""
+(inducing_grad=True).  The exact models also draw joint function samples from their posterior (sample_posterior).  SVSP.loss itself (a value for an autodiff framework to differentiate) still raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -157,7 +157,70 @@ class _LooMixin:
         return -lam.value / n, grads
 
 
-class SPR(_LooMixin, Module):
+class _DrawsMixin:
+    """Joint function draws from the posterior of the exact models: the predictive law of all T test points and C outputs
+    together, where test_nll only ever reads its per-point marginals.  Gaussian likelihood: vec(f) ~ N(mean, I_C x cov).
+    Student-t likelihood: a multivariate t with df_post = 2a + N C degrees of freedom and shape matrix
+    shape (I_C x cov), shape = (2a + quad) / df_post * b/a -- a Gaussian draw times ONE sqrt(shape df_post / chi2(df_post))
+    per draw, shared by all its points and outputs (csrc/draws.hip)."""
+
+    def predict(self, x):
+        """(mean [T,C], cov [T,T]) of NNGPKernel.predict (relative ridge eps) as device arrays in normalised units: one
+        covariance shared by the outputs (C = 1 for SPR)."""
+        return self.kernel.predict(self.kernel.get_kernel_fn(), self.x_data, self.y_data, x, eps=self.eps.safe_value)
+
+    def _draws_quad(self, kernel_fn, scale):
+        return self._student_quad_f64(kernel_fn, scale)
+
+    def predictive_params(self):
+        """(df_post, shape) of the predictive law in normalised units.  Gaussian likelihood: (None, 1.0), no device work.
+        Student-t: df_post = 2a + N C and shape = (2a + quad) / df_post * b/a with quad = y^T ((b/a) K + 1e-6 I)^-1 y, the
+        fp64 number test_nll uses: the marginal of a draw at point t is test_nll's Student-t with sigma_t = sqrt(shape cov_tt)."""
+        if not hasattr(self.likelihood, "lml_params"):
+            raise NotImplementedError("predictive_params needs a Gaussian or Student-t likelihood")
+        df, scale = self.likelihood.lml_params()
+        if not df > 0.0:
+            return None, 1.0
+        n, c = self._loo_shape()
+        df_post = df + n * c
+        quad = self._draws_quad(self.kernel.get_kernel_fn(), scale)
+        return df_post, (df + quad) / df_post * scale
+
+    def sample_posterior(self, key, x, num_samples, *, jitter=1e-6):
+        """num_samples joint draws of the latent function at x: a device array [S,T] (SPR) or [S,T,C] (MultiSPR) in the
+        model's dtype and in NORMALISED units, like predict (test_nll de-normalises as f * y_std + y_mean; do the same to a
+        draw to compare it with targets).  predict, then smn_cholesky of the covariance in place with the relative ridge
+        `jitter` (cov + jitter tr(cov)/T I), then smn_mvn_draws: the draw of (seed, point, output, draw index) is a pure
+        function of those, so `key` is an int seed or (seed, global index of the first point of x), as in SVSP.  A
+        covariance that does not factor, or a Student-t shape that is not a positive finite number (the fp64 quadratic form
+        of predictive_params failed), gives an all-NaN array (the package's convention for a failed Cholesky); neither
+        raises.  1e-6 is the package's default ridge; an fp32 model will usually need more (a posterior covariance is
+        ill-conditioned by nature: 1e-3 is a reasonable start), which is the caller's call.  Works for every nt_kernels
+        factory, since it needs predict only."""
+        seed, point0 = split_key(key)
+        s = int(num_samples)
+        if s < 1:
+            raise ValueError("num_samples must be at least 1")
+        df_post, shape = self.predictive_params()
+        mean, cov = self.predict(x)
+        ctx = mean.ctx
+        mean, cov = as_device(mean, ctx), as_device(cov, ctx)     # plain buffers: a lazy scale * A + shift * I is materialised
+        t, c = mean.shape
+        out_shape = (s, t, c) if hasattr(self, "num_outputs") else (s, t)
+        nan = lambda: ctx.to_device(np.full(out_shape, np.nan, dtype=mean.dtype))
+        if df_post is not None and not (np.isfinite(shape) and shape > 0.0):
+            return nan()
+        info = C.c_int()
+        ctx.call("smn_cholesky", cov.dcode, cov.ptr, t, t, t, t, 0.0, float(jitter), C.byref(info), None)
+        if info.value != 0:
+            return nan()
+        out = ctx.empty(out_shape, mean.dtype)
+        ctx.call("smn_mvn_draws", mean.dcode, mean.ptr, cov.ptr, t, t, c, s, df_post or 0.0, shape, seed, point0, None, None,
+                 out.ptr)
+        return out
+
+
+class SPR(_DrawsMixin, _LooMixin, Module):
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, eps: float = 1e-6):
         super().__init__()
         self.kernel = kernel
@@ -199,6 +262,14 @@ class SPR(_LooMixin, Module):
         val = float("nan") if info.value else quad.value / scale
         self._quad64_cache = (key, val)
         return val
+
+    def _draws_quad(self, kernel_fn, scale):
+        """The quadratic form of test_nll's Student-t head, by test_nll's own two routes."""
+        if isinstance(kernel_fn, KernelFn):
+            return self._student_quad_f64(kernel_fn, scale)
+        from .utils import factor_stats
+        cov_data = self.kernel.K(kernel_fn, self._f64_data()[0])
+        return factor_stats(self.y_host, scale * cov_data + jitter(self.num_data))[0]
 
     # ---- spax/models.py:93-98
     def loss(self):
@@ -307,7 +378,7 @@ def multi_grad_route(kernel_fn, likelihood):
     return grad_route(kernel_fn, likelihood) + "_multi"
 
 
-class MultiSPR(_LooMixin, Module):
+class MultiSPR(_DrawsMixin, _LooMixin, Module):
     """Exact GP / Student-t process with C outputs over ONE kernel matrix: y_data [N,C], K~ = K(x,x) + eps I.
 
     Gaussian likelihood: the C columns are independent GPs that share K~ (the log-pdf is the sum of C
@@ -439,9 +510,7 @@ class MultiSPR(_LooMixin, Module):
             grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
         return -lp / n, grads
 
-    def predict(self, x):
-        """(mean [T,C], cov [T,T]) of NNGPKernel.predict (relative ridge eps): one covariance shared by the outputs."""
-        return self.kernel.predict(self.kernel.get_kernel_fn(), self.x_data, self.y_data, x, eps=self.eps.safe_value)
+    # predict(x) -> (mean [T,C], cov [T,T]) is _DrawsMixin's, shared with SPR
 
     def _student_quad_f64(self, kernel_fn, scale):
         """tr(Y^T (scale K + 1e-6 I)^-1 Y) with K WITHOUT eps, always in fp64 (SPR._student_quad_f64 for C columns); the
