@@ -351,10 +351,12 @@ __global__ void __launch_bounds__(panel_threads(XRV)) panel_kernel(T* __restrict
   }
 
   if (blockIdx.x == 0 && !prefactored) {
-    // logdet += sum_j log d_j, info = first non-positive pivot (one log per thread, not per pivot per thread)
+    // logdet += 2 sum_j log L_jj of the diagonal AS STORED (smnngp.h; the same as panelr_kernel: the log of the pivot d_j
+    // differs from it by the rounding of L_jj = d_j rsqrt(d_j)), info = first non-positive pivot (one log per thread, not
+    // per pivot per thread)
     if (tid < 64) {   // one wave, two pivots per lane: a single deterministic atomic per sub-panel
       const T d0 = piv[tid], d1 = piv[tid + 64];
-      double lg = log((double)d0) + log((double)d1);
+      double lg = 2.0 * (log((double)S[tid * LD + tid]) + log((double)S[(tid + 64) * LD + tid + 64]));
       int bad = !(d0 > T(0)) ? tid : (!(d1 > T(0)) ? tid + 64 : INT_MAX);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
@@ -878,6 +880,9 @@ __global__ void __launch_bounds__(256, BN == 64 ? 4 : (BM == 64 ? (sizeof(T) == 
     upd_decode(u, (int)blockIdx.x, tr, tc);
   }
   const int64_t row0 = u.r0 + (int64_t)tr * BM + qr, col0 = u.c0 + (int64_t)tc * kTile + qc;
+  // a tile on the diagonal reaches above it: those elements are computed (the tile is square) but never stored -- the
+  // strict upper triangle of the matrix is the caller's (smnngp.h: lower triangle read/written).  Uniform per workgroup.
+  const bool clip = col0 + BN - 1 > row0;
   Tile t;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -895,6 +900,19 @@ __global__ void __launch_bounds__(256, BN == 64 ? 4 : (BM == 64 ? (sizeof(T) == 
       }
   // trailing updates (TAG 1) run K = 256 ... 1024: the pipelined K loop; strips (K = 128) the plain one
   t.template mainloop<TAG == 1 ? 1 : 0>(u.a + row0 * u.lda + u.k0, u.lda, u.a + col0 * u.lda + u.k0, u.lda, u.K, smem);
+  if (clip) {   // (its own copy of the loop: the stores of every other tile stay unconditional)
+#pragma unroll
+    for (int m = 0; m < Tile::MT; ++m)
+#pragma unroll
+      for (int n = 0; n < Tile::NT; ++n)
+#pragma unroll
+        for (int i = 0; i < M::ACC; ++i) {
+          const int64_t gr = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
+          const int64_t gc = col0 + wc * Tile::WN + n * M::TN + M::acc_col(lane);
+          if (gc <= gr) u.a[gr * u.lda + gc] = -t.acc[m][n][i];
+        }
+    return;
+  }
 #pragma unroll
   for (int m = 0; m < Tile::MT; ++m)
 #pragma unroll
@@ -995,16 +1013,30 @@ __global__ void __launch_bounds__(256, 2) trail_kernel(UpdArgs<T> u, int ntiles)
     __syncthreads();
     cur ^= 1;
     // C_new = C - acc = -(cn + acc)
+    if (col0 + kTile - 1 > row0) {   // a tile on the diagonal: nothing is stored above it (update_kernel)
 #pragma unroll
-    for (int m = 0; m < Tile::MT; ++m)
+      for (int m = 0; m < Tile::MT; ++m)
 #pragma unroll
-      for (int n = 0; n < Tile::NT; ++n)
+        for (int n = 0; n < Tile::NT; ++n)
 #pragma unroll
-        for (int i = 0; i < M::ACC; ++i) {
-          a[(row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i)) * lda + col0 + wc * Tile::WN + n * M::TN +
-            M::acc_col(lane)] = -(cn[m][n][i] + t.acc[m][n][i]);
-          t.acc[m][n][i] = T(0);
-        }
+          for (int i = 0; i < M::ACC; ++i) {
+            const int64_t gr = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
+            const int64_t gc = col0 + wc * Tile::WN + n * M::TN + M::acc_col(lane);
+            if (gc <= gr) a[gr * lda + gc] = -(cn[m][n][i] + t.acc[m][n][i]);
+            t.acc[m][n][i] = T(0);
+          }
+    } else {
+#pragma unroll
+      for (int m = 0; m < Tile::MT; ++m)
+#pragma unroll
+        for (int n = 0; n < Tile::NT; ++n)
+#pragma unroll
+          for (int i = 0; i < M::ACC; ++i) {
+            a[(row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i)) * lda + col0 + wc * Tile::WN + n * M::TN +
+              M::acc_col(lane)] = -(cn[m][n][i] + t.acc[m][n][i]);
+            t.acc[m][n][i] = T(0);
+          }
+    }
     if (!has_next) break;
     tile = nxt;
     row0 = nrow0;

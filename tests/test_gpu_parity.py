@@ -585,6 +585,18 @@ def test_cholesky_more_workgroups_than_cus_and_lookahead(L, ctx, dtype, n, m):
         w = sla.solve_triangular(l, a[:n, n:], lower=True).T
         assert relerr_norm(got[n:, :n], w) < tol
         assert relerr_norm(np.tril(got[n:, n:]), np.tril(a[n:, n:] - w @ w.T)) < tol
+    # componentwise backward error of the factor on one row of every 16 (tests/_factor_rules.py): the derived bound, and 8 x the
+    # reference's in this precision; logdet against the stored diagonal.  The reference is the emulated chain, not LAPACK
+    # (printed beside it): these sizes lie beyond every shape of R.CHAIN_SHAPES, where the one-chain summation of update_kernel
+    # already costs more than 8 x LAPACK's blocked sums -- measured here: library | LAPACK 53.2 | 4.3 (fp64), 128 | 14.5 (fp32).
+    import _factor_rules as R
+    ah, lh = np.ascontiguousarray(a[:n, :n].astype(dtype)), ad.numpy()[:n, :n]
+    rho = R.rho_factor(ah, lh)
+    f_ref = R.lapack_factor(ah, n)[0]
+    rho_ref = R.chain_residuals(ah, f_ref, n)["factor"]
+    print("rho_factor (%d,%d) %s: gpu %.3g chain %.3g lapack %.3g" % (n, m, np.dtype(dtype).name, rho, rho_ref, R.rho_factor(ah, f_ref)))
+    assert rho <= n + 1 and rho <= R.REF_FACTOR * rho_ref, (rho, rho_ref)
+    assert abs(logdet.value - R.logdet_self(lh)[0]) <= R.logdet_bound(lh), (logdet.value, R.logdet_self(lh))
 
 
 @pytest.mark.parametrize("env", [
