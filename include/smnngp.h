@@ -180,6 +180,35 @@ int smn_trsm(smn_ctx* ctx, int dtype, const void* l_d, int64_t n, int64_t ldl,
 int smn_transpose(smn_ctx* ctx, int dtype, void* dst_d, int64_t ldd, const void* src_d, int64_t lds, int64_t rows,
                   int64_t cols);
 
+/* smn_eigh_pd: eigendecomposition A = V diag(w) V^T of a symmetric POSITIVE DEFINITE matrix a_d [n,n] (lower triangle read,
+ * ld = lda, not modified).  Replaces jnp.linalg.eigh inside neural_tangents.predict.gradient_descent_mse_ensemble
+ * (predict_fn(t=...), reached from spax/kernels.py:29-32) and inside neural_tangents.predict.max_learning_rate.
+ * w_d [n]: eigenvalues, ascending, in dtype.  v_d [n,n] ld = ldv: v_d[i*ldv + k] = component i of eigenvector k.
+ * Method: the project's Cholesky factorisation, then one-sided Jacobi on the factor in fp64 (csrc/eigh.hip); the host
+ * reads one convergence word per sweep.  Two calls on the same input return the same bits.
+ * *info_h: 0 converged; k > 0: not positive definite (the factorisation's failing pivot, 1-based), w and v are NaN;
+ * -1: not converged within max_sweeps (results still written).  max_sweeps <= 0 means 30 (at most 1000).
+ * *sweeps_h (may be NULL): sweeps taken.  Workspace (kept by the context): the padded factor (round_up(n,128)^2 elements),
+ * the fp64 working matrix (n^2 doubles) and V^T (n^2 elements): about 3 n^2 elements in fp64, 4 n^2 in fp32. */
+int smn_eigh_pd(smn_ctx* ctx, int dtype, const void* a_d, int64_t n, int64_t lda, void* w_d, void* v_d, int64_t ldv,
+                int max_sweeps, int* info_h, int* sweeps_h);
+
+/* smn_predict_gd: mean and covariance of the infinite ensemble after gradient-flow time t on the MSE loss
+ * (neural_tangents.predict.gradient_descent_mse_ensemble, predict_fn(t=...); sample.ipynb:194-195 is the t = None form).
+ * k_joint_d / theta_joint_d: NNGP / NTK kernels of [x_train; x_test], [n+t, n+t] ld = ld, lower triangles read, neither
+ * modified; theta_joint_d NULL selects get="nngp" (G = K), otherwise get="ntk" (G = Theta).  y_d [n,c] row-major.
+ *   G~ = G_dd + (diag_abs + diag_rel tr(G_dd)/n) I = V diag(lambda) V^T (smn_eigh_pd's solver), lambda clamped at 0,
+ *   s = learning_rate * time / (n c),  d = -expm1(-lambda s)/lambda,  e = -expm1(-2 lambda s)/lambda  (time = +inf: 1/lambda),
+ *   P = G_*d V,  mean = (P.d) V^T y,  nngp: cov = K_** - (P.e) P^T,
+ *   ntk: A = (P.d) V^T, cov = K_** + A K_dd A^T - (A K_d* + K_*d A^T)   (K_dd without the ridge).
+ * times_h [nt] host, each >= 0 or +inf.  mean_d [nt,t,c]; cov_d [nt,t,ldc] (ldc >= t; NULL: mean only), symmetric to
+ * the bit; evals_d [n] (may be NULL) receives lambda.  The products that do not depend on the time are formed once.
+ * *info_h: smn_eigh_pd's; != 0 gives NaN results and SMN_OK. */
+int smn_predict_gd(smn_ctx* ctx, int dtype, const void* k_joint_d, const void* theta_joint_d, int64_t n, int64_t t,
+                   int64_t ld, const void* y_d, int64_t c, double diag_rel, double diag_abs, const double* times_h,
+                   int64_t nt, double learning_rate, void* mean_d, void* cov_d, int64_t ldc, void* evals_d,
+                   int* info_h);
+
 /* ---- likelihood heads (host scalars out) ----
  * smn_lml: log-marginal likelihood of y_d [n] under cov = K + eps I, K given as k_d [n,n] lower
  * (destroyed: overwritten by its factor).  df <= 0: Gaussian (spax/likelihoods.py:25-28);

@@ -1,5 +1,6 @@
-"""neural_tangents.predict.gradient_descent_mse_ensemble look-alike (t = infinity; NNGP posterior fused on the
-device, NTK posterior composed from the public entry points).
+"""neural_tangents.predict.gradient_descent_mse_ensemble look-alike (t = None: NNGP posterior fused on the
+device, NTK posterior composed from the public entry points; t = times: the finite-time ensemble through the
+device eigensolver, smn_predict_gd).
 
 Called by spax/kernels.py:30-31 and experiments/regression/find.py:75-76 as
     predict_fn = gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=eps)
@@ -20,13 +21,16 @@ __all__ = ["gradient_descent_mse_ensemble", "PredictResult"]
 
 
 class PredictResult(tuple):
-    """(mean, cov) plus the by-products of the factorisation."""
+    """(mean, cov) plus the by-products of the factorisation (t = None) or of the eigendecomposition (t given:
+    `evals`, the ascending eigenvalues of the regularised train-train kernel)."""
     quad = None
     logdet = None
     info = 0
+    evals = None
 
 
-def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, diag_reg_absolute_scale=False):
+def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, diag_reg_absolute_scale=False,
+                                  learning_rate=1.0):
     ctx = getattr(kernel_fn, "ctx", None) or (x_train.ctx if isinstance(x_train, _lib.DeviceArray) else default_context())
     x = as_device(x_train, ctx)
     y = as_device(np.asarray(y_train).reshape(x.shape[0], -1) if not isinstance(y_train, _lib.DeviceArray) else y_train,
@@ -36,7 +40,7 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
 
     def predict_fn(t=None, x_test=None, get="nngp", compute_cov=True):
         if t is not None:
-            raise NotImplementedError("only the t = infinity posterior is on the hot path")
+            return _predict_gd(t, x_test, get, compute_cov)
         if get == "ntk":
             return _predict_ntk(x_test, compute_cov)
         if get != "nngp":
@@ -65,6 +69,49 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
         res.quad = np.array(list(quad))
         res.logdet = logdet.value
         res.info = info.value
+        return res if compute_cov else res[0]
+
+    def _predict_gd(t, x_test, get, compute_cov):
+        """Finite training time (gradient flow on 0.5 * mean((f - y)^2) over all N*C outputs, neural_tangents' normalisation):
+            G~ = G_dd + ridge = V diag(lam) V^T,  s = learning_rate * t / (N C),  d = -expm1(-lam s) / lam,  e = -expm1(-2 lam s) / lam,
+            P = G_*d V,  mean = (P.d) V^T y,   nngp: cov = K_** - (P.e) P^T,
+            ntk: A = (P.d) V^T,  cov = K_** + A K_dd A^T - (A K_d* + K_*d A^T).
+        t: a scalar or a 1-D array of times >= 0 (inf allowed); an array gives results with a leading axis len(t).  One call
+        of smn_predict_gd: eigensolver, the time-independent products once, the scaled products per time, all on the device."""
+        if get not in ("nngp", "ntk"):
+            raise NotImplementedError("get must be 'nngp' or 'ntk'")
+        times = np.asarray(t, dtype=np.float64)
+        scalar = times.ndim == 0
+        times = np.ascontiguousarray(times.reshape(-1))
+        if times.size == 0 or np.isnan(times).any() or (times < 0).any() or np.asarray(t).ndim > 1:
+            raise ValueError("t must be a scalar or a non-empty 1-D array of times >= 0 (inf allowed)")
+        xt = x if x_test is None else as_device(x_test, ctx, dtype=x.dtype)
+        tt, dt, nt = xt.shape[0], x.dtype, times.size
+        if isinstance(kernel_fn, KernelFn):   # the joint build of the t = None NTK branch
+            xa = ctx.to_device(np.concatenate([x.numpy().reshape(n, -1), xt.numpy().reshape(tt, -1)], axis=0))
+        else:
+            xa = np.concatenate([np.asarray(x), np.asarray(xt)], axis=0)
+        if get == "ntk":
+            both = kernel_fn(xa, None, ("nngp", "ntk"))
+            kj, tj = as_device(both[0], ctx, dtype=dt), as_device(both[1], ctx, dtype=dt)
+        else:
+            kj, tj = as_device(kernel_fn(xa, None, "nngp"), ctx, dtype=dt), None
+        m = n + tt
+        mean = ctx.empty((nt, tt, c), dt)
+        cov = ctx.empty((nt, tt, tt), dt) if compute_cov else None
+        evals = ctx.empty((n,), dt)
+        info = C.c_int()
+        rel, ab = (0.0, float(diag_reg)) if diag_reg_absolute_scale else (float(diag_reg), 0.0)
+        ctx.call("smn_predict_gd", x.dcode, kj.ptr, None if tj is None else tj.ptr, n, tt, m, y.ptr, c, rel, ab,
+                 times.ctypes.data_as(C.POINTER(C.c_double)), nt, float(learning_rate), mean.ptr,
+                 None if cov is None else cov.ptr, tt, evals.ptr, C.byref(info))
+        mean_h = mean.numpy()
+        cov_h = cov.numpy() if compute_cov else None
+        if scalar:
+            mean_h, cov_h = mean_h[0], (cov_h[0] if compute_cov else None)
+        res = PredictResult((mean_h, cov_h) if compute_cov else (mean_h,))
+        res.info = info.value
+        res.evals = evals.numpy()
         return res if compute_cov else res[0]
 
     def _predict_ntk(x_test, compute_cov):
