@@ -324,114 +324,78 @@ int cgrad_check(smn_ctx* ctx, const char* who, int dtype, int act, int num_hidde
   return SMN_OK;
 }
 
+// smn_kernel_cnn_grad_terms (multi = false: alpha [n], the single-output kernel forms) / smn_kernel_cnn_grad_terms_multi (the
+// rank-C contraction: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1)
+int cnn_grad_terms(smn_ctx* ctx, const char* who, bool multi, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                   double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* neg_kinv_d,
+                   int64_t ldkinv, const void* alpha_d, int64_t c, double coef, double terms_h[4]) {
+  if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, who, dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  SMN_CHECK_LD(ctx, who, ldkinv, n);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
+  const int nc = multi ? (int)c : 0;
+  if (dtype == SMN_F64)
+    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                                 coef, terms_h, nc);
+  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+                              coef, terms_h, nc);
+}
+
+// smn_spr_cnn_loss_grad / smn_spr_cnn_loss_grad_multi.  Fused: the forward conv build of the lower triangle straight into the
+// factorisation workspace (smn_kernel_cnn), one factorisation of [[K~], [I], [Y^T]] for the c target columns that share K~
+// (heads.hip posterior_from_images: alpha, -K~^-1, quad, logdet), then the contraction above over the image pairs.
+int spr_cnn_loss_grad(smn_ctx* ctx, const char* who, bool multi, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                      double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c,
+                      double eps_abs, double df, double scale, double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h,
+                      double terms_h[4]) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  SMN_TRY(cgrad_check(ctx, who, dtype, act, num_hiddens, last_w_std, n, H, W, C));
+  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
+  Posterior p;
+  SMN_TRY(posterior_from_images(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, y_d, c, eps_abs, &p));
+  const double tot = publish_head(p.quad, c, multi, p.logdet, p.info, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h,
+                                  terms_h);
+  if (p.info != 0) return SMN_OK;
+  return cnn_grad_terms(ctx, multi ? "smn_kernel_cnn_grad_terms_multi" : "smn_kernel_cnn_grad_terms", multi, dtype, act,
+                        num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, p.ninv, p.ldinv, p.alpha, c,
+                        lml_coef(df, scale, tot, n, c), terms_h);
+}
+
 }  // namespace
 
 extern "C" int smn_kernel_cnn_grad_terms(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                                          double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                                          const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, double coef,
                                          double terms_h[4]) {
-  if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  SMN_CHECK_LD(ctx, "smn_kernel_cnn_grad_terms", ldkinv, n);
-  if (dtype == SMN_F64)
-    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
-                                 coef, terms_h);
-  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
-                              coef, terms_h);
+  return cnn_grad_terms(ctx, "smn_kernel_cnn_grad_terms", false, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W,
+                        C, neg_kinv_d, ldkinv, alpha_d, 1, coef, terms_h);
 }
 
-// Fused: the forward conv build of the lower triangle straight into the factorisation workspace (smn_kernel_cnn), the
-// factorisation with identity (heads.hip: alpha, -K~^-1, quad, logdet), then the contraction above.
 extern "C" int smn_spr_cnn_loss_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                                      double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                                      const void* y_d, double eps_abs, double df, double scale, double* quad_h,
                                      double* logdet_h, int* info_h, double terms_h[4]) {
-  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  SMN_TRY(cgrad_check(ctx, "smn_spr_cnn_loss_grad", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad: scale must be > 0");
-  const size_t es = dtype_size(dtype);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void* post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n), &post));
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  double quad = 0.0, logdet = 0.0;
-  int info = 0;
-  const KernelInto build = [&](void* k_d, int64_t ldk) {
-    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER,
-                          k_d, ldk);
-  };
-  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, &quad, &logdet, &info));
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
-  if (info != 0) {
-    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
-    return SMN_OK;
-  }
-  double coef = 1.0;
-  if (df > 0.0) coef = (df + (double)n) / ((df + quad / scale) * scale);
-  return smn_kernel_cnn_grad_terms(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, alpha,
-                                   coef, terms_h);
+  return spr_cnn_loss_grad(ctx, "smn_spr_cnn_loss_grad", false, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C,
+                           y_d, 1, eps_abs, df, scale, quad_h, nullptr, logdet_h, info_h, terms_h);
 }
 
-// The rank-C contraction alone: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1.
 extern "C" int smn_kernel_cnn_grad_terms_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                                                double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                                                const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, int64_t c,
                                                double coef, double terms_h[4]) {
-  if (!ctx || !x_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  SMN_TRY(cgrad_check(ctx, "smn_kernel_cnn_grad_terms_multi", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn_grad_terms_multi: bad sizes");
-  SMN_CHECK_LD(ctx, "smn_kernel_cnn_grad_terms_multi", ldkinv, n);
-  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn_grad_terms_multi: more than 48 output columns");
-  if (dtype == SMN_F64)
-    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
-                                 coef, terms_h, (int)c);
-  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
-                              coef, terms_h, (int)c);
+  return cnn_grad_terms(ctx, "smn_kernel_cnn_grad_terms_multi", true, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H,
+                        W, C, neg_kinv_d, ldkinv, alpha_d, c, coef, terms_h);
 }
 
-// smn_spr_cnn_loss_grad for c target columns that share K~: the forward build, one factorisation of [[K~], [I], [Y^T]], one
-// rank-C contraction over the image pairs.
 extern "C" int smn_spr_cnn_loss_grad_multi(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                                            double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                                            const void* y_d, int64_t c, double eps_abs, double df, double scale, double* quad_h,
                                            double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]) {
-  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  SMN_TRY(cgrad_check(ctx, "smn_spr_cnn_loss_grad_multi", dtype, act, num_hiddens, last_w_std, n, H, W, C));
-  if (c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad_multi: bad sizes");
-  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_cnn_loss_grad_multi: more than 48 output columns");
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loss_grad_multi: scale must be > 0");
-  const size_t es = dtype_size(dtype);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void* post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  double quad[48], logdet = 0.0, tot = 0.0;
-  int info = 0;
-  const KernelInto build = [&](void* k_d, int64_t ldk) {
-    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER,
-                          k_d, ldk);
-  };
-  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, quad, &logdet, &info, c));
-  for (int64_t k = 0; k < c; ++k) tot += quad[k];
-  if (info != 0) tot = std::nan("");
-  if (quad_h) *quad_h = tot;
-  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = quad[k];
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
-  if (info != 0) {
-    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
-    return SMN_OK;
-  }
-  double coef = 1.0;
-  if (df > 0.0) coef = (df + (double)n * (double)c) / ((df + tot / scale) * scale);
-  return smn_kernel_cnn_grad_terms_multi(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, alpha,
-                                         c, coef, terms_h);
+  return spr_cnn_loss_grad(ctx, "smn_spr_cnn_loss_grad_multi", true, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H,
+                           W, C, y_d, c, eps_abs, df, scale, quad_h, quad_cols_h, logdet_h, info_h, terms_h);
 }

@@ -18,6 +18,7 @@
 //           phi_A = 4 / (pi sqrt(P) sqrt(1-s^2))     phi_qi = -(2/pi) s / (sqrt(1-s^2) (1+2q_i))
 #include <climits>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "gemm_nt.hpp"
@@ -425,6 +426,17 @@ __global__ void cast_q_kernel(const T* __restrict__ s, double* __restrict__ d, i
   if (i < n) d[i] = (double)s[i];
 }
 
+// f(NET, ACT) with the (net, act) pair of a validated call as compile-time constants: the one place the host code of this file
+// picks a kernel instantiation
+template <typename F>
+int with_net_act(int net, int act, F&& f) {
+  using std::integral_constant;
+  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) return f(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_RELU>{});
+  if (net == SMN_NET_MLP) return f(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_ERF>{});
+  if (act == SMN_ACT_RELU) return f(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_RELU>{});
+  return f(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_ERF>{});
+}
+
 template <typename T, int NET, int ACT>
 int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t ntiles, double* out_d, bool multi) {
   hipLaunchKernelGGL((grad_tables_kernel<NET, ACT, T>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -468,12 +480,9 @@ int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, 
   a.n = n; a.tab = reinterpret_cast<const T*>(tabd); a.nsets = nsets;
   a.w2 = w_std * w_std; a.b2 = b_std * b_std; a.lw2 = last_w_std * last_w_std; a.coef = coef;
   a.partial = partial;
-  int rc;
-  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_MLP, ACT_RELU>(ctx, a, q64, ntiles, out_d, multi);
-  else if (net == SMN_NET_MLP) rc = grad_terms_na<T, NET_MLP, ACT_ERF>(ctx, a, q64, ntiles, out_d, multi);
-  else if (act == SMN_ACT_RELU) rc = grad_terms_na<T, NET_RESNET, ACT_RELU>(ctx, a, q64, ntiles, out_d, multi);
-  else rc = grad_terms_na<T, NET_RESNET, ACT_ERF>(ctx, a, q64, ntiles, out_d, multi);
-  SMN_TRY(rc);
+  SMN_TRY(with_net_act(net, act, [&](auto NET, auto ACT) {
+    return grad_terms_na<T, decltype(NET)::value, decltype(ACT)::value>(ctx, a, q64, ntiles, out_d, multi);
+  }));
   double s[4];
   SMN_HIP(ctx, hipMemcpyAsync(s, out_d, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
   SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -577,16 +586,13 @@ int grad_batch_t(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int
     ba.aug = static_cast<const T*>(av); ba.lda = lda; ba.bstride = bstride; ba.aug0 = n_pad;
     ba.n = n; ba.tab = reinterpret_cast<const T*>(tabd); ba.tab_bs = (int64_t)ntab; ba.nsets = nsets;
     ba.prob = prob_d; ba.partial = partial; ba.ntiles = ntiles;
-    int rc;
     // a chunk of up to eight problems (a single start above all) publishes straight into the pinned mailbox, as the serial
     // call's read-out does: one synchronisation, no copy
     const bool mail = (size_t)nb * kBatchRes <= (size_t)smn_ctx::kMailGram;
     double* out_d = mail ? ctx->d_mail : res_d;
-    if (net == SMN_NET_MLP && act == SMN_ACT_RELU) rc = grad_batch_launch<T, NET_MLP, ACT_RELU>(ctx, ba, nb, q64, ld_d, info_d, out_d);
-    else if (net == SMN_NET_MLP) rc = grad_batch_launch<T, NET_MLP, ACT_ERF>(ctx, ba, nb, q64, ld_d, info_d, out_d);
-    else if (act == SMN_ACT_RELU) rc = grad_batch_launch<T, NET_RESNET, ACT_RELU>(ctx, ba, nb, q64, ld_d, info_d, out_d);
-    else rc = grad_batch_launch<T, NET_RESNET, ACT_ERF>(ctx, ba, nb, q64, ld_d, info_d, out_d);
-    SMN_TRY(rc);
+    SMN_TRY(with_net_act(net, act, [&](auto NET, auto ACT) {
+      return grad_batch_launch<T, decltype(NET)::value, decltype(ACT)::value>(ctx, ba, nb, q64, ld_d, info_d, out_d);
+    }));
     if (!mail)
       SMN_HIP(ctx, hipMemcpyAsync(res_h.data(), res_d, sizeof(double) * (size_t)nb * kBatchRes, hipMemcpyDeviceToHost, ctx->stream));
     SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -614,131 +620,86 @@ int grad_batch_t(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int
   return SMN_OK;
 }
 
+// smn_lml_grad_terms (multi = false: alpha [n], the single-output kernel form) / smn_lml_grad_terms_multi (the rank-C
+// contraction: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1)
+int lml_grad_terms(smn_ctx* ctx, const char* who, bool multi, int dtype, int net, int act, int num_hiddens, double w_std,
+                   double b_std, double last_w_std, const void* k0_d, int64_t n, int64_t ldk0, const void* q_d,
+                   const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, int64_t c, double coef, double terms_h[4]) {
+  if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
+  SMN_CHECK_LD(ctx, who, ldk0, n);
+  SMN_CHECK_LD(ctx, who, ldkinv, n);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
+  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
+  if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: bad hyper-parameters", who);
+  const int nc = multi ? (int)c : 0;
+  if (dtype == SMN_F64)
+    return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
+                                ldkinv, alpha_d, coef, terms_h, nc);
+  return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
+                             alpha_d, coef, terms_h, nc);
+}
+
+// smn_spr_loss_grad / smn_spr_loss_grad_multi.  Fused: K0 = X X^T / d and its diagonal, K by the stand-alone recursion straight
+// into the factorisation workspace laid out as the rectangle [[K~], [I], [Y^T]] for the c target columns that share K~, a
+// no-Schur factorisation (L, L^-T, L^-1 Y), -K~^-1 = -L^-T L^-1 as one full-rate launch, alpha = L^-T (L^-1 Y) (heads.hip
+// posterior_from_x), then the contraction under the coef of the joint Student-t head (lml_coef).
+int spr_loss_grad(smn_ctx* ctx, const char* who, bool multi, int dtype, int net, int act, int num_hiddens, double w_std,
+                  double b_std, double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                  double eps_abs, double df, double scale, double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h,
+                  double terms_h[4]) {
+  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
+  if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: empty", who);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
+  SMN_CHECK_LD(ctx, who, ldx, d);
+  Posterior p;
+  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p));
+  const double tot = publish_head(p.quad, c, multi, p.logdet, p.info, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h,
+                                  terms_h);
+  if (p.info != 0) return SMN_OK;
+  return lml_grad_terms(ctx, multi ? "smn_lml_grad_terms_multi" : "smn_lml_grad_terms", multi, dtype, net, act, num_hiddens, w_std,
+                        b_std, last_w_std, p.k0, n, p.ld0, p.q, p.ninv, p.ldinv, p.alpha, c, lml_coef(df, scale, tot, n, c),
+                        terms_h);
+}
+
 }  // namespace
 
 extern "C" int smn_lml_grad_terms(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
                                   double b_std, double last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
                                   const void* q_d, const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d,
                                   double coef, double terms_h[4]) {
-  if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms: bad sizes");
-  SMN_CHECK_LD(ctx, "smn_lml_grad_terms", ldk0, n);
-  SMN_CHECK_LD(ctx, "smn_lml_grad_terms", ldkinv, n);
-  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
-  if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms: bad hyper-parameters");
-  if (dtype == SMN_F64)
-    return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
-                                ldkinv, alpha_d, coef, terms_h);
-  return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
-                             alpha_d, coef, terms_h);
+  return lml_grad_terms(ctx, "smn_lml_grad_terms", false, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0,
+                        q_d, neg_kinv_d, ldkinv, alpha_d, 1, coef, terms_h);
 }
 
-// The rank-C contraction alone: alpha_d [n, c] row-major, G = coef A A^T - c K~^-1.
 extern "C" int smn_lml_grad_terms_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
                                         double b_std, double last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
                                         const void* q_d, const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d,
                                         int64_t c, double coef, double terms_h[4]) {
-  if (!ctx || !k0_d || !q_d || !neg_kinv_d || !alpha_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad sizes");
-  SMN_CHECK_LD(ctx, "smn_lml_grad_terms_multi", ldk0, n);
-  SMN_CHECK_LD(ctx, "smn_lml_grad_terms_multi", ldkinv, n);
-  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_grad_terms_multi: more than 48 output columns");
-  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
-  if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_grad_terms_multi: bad hyper-parameters");
-  if (dtype == SMN_F64)
-    return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
-                                ldkinv, alpha_d, coef, terms_h, (int)c);
-  return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
-                             alpha_d, coef, terms_h, (int)c);
+  return lml_grad_terms(ctx, "smn_lml_grad_terms_multi", true, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n,
+                        ldk0, q_d, neg_kinv_d, ldkinv, alpha_d, c, coef, terms_h);
 }
 
-// smn_spr_loss_grad for c target columns that share K~: one factorisation of [[K~], [I], [Y^T]] (heads.hip), one rank-C
-// contraction.  coef of the joint Student-t head: (df + n c) / ((df + Q / s) s), Q = the sum of the c quadratic forms.
 extern "C" int smn_spr_loss_grad_multi(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
                                        double b_std, double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d,
                                        const void* y_d, int64_t c, double eps_abs, double df, double scale, double* quad_h,
                                        double* quad_cols_h, double* logdet_h, int* info_h, double terms_h[4]) {
-  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || d <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: empty");
-  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_grad_multi: more than 48 output columns");
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_multi: scale must be > 0");
-  SMN_CHECK_LD(ctx, "smn_spr_loss_grad_multi", ldx, d);
-  const size_t es = dtype_size(dtype);
-  const int64_t al = 16 / (int64_t)es;
-  const int64_t ld0 = round_up(n, al);
-  void *k0 = nullptr, *post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
-  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));
-  double quad[48], logdet = 0.0, tot = 0.0;
-  int info = 0;
-  SMN_TRY(factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, ld0, q, n, y_d, eps_abs, alpha,
-                               ninv, ld0, quad, &logdet, &info, c));
-  for (int64_t k = 0; k < c; ++k) tot += quad[k];
-  if (info != 0) tot = std::nan("");
-  if (quad_h) *quad_h = tot;
-  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = quad[k];
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
-  if (info != 0) {
-    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
-    return SMN_OK;
-  }
-  double coef = 1.0;
-  if (df > 0.0) coef = (df + (double)n * (double)c) / ((df + tot / scale) * scale);
-  return smn_lml_grad_terms_multi(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, n, ld0, q, ninv, ld0, alpha, c,
-                                  coef, terms_h);
+  return spr_loss_grad(ctx, "smn_spr_loss_grad_multi", true, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx,
+                       d, y_d, c, eps_abs, df, scale, quad_h, quad_cols_h, logdet_h, info_h, terms_h);
 }
 
-// Fused: K0 = X X^T / d and its diagonal, K by the stand-alone recursion straight into the factorisation workspace
-// laid out as the rectangle [[K~], [I], [y^T]], a no-Schur factorisation (L, L^-T, L^-1 y), -K~^-1 = -L^-T L^-1 as one
-// full-rate launch, alpha = L^-T (L^-1 y) (heads.hip factor_with_identity), then the contraction.
 extern "C" int smn_spr_loss_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std,
                                  double b_std, double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d,
                                  const void* y_d, double eps_abs, double df, double scale, double* quad_h,
                                  double* logdet_h, int* info_h, double terms_h[4]) {
-  if (!ctx || !x_d || !y_d || !terms_h) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad: empty");
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad: scale must be > 0");
-  SMN_CHECK_LD(ctx, "smn_spr_loss_grad", ldx, d);
-  const size_t es = dtype_size(dtype);
-  const int64_t al = 16 / (int64_t)es;
-  const int64_t ld0 = round_up(n, al);
-  void *k0 = nullptr, *post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n), &post));
-  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));   // (lower tiles: all the recursion and the contraction read)
-  double quad = 0.0, logdet = 0.0;
-  int info = 0;
-  SMN_TRY(factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, ld0, q, n, y_d, eps_abs, alpha,
-                               ninv, ld0, &quad, &logdet, &info));
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
-  if (info != 0) {
-    for (int i = 0; i < 4; ++i) terms_h[i] = std::nan("");
-    return SMN_OK;
-  }
-  double coef = 1.0;
-  if (df > 0.0) coef = (df + (double)n) / ((df + quad / scale) * scale);
-  return smn_lml_grad_terms(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, n, ld0, q, ninv, ld0, alpha,
-                            coef, terms_h);
+  return spr_loss_grad(ctx, "smn_spr_loss_grad", false, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d,
+                       y_d, 1, eps_abs, df, scale, quad_h, nullptr, logdet_h, info_h, terms_h);
 }
 
 // nprob x smn_spr_loss_grad on one data set (their own w_std, b_std, last_w_std, shift and head) as ONE sequence of launches

@@ -236,67 +236,44 @@ extern "C" int smn_transpose(smn_ctx* ctx, int dtype, void* dst_d, int64_t ldd, 
   return transpose_matrix(ctx, dtype, dst_d, ldd, src_d, lds, rows, cols);
 }
 
-extern "C" int smn_lml(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, double eps_abs,
-                       double df, double scale, double* logpdf_h, double* quad_h, double* logdet_h, int* info_h) {
-  if (!ctx || !k_d || !y_d) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_lml: empty");
-  SMN_CHECK_LD(ctx, "smn_lml", ldk, n);
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml: scale must be > 0");
-  Aug g;
-  SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
-  // only rows >= n (identity padding + appended rows) need clearing: above them just the lower triangle is ever
-  // read (tests: test_cholesky_reads_the_lower_triangle_only), and that is copied in below
-  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-  SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, k_d, ldk, n, n, 1));
-  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-  double quad = 0.0, ld = 0.0;
-  int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
-  if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
-  return SMN_OK;
-}
-
 namespace {
-// the joint head of c target columns from their quadratic forms: total quad, log-pdf in dimension n c with logdet c logdet K~
-void multi_head(const double* quad, int64_t c, double ld, int info, int64_t n, double df, double scale, double* logpdf_h,
-                double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h) {
-  double tot = 0.0;
-  for (int64_t k = 0; k < c; ++k) tot += quad[k];
-  if (info != 0) tot = std::nan("");
-  if (logpdf_h) *logpdf_h = logpdf_from(tot, (double)c * ld, n * c, df, scale, info);
-  if (quad_h) *quad_h = tot;
-  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = info != 0 ? std::nan("") : quad[k];
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
-}
-}  // namespace
-
-// smn_lml for c target columns that share K: one factorisation carrying the c rows Y^T.
-extern "C" int smn_lml_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
-                             double eps_abs, double df, double scale, double* logpdf_h, double* quad_h, double* quad_cols_h,
-                             double* logdet_h, int* info_h) {
+// smn_lml / smn_lml_multi: one factorisation carrying the c rows Y^T of target columns that share K.
+int lml_entry(smn_ctx* ctx, const char* who, bool multi, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
+              double eps_abs, double df, double scale, double* logpdf_h, double* quad_h, double* quad_cols_h, double* logdet_h,
+              int* info_h) {
   if (!ctx || !k_d || !y_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
-  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: bad sizes");
-  SMN_CHECK_LD(ctx, "smn_lml_multi", ldk, n);
-  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_lml_multi: more than 48 output columns");
-  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_multi: scale must be > 0");
+  if (n <= 0 || c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: %s", who, multi ? "bad sizes" : "empty");
+  SMN_CHECK_LD(ctx, who, ldk, n);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
+  if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
+  // only rows >= n (identity padding + appended rows) need clearing: above them just the lower triangle is ever
+  // read (tests: test_cholesky_reads_the_lower_triangle_only), and that is copied in below
   SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
   SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, k_d, ldk, n, n, 1));
   SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
   double quad[48], ld = 0.0;
   int info = 0;
   SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
-  multi_head(quad, c, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
+  publish_head(quad, c, multi, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
+}
+}  // namespace
+
+extern "C" int smn_lml(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, double eps_abs,
+                       double df, double scale, double* logpdf_h, double* quad_h, double* logdet_h, int* info_h) {
+  return lml_entry(ctx, "smn_lml", false, dtype, k_d, n, ldk, y_d, 1, eps_abs, df, scale, logpdf_h, quad_h, nullptr, logdet_h,
+                   info_h);
+}
+
+extern "C" int smn_lml_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
+                             double eps_abs, double df, double scale, double* logpdf_h, double* quad_h, double* quad_cols_h,
+                             double* logdet_h, int* info_h) {
+  return lml_entry(ctx, "smn_lml_multi", true, dtype, k_d, n, ldk, y_d, c, eps_abs, df, scale, logpdf_h, quad_h, quad_cols_h,
+                   logdet_h, info_h);
 }
 
 // smn_lml fed straight from the gathered paired lower-block staging buffer (multi-GPU path): the blocks are
@@ -622,6 +599,52 @@ int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hidd
   return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, c);
 }
 
+namespace {
+// The storage of a Posterior, in today's order of allocations: workspace slot 5 as k0 | q (with_gram), then -K~^-1 | alpha in the
+// caller's buffers or in slot 7 carved with ld0.  The slots only grow: sizes and order are part of what a context allocates.
+int posterior_storage(smn_ctx* ctx, int dtype, int64_t n, int64_t c, bool with_gram, Posterior* p, void* ninv_d = nullptr,
+                      int64_t ldinv = 0, void* alpha_d = nullptr) {
+  const size_t es = dtype_size(dtype);
+  p->ld0 = round_up(n, 16 / (int64_t)es);
+  if (with_gram) {
+    SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * p->ld0 + (size_t)n), &p->k0));
+    p->q = static_cast<char*>(p->k0) + es * (size_t)n * p->ld0;
+  }
+  p->ninv = ninv_d; p->ldinv = ldinv; p->alpha = alpha_d;
+  if (ninv_d) return SMN_OK;
+  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * p->ld0 + (size_t)n * (size_t)c), &p->ninv));
+  p->ldinv = p->ld0;
+  p->alpha = static_cast<char*>(p->ninv) + es * (size_t)n * p->ld0;
+  return SMN_OK;
+}
+}  // namespace
+
+int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
+                     void* ninv_d, int64_t ldinv, void* alpha_d) {
+  SMN_TRY(posterior_storage(ctx, dtype, n, c, true, p, ninv_d, ldinv, alpha_d));
+  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, p->k0, p->ld0, p->q));   // (lower tiles: all the recursion and the contraction read)
+  return factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, p->k0, p->ld0, p->q, n, y_d, eps_abs,
+                              p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info, c);
+}
+
+int posterior_from_build(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c, double eps_abs,
+                         Posterior* p) {
+  SMN_TRY(posterior_storage(ctx, dtype, n, c, false, p));
+  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info,
+                                    c);
+}
+
+int posterior_from_images(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                          const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c, double eps_abs,
+                          Posterior* p) {
+  const KernelInto build = [&](void* k_d, int64_t ldk) {
+    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER, k_d,
+                          ldk);
+  };
+  return posterior_from_build(ctx, dtype, n, build, y_d, c, eps_abs, p);
+}
+
 int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,
                   double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov, double* quad_h,
                   double* logdet_h, int* info_h) {
@@ -700,7 +723,7 @@ extern "C" int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int
   int info = 0;
   SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built));
   SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
-  multi_head(quad, c, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
+  publish_head(quad, c, true, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
 }
 

@@ -1,5 +1,6 @@
 // internal.hpp — C++-side interfaces between the translation units of libsmnngp.so.
 #pragma once
+#include <cmath>
 #include <functional>
 
 #include "common.hpp"
@@ -136,6 +137,54 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
                                int64_t c = 1);
 // Gaussian / multivariate-t log-pdf from (quad = y^T cov^-1 y, logdet = log det cov) in dimension n (heads.hip)
 double logpdf_from(double quad, double logdet, int64_t n, double df, double scale, int info);
+// The joint head of c target columns from their quadratic forms, published to whichever outputs the caller wants: total quad,
+// log-pdf in dimension n c with logdet c logdet K~, the per-column quads, logdet, info, and NaN terms when the matrix was not
+// positive definite.  Returns the total.  A single-output entry (multi = false) publishes its one quadratic form as it is:
+// 0.0 + quad would turn a -0.0 into +0.0.
+inline double publish_head(const double* quad, int64_t c, bool multi, double ld, int info, int64_t n, double df, double scale,
+                           double* logpdf_h, double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h,
+                           double* terms_h = nullptr) {
+  double tot = quad[0];
+  if (multi) {
+    tot = 0.0;
+    for (int64_t k = 0; k < c; ++k) tot += quad[k];
+  }
+  if (info != 0) tot = std::nan("");
+  if (logpdf_h) *logpdf_h = logpdf_from(tot, (double)c * ld, n * c, df, scale, info);
+  if (quad_h) *quad_h = tot;
+  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = info != 0 ? std::nan("") : quad[k];
+  if (logdet_h) *logdet_h = ld;
+  if (info_h) *info_h = info;
+  for (int i = 0; i < 4 && terms_h && info != 0; ++i) terms_h[i] = std::nan("");
+  return tot;
+}
+// coef of the Student-t head of c columns, G = coef A A^T - c K~^-1: (df + n c) / ((df + Q / s) s), Q = the total quadratic
+// form; 1 for the Gaussian head.  Operation by operation the expression the device-side grad_coef (grad.hip) repeats.
+inline double lml_coef(double df, double scale, double quad_total, int64_t n, int64_t c) {
+  if (!(df > 0.0)) return 1.0;
+  return (df + (double)n * (double)c) / ((df + quad_total / scale) * scale);
+}
+// The factored posterior every gradient, leave-one-out and K~^-1 entry starts from: alpha = K~^-1 Y [n, c] row-major and -K~^-1
+// (lower triangle, ld = ldinv) in workspace slot 7 -- or in the caller's buffers --, the c quadratic forms, logdet K~ and info
+// (NaN in quad and logdet when info != 0).  The MLP / dense-ResNet builder also leaves the Gram matrix k0 = x x^T / d (ld = ld0)
+// and its diagonal q in slot 5: what the tangent pass of grad.hip reads.  A new objective adds a tail behind one of these, a new
+// kernel family a builder beside them; neither copies the pipeline.
+struct Posterior {
+  void* k0 = nullptr; void* q = nullptr; int64_t ld0 = 0;
+  void* ninv = nullptr; int64_t ldinv = 0; void* alpha = nullptr;
+  double quad[48]; double logdet = 0.0; int info = 0;
+};
+// from x [n, d]: gram_lower + factor_with_identity.  ninv_d / alpha_d: the caller's storage (ld = ldinv) instead of slot 7.
+int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
+                     void* ninv_d = nullptr, int64_t ldinv = 0, void* alpha_d = nullptr);
+// from K written by `build` into the factorisation workspace (factor_built_with_identity)
+int posterior_from_build(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c, double eps_abs,
+                         Posterior* p);
+// from images x [n, H, W, C] under get_cnn_kernel: the lower build of smn_kernel_cnn
+int posterior_from_images(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                          const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c, double eps_abs,
+                          Posterior* p);
 // true from the size on at which the gradient takes the rectangle route instead of the joint factorisation (heads.hip)
 bool grad_uses_rectangle(int64_t n);
 int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info);

@@ -446,6 +446,17 @@ int loo_zero_alpha(smn_ctx* ctx, int dtype, int64_t n, int64_t c, void** zeros) 
   return SMN_OK;
 }
 
+// What the two gradient entries do between the factored posterior and their tangent pass: info out; NaN in every output when K~
+// did not factor (*zeros stays null: no tangent pass); else the head with its seed written over -K~^-1, and the zero alpha
+int loo_seed(smn_ctx* ctx, int dtype, const Posterior& p, const void* y_d, int64_t n, int64_t c, double df, double scale,
+             double* lam_h, double* dhead_h, int* info_h, double* terms_h, void* mean, void* scale2, void** zeros) {
+  *zeros = nullptr;
+  if (info_h) *info_h = p.info;
+  if (p.info != 0) return loo_all_nan(ctx, dtype, n, c, lam_h, mean, scale2, dhead_h, terms_h, nullptr, 0);
+  SMN_TRY(loo_head(ctx, dtype, p.ninv, p.ldinv, p.alpha, y_d, n, c, df, scale, lam_h, mean, scale2, dhead_h, p.ninv, p.ldinv));
+  return loo_zero_alpha(ctx, dtype, n, c, zeros);
+}
+
 }  // namespace
 
 extern "C" int smn_loo_head(smn_ctx* ctx, int dtype, const void* neg_kinv_d, int64_t ldkinv, const void* alpha_d, const void* y_d,
@@ -468,20 +479,14 @@ extern "C" int smn_loo_multi(smn_ctx* ctx, int dtype, void* k_d, int64_t n, int6
   SMN_TRY(loo_check(ctx, "smn_loo_multi", dtype, n, c, df, scale));
   SMN_CHECK_LD(ctx, "smn_loo_multi", ldk, n);
   if (g_d) SMN_CHECK_LD(ctx, "smn_loo_multi", ldg, n);
-  const size_t es = dtype_size(dtype);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void* post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  double quad[48], logdet = 0.0;
-  int info = 0;
   const KernelInto build = [&](void* w_d, int64_t ldw) { return copy_matrix(ctx, dtype, w_d, ldw, k_d, ldk, n, n, 1); };
-  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, quad, &logdet, &info, c));
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
-  if (info != 0) return loo_all_nan(ctx, dtype, n, c, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, nullptr, g_d, ldg);
-  return loo_head(ctx, dtype, ninv, ld0, alpha, y_d, n, c, df, scale, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, g_d, ldg);
+  Posterior p;
+  SMN_TRY(posterior_from_build(ctx, dtype, n, build, y_d, c, eps_abs, &p));
+  if (logdet_h) *logdet_h = p.logdet;
+  if (info_h) *info_h = p.info;
+  if (p.info != 0) return loo_all_nan(ctx, dtype, n, c, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, nullptr, g_d, ldg);
+  return loo_head(ctx, dtype, p.ninv, p.ldinv, p.alpha, y_d, n, c, df, scale, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, g_d,
+                  ldg);
 }
 
 // Everything from x and Y [n,c] for the MLP / dense-ResNet kernels: Gram matrix, factorisation with identity (heads.hip: both
@@ -495,26 +500,13 @@ extern "C" int smn_spr_loo_grad(smn_ctx* ctx, int dtype, int net, int act, int n
   SMN_TRY(loo_check(ctx, "smn_spr_loo_grad", dtype, n, c, df, scale));
   if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loo_grad: bad sizes");
   SMN_CHECK_LD(ctx, "smn_spr_loo_grad", ldx, d);
-  const size_t es = dtype_size(dtype);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void *k0 = nullptr, *post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
-  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));
-  double quad[48], logdet = 0.0;
-  int info = 0;
-  SMN_TRY(factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, ld0, q, n, y_d, eps_abs, alpha,
-                               ninv, ld0, quad, &logdet, &info, c));
-  if (info_h) *info_h = info;
-  if (info != 0) return loo_all_nan(ctx, dtype, n, c, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, terms_h, nullptr, 0);
-  SMN_TRY(loo_head(ctx, dtype, ninv, ld0, alpha, y_d, n, c, df, scale, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, ninv, ld0));
+  Posterior p;
+  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p));
   void* zeros = nullptr;
-  SMN_TRY(loo_zero_alpha(ctx, dtype, n, c, &zeros));
-  return smn_lml_grad_terms(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, n, ld0, q, ninv, ld0, zeros, 0.0,
-                            terms_h);
+  SMN_TRY(loo_seed(ctx, dtype, p, y_d, n, c, df, scale, loo_logpdf_h, dhead_h, info_h, terms_h, loo_mean_d, loo_scale2_d, &zeros));
+  if (!zeros) return SMN_OK;
+  return smn_lml_grad_terms(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, p.k0, n, p.ld0, p.q, p.ninv, p.ldinv,
+                            zeros, 0.0, terms_h);
 }
 
 // The same for get_cnn_kernel: the conv build of the lower triangle straight into the factorisation workspace, and the
@@ -530,26 +522,13 @@ extern "C" int smn_spr_cnn_loo_grad(smn_ctx* ctx, int dtype, int act, int num_hi
   if (H * W > SMN_CNN_GRAD_MAX_PIXELS)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_cnn_loo_grad: images of more than %d pixels", SMN_CNN_GRAD_MAX_PIXELS);
   if (!(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loo_grad: bad hyper-parameters");
-  const size_t es = dtype_size(dtype);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void* post = nullptr;
-  SMN_TRY(smn_workspace(ctx, 7, es * ((size_t)n * ld0 + (size_t)n * (size_t)c), &post));
-  void* ninv = post;
-  void* alpha = static_cast<char*>(post) + es * (size_t)n * ld0;
-  double quad[48], logdet = 0.0;
-  int info = 0;
-  const KernelInto build = [&](void* k_d, int64_t ldk) {
-    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER,
-                          k_d, ldk);
-  };
-  SMN_TRY(factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha, ninv, ld0, quad, &logdet, &info, c));
-  if (info_h) *info_h = info;
-  if (info != 0) return loo_all_nan(ctx, dtype, n, c, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, terms_h, nullptr, 0);
-  SMN_TRY(loo_head(ctx, dtype, ninv, ld0, alpha, y_d, n, c, df, scale, loo_logpdf_h, loo_mean_d, loo_scale2_d, dhead_h, ninv, ld0));
+  Posterior p;
+  SMN_TRY(posterior_from_images(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, y_d, c, eps_abs, &p));
   void* zeros = nullptr;
-  SMN_TRY(loo_zero_alpha(ctx, dtype, n, c, &zeros));
-  return smn_kernel_cnn_grad_terms(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, ninv, ld0, zeros, 0.0,
-                                   terms_h);
+  SMN_TRY(loo_seed(ctx, dtype, p, y_d, n, c, df, scale, loo_logpdf_h, dhead_h, info_h, terms_h, loo_mean_d, loo_scale2_d, &zeros));
+  if (!zeros) return SMN_OK;
+  return smn_kernel_cnn_grad_terms(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, p.ninv, p.ldinv, zeros,
+                                   0.0, terms_h);
 }
 
 // -K~^-1 and A = K~^-1 Y exactly as the gradient entries form them (Gram matrix, layer recursion, factorisation with identity:
@@ -568,16 +547,10 @@ extern "C" int smn_spr_kinv(smn_ctx* ctx, int dtype, int net, int act, int num_h
   SMN_CHECK_LD(ctx, "smn_spr_kinv", ldkinv, n);
   if (ldkinv % (16 / (int64_t)es))
     return smn_fail(ctx, SMN_EINVAL, "smn_spr_kinv: ldkinv = %lld is not a multiple of 16 bytes", (long long)ldkinv);
-  const int64_t ld0 = round_up(n, 16 / (int64_t)es);
-  void* k0 = nullptr;
-  SMN_TRY(smn_workspace(ctx, 5, es * ((size_t)n * ld0 + (size_t)n), &k0));
-  void* q = static_cast<char*>(k0) + es * (size_t)n * ld0;
-  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, k0, ld0, q));
-  double quad[48], logdet = 0.0;
-  int info = 0;
-  SMN_TRY(factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0, ld0, q, n, y_d, eps_abs, alpha_d,
-                               neg_kinv_d, ldkinv, quad, &logdet, &info, c));
-  if (logdet_h) *logdet_h = logdet;
-  if (info_h) *info_h = info;
+  Posterior p;
+  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p,
+                           neg_kinv_d, ldkinv, alpha_d));
+  if (logdet_h) *logdet_h = p.logdet;
+  if (info_h) *info_h = p.info;
   return SMN_OK;
 }

@@ -61,6 +61,13 @@ def grad_route(kernel_fn, likelihood):
                               "a Gaussian or Student-t likelihood; use train.value_and_grad_fd")
 
 
+def _raw_grads(model, d_con, divisor=1.0):
+    """{variable name: d / d RAW value} from d_con = {key: (variable, d / d constrained value)}: the chain rule through each
+    variable's constraint, over `divisor` (-N turns a log-pdf into the exact models' loss)."""
+    names = {id(v): k for k, v in model.vars().items()}
+    return {names[id(var)]: float(g / divisor * var.constraint.grad(var.value)) for var, g in d_con.values()}
+
+
 class _LooMixin:
     """Leave-one-out cross-validation (Rasmussen & Williams 5.4.2) for the exact models: how would the model have predicted
     training point i had it not seen it?  Closed forms on K~^-1 and A = K~^-1 Y, which every gradient call already leaves on
@@ -115,46 +122,19 @@ class _LooMixin:
         (d Lambda = sum_ij G_ij dK~_ij; one N^3 product on the MFMA tile engine) and the tangent pass of loss_and_grad over G
         (smn_spr_loo_grad / smn_spr_cnn_loo_grad).  Follows grad_route: the conv ResNet, a likelihood without lml_params and
         images above 1024 pixels raise NotImplementedError."""
-        kernel_fn = self.kernel.get_kernel_fn()
-        mlp = grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad"
-        eps = self.eps.safe_value
-        df, scale = self.likelihood.lml_params()
-        x, ctx = self.x_data, self.x_data.ctx
+        grad_route(self.kernel.get_kernel_fn(), self.likelihood)   # what has no analytic gradient raises before anything else
         n, c = self._loo_shape()
         lam, info = C.c_double(), C.c_int()
         terms, dhead = (C.c_double * 4)(), (C.c_double * 2)()
-        if mlp:
-            net, act, L, w, b, lw = kernel_fn.params
-            ctx.call("smn_spr_loo_grad", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1], self.y_data.ptr, c,
-                     eps, df, scale, C.byref(lam), dhead, C.byref(info), terms, None, None)
-        else:
-            if len(x.shape) != 4:
-                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
-            act, L, w, b, lw = kernel_fn.params
-            try:
-                ctx.call("smn_spr_cnn_loo_grad", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2], x.shape[3],
-                         self.y_data.ptr, c, eps, df, scale, C.byref(lam), dhead, C.byref(info), terms, None, None)
-            except _lib.SmnError as e:
-                if e.code == _lib.ENOTSUP and c <= 48:        # images above the tangent kernel's limit
-                    raise NotImplementedError(str(e)) from e
-                raise
-        nan = float("nan")
+        df, _ = self._call_grad_entry("loo_grad", c, (C.byref(lam), dhead, C.byref(info), terms, None, None))
         if info.value != 0:
-            return nan, {k: nan for k in self.vars()}
+            return self._nan_grads()
         dlam = dict(zip(("w_std", "b_std", "last_w_std", "eps"), terms))   # d Lambda / d constrained value
-        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
-                  "eps": self.eps}
         if df > 0.0:
             a_, b_ = self.likelihood.a.safe_value, self.likelihood.b.safe_value
             dlam["a"] = 2.0 * dhead[0] - dhead[1] * b_ / (a_ * a_)      # df = 2a, scale = b/a
             dlam["b"] = dhead[1] / a_
-            owners.update(a=self.likelihood.a, b=self.likelihood.b)
-        names = {id(v): k for k, v in self.vars().items()}
-        grads = {}
-        for key, g in dlam.items():
-            var = owners[key]
-            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
-        return -lam.value / n, grads
+        return -lam.value / n, self._raw_grads(dlam, -n)
 
 
 class _DrawsMixin:
@@ -220,7 +200,77 @@ class _DrawsMixin:
         return out
 
 
-class SPR(_DrawsMixin, _LooMixin, Module):
+class _ExactGP(_DrawsMixin, _LooMixin, Module):
+    """What SPR and MultiSPR share around the fused gradient entries (csrc/grad.hip, cnn_grad.hip, loo.hip): which entry a
+    kernel function takes, its argument list, the errors it translates, and the host chain rule behind it."""
+
+    _multi = False                                            # MultiSPR: the *_multi entries, whatever its C
+
+    def _f64_data(self):
+        if self.x_data.dtype == np.float64:
+            return self.x_data, self.y_data
+        if getattr(self, "_x64", None) is None:
+            ctx = self.x_data.ctx
+            self._x64 = ctx.to_device(self.x_data.numpy().astype(np.float64))
+            self._y64 = ctx.to_device(self.y_host)
+        return self._x64, self._y64
+
+    def _call_grad_entry(self, kind, c, outs):
+        """One fused entry on the training data, "smn_spr_" + kind (MLP / dense ResNet) or "smn_spr_cnn_" + kind
+        (get_cnn_kernel) as grad_route decides: (x, y, [c unless None,] eps, df, scale, *outs).  Returns (df, scale)."""
+        kernel_fn = self.kernel.get_kernel_fn()
+        mlp = grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad"
+        eps = self.eps.safe_value
+        df, scale = self.likelihood.lml_params()
+        x, ctx = self.x_data, self.x_data.ctx
+        if mlp:
+            name, data = "smn_spr_" + kind, (x.ptr, self.num_data, x.shape[1], x.shape[1])
+        else:
+            if len(x.shape) != 4:
+                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+            name, data = "smn_spr_cnn_" + kind, (x.ptr, self.num_data, x.shape[1], x.shape[2], x.shape[3])
+        args = (x.dcode, *kernel_fn.params, *data, self.y_data.ptr) + (() if c is None else (c,)) + (eps, df, scale) + outs
+        try:
+            ctx.call(name, *args)
+        except _lib.SmnError as e:
+            if not mlp and e.code == _lib.ENOTSUP and (c or 1) <= 48:   # images above the tangent kernel's limit
+                raise NotImplementedError(str(e)) from e
+            raise
+        return df, scale
+
+    def _nan_grads(self):
+        """(loss, gradients) when the kernel matrix is not positive definite."""
+        nan = float("nan")
+        return nan, {k: nan for k in self.vars()}
+
+    def _raw_grads(self, d_con, divisor):
+        """_raw_grads for d_con = {"w_std" | "b_std" | "last_w_std" | "eps" | "a" | "b": d / d constrained value}."""
+        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
+                  "eps": self.eps}
+        if "a" in d_con:
+            owners.update(a=self.likelihood.a, b=self.likelihood.b)
+        return _raw_grads(self, {key: (owners[key], g) for key, g in d_con.items()}, divisor)
+
+    def _lml_loss_and_grad(self):
+        """loss_and_grad of both models: the head in dimension N C with log-determinant C logdet K~."""
+        n, c = self._loo_shape()
+        quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
+        terms = (C.c_double * 4)()
+        if self._multi:
+            outs = (C.byref(quad), None, C.byref(logdet), C.byref(info), terms)
+            df, scale = self._call_grad_entry("loss_grad_multi", c, outs)
+        else:
+            df, scale = self._call_grad_entry("loss_grad", None, (C.byref(quad), C.byref(logdet), C.byref(info), terms))
+        if info.value != 0:
+            return self._nan_grads()
+        student = df > 0.0
+        lp, dlp = lml_value_and_grads(terms, quad.value, c * logdet.value, n * c, df, scale,
+                                      self.likelihood.a.safe_value if student else None,
+                                      self.likelihood.b.safe_value if student else None)
+        return -lp / n, self._raw_grads(dlp, -n)
+
+
+class SPR(_ExactGP):
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, eps: float = 1e-6):
         super().__init__()
         self.kernel = kernel
@@ -232,15 +282,6 @@ class SPR(_DrawsMixin, _LooMixin, Module):
         self.y_std = float(np.asarray(y_std))
         self.num_data = self.x_data.shape[0]
         self.eps = ConstraintTrainVar(eps, constraint=positive())
-
-    def _f64_data(self):
-        if self.x_data.dtype == np.float64:
-            return self.x_data, self.y_data
-        if getattr(self, "_x64", None) is None:
-            ctx = self.x_data.ctx
-            self._x64 = ctx.to_device(self.x_data.numpy().astype(np.float64))
-            self._y64 = ctx.to_device(self.y_host)
-        return self._x64, self._y64
 
     def _student_quad_f64(self, kernel_fn, scale):
         """y^T (K + (1e-6 / scale) I)^-1 y / scale  =  y^T (scale K + 1e-6 I)^-1 y in fp64 (likelihoods.py:60-61).
@@ -298,46 +339,7 @@ class SPR(_DrawsMixin, _LooMixin, Module):
         pairs for get_cnn_kernel (csrc/cnn_grad.hip, images of up to 1024 pixels).  The (a, b) derivatives of the
         Student-t head and the softplus chain rule are closed forms on the host (lml_value_and_grads).  Anything else --
         the conv ResNet, a likelihood without lml_params, larger images -- raises NotImplementedError."""
-        kernel_fn = self.kernel.get_kernel_fn()
-        mlp = grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad"
-        eps = self.eps.safe_value
-        df, scale = self.likelihood.lml_params()
-        x, ctx = self.x_data, self.x_data.ctx
-        n = self.num_data
-        quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
-        terms = (C.c_double * 4)()
-        if mlp:
-            net, act, L, w, b, lw = kernel_fn.params
-            ctx.call("smn_spr_loss_grad", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1],
-                     self.y_data.ptr, eps, df, scale, C.byref(quad), C.byref(logdet), C.byref(info), terms)
-        else:
-            if len(x.shape) != 4:
-                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
-            act, L, w, b, lw = kernel_fn.params
-            try:
-                ctx.call("smn_spr_cnn_loss_grad", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2], x.shape[3],
-                         self.y_data.ptr, eps, df, scale, C.byref(quad), C.byref(logdet), C.byref(info), terms)
-            except _lib.SmnError as e:
-                if e.code == _lib.ENOTSUP:                    # images above the tangent kernel's limit
-                    raise NotImplementedError(str(e)) from e
-                raise
-        nan = float("nan")
-        if info.value != 0:
-            return nan, {k: nan for k in self.vars()}
-        student = df > 0.0
-        lp, dlp = lml_value_and_grads(terms, quad.value, logdet.value, n, df, scale,
-                                      self.likelihood.a.safe_value if student else None,
-                                      self.likelihood.b.safe_value if student else None)
-        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
-                  "eps": self.eps}
-        if student:
-            owners.update(a=self.likelihood.a, b=self.likelihood.b)
-        names = {id(v): k for k, v in self.vars().items()}
-        grads = {}
-        for key, g in dlp.items():
-            var = owners[key]
-            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
-        return -lp / n, grads
+        return self._lml_loss_and_grad()
 
     # ---- spax/models.py:100-120
     def test_nll(self, x, y):
@@ -378,7 +380,7 @@ def multi_grad_route(kernel_fn, likelihood):
     return grad_route(kernel_fn, likelihood) + "_multi"
 
 
-class MultiSPR(_DrawsMixin, _LooMixin, Module):
+class MultiSPR(_ExactGP):
     """Exact GP / Student-t process with C outputs over ONE kernel matrix: y_data [N,C], K~ = K(x,x) + eps I.
 
     Gaussian likelihood: the C columns are independent GPs that share K~ (the log-pdf is the sum of C
@@ -391,6 +393,8 @@ class MultiSPR(_DrawsMixin, _LooMixin, Module):
     Trainables and their names are SPR's (kernel.w_std, kernel.b_std, kernel.last_w_std, eps, likelihood.a / .b), so
     train.train_vars, train.build_train_step and the checkpoint reader work on it unchanged.  Classification: targets
     onehot(labels) - 1/C (from_labels), the predicted class is the arg-max of the posterior mean (classify, accuracy)."""
+
+    _multi = True
 
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean=0., y_std=1., *, eps: float = 1e-6):
         super().__init__()
@@ -430,15 +434,6 @@ class MultiSPR(_DrawsMixin, _LooMixin, Module):
             raise NotImplementedError("MultiSPR needs a Gaussian or Student-t likelihood")
         return self.likelihood.lml_params()
 
-    def _f64_data(self):
-        if self.x_data.dtype == np.float64:
-            return self.x_data, self.y_data
-        if getattr(self, "_x64", None) is None:
-            ctx = self.x_data.ctx
-            self._x64 = ctx.to_device(self.x_data.numpy().astype(np.float64))
-            self._y64 = ctx.to_device(self.y_host)
-        return self._x64, self._y64
-
     def _joint_lml(self, kernel_fn, x, y, eps, df, scale):
         """(log-pdf, total quadratic form, info) of y [N,C] under K(x,x) + eps I: the fused build for the MLP family, the
         conv build followed by smn_lml_multi for the conv kernels."""
@@ -468,47 +463,7 @@ class MultiSPR(_DrawsMixin, _LooMixin, Module):
         G = coef A A^T - C K~^-1 with the forward-mode dK/d(w_std, b_std, last_w_std) (csrc/grad.hip, csrc/cnn_grad.hip), and
         lml_value_and_grads supplies the head in dimension N C with log-determinant C logdet K~.  The conv ResNet, a
         likelihood without lml_params and images above 1024 pixels raise NotImplementedError."""
-        kernel_fn = self.kernel.get_kernel_fn()
-        mlp = multi_grad_route(kernel_fn, self.likelihood) == "smn_spr_loss_grad_multi"
-        eps = self.eps.safe_value
-        df, scale = self.likelihood.lml_params()
-        x, ctx = self.x_data, self.x_data.ctx
-        n, c = self.num_data, self.num_outputs
-        quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
-        terms = (C.c_double * 4)()
-        if mlp:
-            net, act, L, w, b, lw = kernel_fn.params
-            ctx.call("smn_spr_loss_grad_multi", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1],
-                     self.y_data.ptr, c, eps, df, scale, C.byref(quad), None, C.byref(logdet), C.byref(info), terms)
-        else:
-            if len(x.shape) != 4:
-                raise ValueError("conv kernel expects x of shape [N,H,W,C]")
-            act, L, w, b, lw = kernel_fn.params
-            try:
-                ctx.call("smn_spr_cnn_loss_grad_multi", x.dcode, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[2],
-                         x.shape[3], self.y_data.ptr, c, eps, df, scale, C.byref(quad), None, C.byref(logdet),
-                         C.byref(info), terms)
-            except _lib.SmnError as e:
-                if e.code == _lib.ENOTSUP and c <= 48:        # images above the tangent kernel's limit
-                    raise NotImplementedError(str(e)) from e
-                raise
-        nan = float("nan")
-        if info.value != 0:
-            return nan, {k: nan for k in self.vars()}
-        student = df > 0.0
-        lp, dlp = lml_value_and_grads(terms, quad.value, c * logdet.value, n * c, df, scale,
-                                      self.likelihood.a.safe_value if student else None,
-                                      self.likelihood.b.safe_value if student else None)
-        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std,
-                  "eps": self.eps}
-        if student:
-            owners.update(a=self.likelihood.a, b=self.likelihood.b)
-        names = {id(v): k for k, v in self.vars().items()}
-        grads = {}
-        for key, g in dlp.items():
-            var = owners[key]
-            grads[names[id(var)]] = float(-g / n * var.constraint.grad(var.value))
-        return -lp / n, grads
+        return self._lml_loss_and_grad()
 
     # predict(x) -> (mean [T,C], cov [T,T]) is _DrawsMixin's, shared with SPR
 
@@ -676,8 +631,7 @@ class SVSP(Module):
                          gbar.ptr, n_u, zeros.ptr, 0.0, terms)
             for i, key_ in enumerate(("w_std", "b_std", "last_w_std")):
                 d_con[key_] = (getattr(self.kernel, key_), terms[i] if info.value == 0 else float("nan"))
-        for var, g in d_con.values():
-            grads[names[id(var)]] = float(g * var.constraint.grad(var.value))
+        grads.update(_raw_grads(self, d_con))
         if inducing_grad:
             if info.value == 0:
                 act, depth, w, b_, lw = kernel_fn.params

@@ -465,3 +465,28 @@ def test_rectangle_route_carries_the_columns(L, ctx):
     q1, qc1, ld1, t1 = multi(ctx.to_device(np.ascontiguousarray(yh[:, :1])), 1)
     assert abs(q1 - singles[0][0]) <= 1e-12 * q1 and abs(ld1 - singles[0][1]) <= 1e-12 * abs(ld1)
     assert np.all(np.abs(t1 - singles[0][2]) <= 1e-12 * np.abs(singles[0][2]))
+
+
+# ------------------------------------------------------ the fused entries start from one factored posterior (heads.hip)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fused_entries_share_one_factorisation(L, ctx, dtype):
+    """n = 129, d = 5, MLP-ReLU with two layers, eps_abs = 0.1: smn_spr_loss_grad, smn_spr_loss_grad_multi (c = 1),
+    smn_spr_kinv (c = 1) and smn_spr_loo_grad (c = 1) all build the same K~ and factor it with the same identity block, so
+    what each of them reports of that factorisation -- quad, logdet, info -- is the same bits."""
+    rng = np.random.default_rng(129)
+    n, d, ld = 129, 5, 132
+    x, y = ctx.to_device(rng.standard_normal((n, d)).astype(dtype)), ctx.to_device(rng.standard_normal(n).astype(dtype))
+    args = (L.dtype_code(np.dtype(dtype)), L.NET_MLP, L.ACT["relu"], 2, 1.3, 0.4, 0.9, x.ptr, n, d, d, y.ptr)
+    quad, logdet, info = [C.c_double() for _ in range(2)], [C.c_double() for _ in range(3)], [C.c_int(-1) for _ in range(4)]
+    terms, dhead, lam = (C.c_double * 4)(), (C.c_double * 2)(), C.c_double()
+    ctx.call("smn_spr_loss_grad", *args, 0.1, 0.0, 1.0, C.byref(quad[0]), C.byref(logdet[0]), C.byref(info[0]), terms)
+    ctx.call("smn_spr_loss_grad_multi", *args, 1, 0.1, 0.0, 1.0, C.byref(quad[1]), None, C.byref(logdet[1]), C.byref(info[1]),
+             terms)
+    ninv, alpha = ctx.empty((n, ld), dtype), ctx.empty((n, 1), dtype)
+    ctx.call("smn_spr_kinv", *args, 1, 0.1, ninv.ptr, ld, alpha.ptr, C.byref(logdet[2]), C.byref(info[2]))
+    ctx.call("smn_spr_loo_grad", *args, 1, 0.1, 0.0, 1.0, C.byref(lam), dhead, C.byref(info[3]), terms, None, None)
+    print("quad", [q.value for q in quad], "logdet", [v.value for v in logdet], "info", [i.value for i in info])
+    assert info[0].value == 0 and np.isfinite(quad[0].value) and np.isfinite(logdet[0].value)
+    assert quad[1].value == quad[0].value and logdet[1].value == logdet[0].value and info[1].value == info[0].value
+    assert logdet[2].value == logdet[0].value and info[2].value == info[0].value
+    assert info[3].value == info[0].value
