@@ -2,7 +2,10 @@
 """The reference's regression experiment (experiments/regression/train.py + test.py) on its two offline datasets,
 run on the device path.  Not a CLI replica: a short script that shows the drop-in surface end to end.
 
-    python examples/regression_synthetic.py [syn-t|syn-normal] [gp|tp]
+    python examples/regression_synthetic.py [syn-t|syn-normal] [gp|tp] [--kernel {nngp,ntk}]
+
+--kernel ntk trains the same model on the neural tangent kernel of the architecture (spax.kernels.NTKKernel): a GP / Student-t
+process whose covariance function is Theta.  Default: nngp.
 """
 import os
 import sys
@@ -13,7 +16,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from smnngp import checkpoint, nt_kernels, train                      # noqa: E402
-from smnngp.spax.kernels import NNGPKernel                            # noqa: E402
+from smnngp.spax.kernels import NNGPKernel, NTKKernel                 # noqa: E402
 from smnngp.spax.likelihoods import GaussianLikelihood, StudentTLikelihood  # noqa: E402
 from smnngp.spax.models import SPR                                    # noqa: E402
 
@@ -39,11 +42,21 @@ def dataset(name):
 
 
 def main():
-    name = sys.argv[1] if len(sys.argv) > 1 else "syn-t"
-    method = sys.argv[2] if len(sys.argv) > 2 else "tp"
+    argv = list(sys.argv[1:])
+    covariance = "nngp"
+    if "--kernel" in argv:
+        i = argv.index("--kernel")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("nngp", "ntk"):
+            raise SystemExit("--kernel takes nngp or ntk")
+        covariance = argv[i + 1]
+        del argv[i:i + 2]
+    name = argv[0] if len(argv) > 0 else "syn-t"
+    method = argv[1] if len(argv) > 1 else "tp"
     (xtr, ytr), (xva, yva), (xte, yte), (ym, ys) = dataset(name)
     args = dict(method=method, network="mlp", num_hiddens=2, activation="relu", data_name=name, last_w_std=1.0)
-    kernel = NNGPKernel(lambda w, b, l: nt_kernels.get_mlp_kernel(2, act="relu", w_std=w, b_std=b, last_w_std=l), 1.0, 1.0, 1.0)
+    if covariance == "ntk":
+        args["kernel"] = "ntk"                                        # restore_spr rebuilds the model on NTKKernel
+    kernel = (NTKKernel if covariance == "ntk" else NNGPKernel)(lambda w, b, l: nt_kernels.get_mlp_kernel(2, act="relu", w_std=w, b_std=b, last_w_std=l), 1.0, 1.0, 1.0)
     likelihood = GaussianLikelihood() if method == "gp" else StudentTLikelihood(2.0, 2.0)
     model = SPR(kernel, likelihood, xtr, ytr, ym, ys, eps=1e-2)
     step = train.build_train_step(model)                              # analytic gradient + Adam

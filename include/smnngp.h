@@ -47,6 +47,18 @@ enum { SMN_ACT_RELU = 0, SMN_ACT_ERF = 1 };            /* experiments/nt_kernels
 enum { SMN_GET_NNGP = 1, SMN_GET_NTK = 2 };            /* kernel_fn(..., get=) bit mask             */
 enum { SMN_FILL_FULL = 0, SMN_FILL_LOWER = 1 };        /* symmetric build: mirror or lower triangle */
 enum { SMN_NET_MLP = 0, SMN_NET_DENSE_RESNET = 1 };    /* nt_kernels.py:21-31 / :83-103             */
+/* SMN_NET_NTK, OR-ed into the `net` argument (SMN_NET_MLP | SMN_NET_NTK, SMN_NET_DENSE_RESNET | SMN_NET_NTK): the model's
+ * covariance function is the neural tangent kernel Theta instead of the NNGP kernel K -- a GP (or Student-t process) with
+ * K~ = Theta(X,X) + eps I, posterior mean Theta_td Theta~^-1 y and covariance Theta_tt - Theta_td Theta~^-1 Theta_dt.  (This is
+ * not neural_tangents' get="ntk" ensemble covariance, which mixes K and Theta; the two means coincide.)  The gradient entries
+ * then differentiate Theta (csrc/grad.hip).  Entries that take the flag:
+ *   smn_spr_loss, smn_spr_loss_multi, smn_spr_predict,
+ *   smn_spr_loss_grad, smn_spr_loss_grad_multi, smn_lml_grad_terms, smn_lml_grad_terms_multi,
+ *   smn_spr_loo_grad (one entry for every c), smn_spr_kinv.
+ * With the flag smn_spr_loss neither reads nor writes its Gram cache.  The batched and grid entries (smn_spr_loss_batch,
+ * smn_spr_predict_batch, smn_spr_loss_grad_batch) return SMN_ENOTSUP with it; every other entry, and any other bit in `net`,
+ * SMN_EINVAL naming the value. */
+enum { SMN_NET_NTK = 0x100 };
 
 /* ---- context, errors, memory (JAX array semantics: the spax modules never manage memory themselves) ---- */
 int smn_version(void);

@@ -6,7 +6,7 @@ log-marginal-likelihood / predictive mean+variance):
     smnngp.nt_kernels   get_mlp_kernel / get_dense_resnet_kernel / get_cnn_kernel   (experiments/nt_kernels.py)
     smnngp.predict      gradient_descent_mse_ensemble                               (neural_tangents.predict)
     smnngp.spectral     eigh_pd / max_learning_rate                                 (jnp.linalg.eigh, neural_tangents.predict)
-    smnngp.spax         kernels.NNGPKernel, likelihoods.*, models.SPR, utils, bijectors, base   (spax/*)
+    smnngp.spax         kernels.NNGPKernel / NTKKernel, likelihoods.*, models.SPR, utils, bijectors, base   (spax/*)
 
 All arithmetic runs in libsmnngp.so (hand-written HIP for gfx950) through a ctypes C-ABI
 (include/smnngp.h).  There is no CPU fallback: importing ``smnngp._lib`` raises if the library

@@ -19,6 +19,7 @@ ACT = {"relu": 0, "erf": 1}
 GET_NNGP, GET_NTK = 1, 2
 FILL_FULL, FILL_LOWER = 0, 1
 NET_MLP, NET_DENSE_RESNET = 0, 1
+NET_NTK = 0x100   # SMN_NET_NTK: OR-ed into `net`, the model entries then work on Theta instead of K (include/smnngp.h)
 
 
 class SmnError(RuntimeError):

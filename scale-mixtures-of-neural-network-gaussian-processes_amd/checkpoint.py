@@ -129,9 +129,11 @@ def read_run(ckpt_dir, ckpt_index=None):
 
 
 def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtype=np.float32):
-    """experiments/regression/test.py:89-130: rebuild SPR from a run directory and assign the stored raw values."""
+    """experiments/regression/test.py:89-130: rebuild SPR from a run directory and assign the stored raw values.  The
+    run's arguments may carry ``kernel``: "nngp" (the default when absent) or "ntk" for a model built on NTKKernel, whose
+    trainables and names are the same."""
     from . import nt_kernels
-    from .spax.kernels import NNGPKernel
+    from .spax.kernels import NNGPKernel, NTKKernel
     from .spax.likelihoods import GaussianLikelihood, StudentTLikelihood
     from .spax.models import SPR
     raw, context = read_run(ckpt_dir, ckpt_index)
@@ -147,7 +149,10 @@ def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtyp
     def get_kernel_fn(w_std, b_std, last_w_std):
         return base_kernel_fn(num_hiddens, act=activation, w_std=w_std, b_std=b_std, last_w_std=last_w_std)
 
-    kernel = NNGPKernel(get_kernel_fn, 1.0, 1.0, 1.0)
+    covariance = context.get("kernel") or "nngp"
+    if covariance not in ("nngp", "ntk"):
+        raise ValueError("Unsupported kernel '%s'" % covariance)
+    kernel = (NTKKernel if covariance == "ntk" else NNGPKernel)(get_kernel_fn, 1.0, 1.0, 1.0)
     method = context["method"]
     if method == "gp":
         likelihood = GaussianLikelihood()

@@ -100,6 +100,61 @@ __device__ __forceinline__ ActR<R> act_r(R a, R rai, R rbi, R raj, R rbj) {
   return r;
 }
 
+// NTK form: the same maps with the second derivatives of the activation map that the tangent of Theta needs.  D = phi_A is the
+// factor Theta takes per layer (Theta <- T D, T = A + w2 Theta), so  dD = D_A dA + D_1 dq_i + D_2 dq_j:
+//   ReLU: D_A = 1 / (2 pi sqrt(1-c^2) sqrt(q_i q_j)) = ra_i ra_j / (2 pi sqrt(1-c^2)),   D_i = -c / (4 pi q_i sqrt(1-c^2))
+//         = -c ra_i^2 / (4 pi sqrt(1-c^2)).  Where (1-c)(1+c) <= 0 after clamping -- and on the exact diagonal -- D is 1/2
+//         whatever the hyper-parameters (c = 1 identically: the diagonal, exactly duplicate rows): D_A = D_i = 0.
+//   Erf:  R = (1+2q_i)(1+2q_j) - 4A^2 = (1-s^2) / (ra_i ra_j)^2 >= 1 + 4q:   D_A = 16 A / (pi R^(3/2)) = (16/pi) A (uu rden)^3,
+//         D_i = -4 (1+2q_j) / (pi R^(3/2)) = -(4/pi) uu rb_i rden^3,   uu = ra_i ra_j, rden = 1/sqrt(1-s^2).
+// Division-free from the same per-row fields as act_r.
+template <typename R>
+struct ActR2 {
+  R o, dA, d1, d2, hA, h1, h2;
+};
+
+template <int ACT, typename R>
+__device__ __forceinline__ ActR2<R> act_r2(R a, R rai, R rbi, R raj, R rbj, bool diag) {
+  ActR2<R> r;
+  if (ACT == ACT_RELU) {
+    const R uu = rai * raj;
+    // the diagonal: c = 1 exactly (q ra^2 is 1 only to rounding, and asin has no slope to spare there: 1e-16 in c is 1e-8 in D)
+    const R c = diag ? R(1) : nngp::clamp1(a * uu);
+    const R as = nngp::asin_abs(fabs(c), c * c);
+    const R om = (R(1) - c) * (R(1) + c);
+    const bool flat = diag || !(om > R(0));
+    const R s1 = nngp::fast_sqrt(fmax(om, R(0)));
+    const R rs1 = flat ? R(0) : nngp::fast_rsqrt(flat ? R(1) : om);
+    const R pm = R(kPiD / 2) + copysign(as, c);
+    const R sp = rbi * rbj;
+    r.o = sp * fma(pm, c, s1) * R(1.0 / (2.0 * kPiD));
+    r.dA = pm * R(1.0 / (2.0 * kPiD));
+    const R t = s1 * R(1.0 / (4.0 * kPiD));
+    r.d1 = t * (rbj * rai);
+    r.d2 = t * (rbi * raj);
+    r.hA = R(1.0 / (2.0 * kPiD)) * rs1 * uu;
+    const R u = R(-1.0 / (4.0 * kPiD)) * c * rs1;
+    r.h1 = u * (rai * rai);
+    r.h2 = u * (raj * raj);
+  } else {
+    const R uu = rai * raj;
+    const R sv = nngp::clamp1(R(2) * a * uu);
+    const R as = nngp::asin_abs(fabs(sv), sv * sv);
+    const R rden = nngp::fast_rsqrt(fmax(fma(-sv, sv, R(1)), sizeof(R) == 8 ? R(1e-300) : R(1e-30)));
+    r.o = R(2.0 / kPiD) * copysign(as, sv);
+    r.dA = R(4.0 / kPiD) * uu * rden;
+    const R t = R(-2.0 / kPiD) * sv * rden;
+    r.d1 = t * rbi;
+    r.d2 = t * rbj;
+    const R ur = uu * rden, r2 = rden * rden;
+    r.hA = R(16.0 / kPiD) * a * (ur * ur * ur);
+    const R v = R(-4.0 / kPiD) * ur * r2;
+    r.h1 = v * rbi;
+    r.h2 = v * rbj;
+  }
+  return r;
+}
+
 constexpr int kTabFields = 5;   // per activation layer and row: q, dq/dw2, dq/db2, ra, rb
 
 // Diagonal of the same recursion (fp64 arithmetic): variance entering each activation, its derivatives and the two
@@ -287,6 +342,136 @@ __global__ void __launch_bounds__(256) grad_contract_multi_kernel(GradArgs<T> a)
   grad_contract_tile<T, NET, ACT, false, true>(a, a.partial);
 }
 
+// NTK form (SMN_NET_NTK): the covariance is Theta_out = lw2 (K + Theta), so the thread carries SIX values per entry,
+// (K, K_w, K_b, Theta, Theta_w, Theta_b) with subscripts d/dw2, d/db2 -- Theta the tangent kernel behind an activation, T the one
+// in front of it (the dense ResNet keeps T in the Theta slots between blocks):
+//   Dense:       A = w2 K + b2,  A_w = K + w2 K_w,  A_b = 1 + w2 K_b;   T = A + w2 Theta,  T_w = A_w + Theta + w2 Theta_w,
+//                T_b = A_b + w2 Theta_b
+//   activation:  K <- phi(A), K_t = D A_t + phi_1 q_i,t + phi_2 q_j,t  (as above);   D = phi_A,  D_t = D_A A_t + D_1 q_i,t + D_2 q_j,t;
+//                Theta <- T D,  Theta_t = T_t D + T D_t
+//   dense ResNet: every state of a block is Dense(act(S)) + S with the same rules (layer_prog.hpp ElemProg::step).
+// Six values x 16 rows do not fit the f64 register budget: the thread takes 8 rows at a time and the tile is covered in two
+// passes (rows w + 4 r of each 32-row half), the sums running on in the same fixed order.  The sums, the reduction tree and
+// the MULTI seed (formed behind the layer loop) are those of grad_contract_tile.
+template <typename T, int NET, int ACT, bool MULTI>
+__device__ __forceinline__ void grad_contract_tile_ntk(const GradArgs<T>& a, double* __restrict__ partial) {
+  using R = typename GradArgs<T>::R;
+  int tr, tc;
+  tri_decode(blockIdx.x, tr, tc);
+  const int64_t row0 = (int64_t)tr * GT, col0 = (int64_t)tc * GT, n = a.n;
+  const int tid = threadIdx.x;
+  const int lc = tid % GT;
+  const int w = __builtin_amdgcn_readfirstlane(tid / GT);
+  constexpr int NR = GT / 8, NPASS = 2;
+  const int64_t j = col0 + lc, jc = j < n ? j : n - 1;
+  const R w2 = (R)a.w2, b2 = (R)a.b2;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum G dTheta_out/dw2, sum G dTheta_out/db2, sum G Theta_out, tr G
+  const R coef = (R)a.coef, lw2 = (R)a.lw2;
+  const R aj = MULTI ? R(0) : (R)a.alpha[jc];
+#pragma unroll 1
+  for (int p = 0; p < NPASS; ++p) {
+    const int64_t rowp = row0 + w + 4 * NR * p;
+    R k[NR], kw[NR], kb[NR], th[NR], tw[NR], tb[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int64_t i = rowp + 4 * r, ic = i < n ? i : n - 1;
+      k[r] = (R)a.k0[ic * a.ldk0 + jc];
+      kw[r] = kb[r] = th[r] = tw[r] = tb[r] = R(0);
+      if (NET == NET_RESNET) {   // the Dense in front of the first block: A and T = A (Theta = 0)
+        kw[r] = k[r];
+        kb[r] = R(1);
+        k[r] = fma(w2, k[r], b2);
+        th[r] = k[r]; tw[r] = kw[r]; tb[r] = kb[r];
+      }
+    }
+    for (int s = 0; s < a.nsets; ++s) {
+      const R* ts = a.tab + (int64_t)s * kTabFields * n;
+      const R cdw = ts[n + jc], cdb = ts[2 * n + jc], cra = ts[3 * n + jc], crb = ts[4 * n + jc];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int64_t i = rowp + 4 * r, ic = i < n ? i : n - 1;   // wave-uniform
+        const R rq = ts[ic], rdw = ts[n + ic], rdb = ts[2 * n + ic], rra = ts[3 * n + ic], rrb = ts[4 * n + ic];
+        R aa = k[r], aw = kw[r], ab = kb[r], tt = th[r], ttw = tw[r], ttb = tb[r];
+        if (NET == NET_MLP) {
+          ttw = fma(w2, ttw, tt);          // Theta + w2 Theta_w (+ A_w below)
+          ttb = w2 * ttb;
+          aw = fma(w2, aw, aa);
+          ab = fma(w2, ab, R(1));
+          aa = fma(w2, aa, b2);
+          if (i == j) aa = rq;             // exact diagonal
+          tt = fma(w2, tt, aa);
+          ttw += aw;
+          ttb += ab;
+        } else if (i == j) {
+          aa = rq;                         // exact diagonal
+        }
+        const ActR2<R> q = act_r2<ACT, R>(aa, rra, rrb, cra, crb, i == j);
+        R o = q.o;
+        R ow = fma(q.dA, aw, fma(q.d1, rdw, q.d2 * cdw));
+        R ob = fma(q.dA, ab, fma(q.d1, rdb, q.d2 * cdb));
+        const R dw_ = fma(q.hA, aw, fma(q.h1, rdw, q.h2 * cdw));
+        const R db_ = fma(q.hA, ab, fma(q.h1, rdb, q.h2 * cdb));
+        R to = tt * q.dA;
+        R tow = fma(ttw, q.dA, tt * dw_);
+        R tob = fma(ttb, q.dA, tt * db_);
+        if (NET == NET_RESNET && s != a.nsets - 1) {   // S <- Dense(act(S)) + S, the Theta slots holding T
+          const R a2 = fma(w2, o, b2), a2w = fma(w2, ow, o), a2b = fma(w2, ob, R(1));
+          const R t2 = fma(w2, to, a2), t2w = fma(w2, tow, to) + a2w, t2b = fma(w2, tob, a2b);
+          o = aa + a2; ow = aw + a2w; ob = ab + a2b;
+          to = tt + t2; tow = ttw + t2w; tob = ttb + t2b;
+        }
+        k[r] = o; kw[r] = ow; kb[r] = ob; th[r] = to; tw[r] = tow; tb[r] = tob;
+      }
+    }
+    R gc[MULTI ? NR : 1];
+    if (MULTI) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int64_t i = rowp + 4 * r, ic = i < n ? i : n - 1;
+        gc[r] = R(a.nc) * (R)a.nkinv[ic * a.ldki + jc];
+      }
+      const T* rj = a.alpha + jc * a.nc;
+      for (int c = 0; c < a.nc; ++c) {
+        const R ajc = (R)rj[c];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int64_t i = rowp + 4 * r, ic = i < n ? i : n - 1;   // wave-uniform
+          gc[r] = fma(coef * (R)a.alpha[ic * a.nc + c], ajc, gc[r]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int64_t i = rowp + 4 * r, ic = i < n ? i : n - 1;
+      const bool valid = i < n && j < n && j <= i;
+      const R ai = MULTI ? R(0) : (R)a.alpha[ic];
+      const R g = MULTI ? gc[r] : fma(coef * ai, aj, (R)a.nkinv[ic * a.ldki + jc]);
+      const R m = !valid ? R(0) : (i == j ? R(1) : R(2));   // the upper triangle is the mirror image
+      const R gm = m * g * lw2;
+      // the last activation leaves (K, Theta); the last Dense adds them
+      acc[0] += (double)(gm * (kw[r] + tw[r]));
+      acc[1] += (double)(gm * (kb[r] + tb[r]));
+      acc[2] += (double)(gm * (k[r] + th[r]));
+      if (valid && i == j) acc[3] += (double)g;
+    }
+  }
+  __shared__ double red[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    double v = acc[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) red[q][tid >> 6] = v;
+  }
+  __syncthreads();
+  if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+template <typename T, int NET, int ACT, bool MULTI>
+__global__ void __launch_bounds__(256) grad_contract_ntk_kernel(GradArgs<T> a) {
+  grad_contract_tile_ntk<T, NET, ACT, MULTI>(a, a.partial);
+}
+
 // Second stage: fixed-order sum of the per-tile partials (bitwise reproducible).
 __device__ __forceinline__ void grad_reduce_block(const double* __restrict__ partial, int64_t ntiles, double* __restrict__ out) {
   __shared__ double red[4][4];
@@ -438,13 +623,15 @@ int with_net_act(int net, int act, F&& f) {
 }
 
 template <typename T, int NET, int ACT>
-int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t ntiles, double* out_d, bool multi) {
+int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t ntiles, double* out_d, bool multi, bool ntk) {
   hipLaunchKernelGGL((grad_tables_kernel<NET, ACT, T>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream,
                      q64, a.n, a.nsets, a.w2, a.b2, const_cast<T*>(a.tab));
   SMN_CHECK_LAUNCH(ctx);
   {
     ProfScope ps(ctx, PROF_MISC, ctx->stream);
-    if (multi) hipLaunchKernelGGL((grad_contract_multi_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
+    if (ntk && multi) hipLaunchKernelGGL((grad_contract_ntk_kernel<T, NET, ACT, true>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
+    else if (ntk) hipLaunchKernelGGL((grad_contract_ntk_kernel<T, NET, ACT, false>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
+    else if (multi) hipLaunchKernelGGL((grad_contract_multi_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((grad_contract_kernel<T, NET, ACT>), dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
   }
   SMN_CHECK_LAUNCH(ctx);
@@ -456,7 +643,8 @@ int grad_terms_na(smn_ctx* ctx, const GradArgs<T>& a, const double* q64, int64_t
 template <typename T>
 int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
                  const void* k0, int64_t n, int64_t ldk0, const void* q, const void* nkinv, int64_t ldki,
-                 const void* alpha, double coef, double out_h[4], int nc = 0) {   // nc > 0: the rank-C form, alpha [n, nc]
+                 const void* alpha, double coef, double out_h[4], int nc = 0,   // nc > 0: the rank-C form, alpha [n, nc]
+                 bool ntk = false) {                                              // the tangent of Theta instead of K
   const bool multi = nc > 0;
   const int nsets = net == SMN_NET_MLP ? num_hiddens : num_hiddens + 1;
   if (nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "num_hiddens too large (max %d activation layers)", kMaxSets);
@@ -481,14 +669,14 @@ int grad_terms_t(smn_ctx* ctx, int net, int act, int num_hiddens, double w_std, 
   a.w2 = w_std * w_std; a.b2 = b_std * b_std; a.lw2 = last_w_std * last_w_std; a.coef = coef;
   a.partial = partial;
   SMN_TRY(with_net_act(net, act, [&](auto NET, auto ACT) {
-    return grad_terms_na<T, decltype(NET)::value, decltype(ACT)::value>(ctx, a, q64, ntiles, out_d, multi);
+    return grad_terms_na<T, decltype(NET)::value, decltype(ACT)::value>(ctx, a, q64, ntiles, out_d, multi, ntk);
   }));
   double s[4];
   SMN_HIP(ctx, hipMemcpyAsync(s, out_d, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
   SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   out_h[0] = s[0] * 2.0 * w_std;                  // d/dw_std  = 2 w  d/dw^2
   out_h[1] = s[1] * 2.0 * b_std;
-  out_h[2] = s[2] * 2.0 / last_w_std;             // K = lw^2 K_L  =>  dK/dlw = 2 K / lw
+  out_h[2] = s[2] * 2.0 / last_w_std;             // K = lw^2 K_L  =>  dK/dlw = 2 K / lw  (NTK form: lw^2 (K_L + Theta_L))
   out_h[3] = s[3];                                // dK~/deps = I
   return SMN_OK;
 }
@@ -632,15 +820,16 @@ int lml_grad_terms(smn_ctx* ctx, const char* who, bool multi, int dtype, int net
   SMN_CHECK_LD(ctx, who, ldk0, n);
   SMN_CHECK_LD(ctx, who, ldkinv, n);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
-  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: bad hyper-parameters", who);
   const int nc = multi ? (int)c : 0;
   if (dtype == SMN_F64)
     return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
-                                ldkinv, alpha_d, coef, terms_h, nc);
+                                ldkinv, alpha_d, coef, terms_h, nc, ntk);
   return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
-                             alpha_d, coef, terms_h, nc);
+                             alpha_d, coef, terms_h, nc, ntk);
 }
 
 // smn_spr_loss_grad / smn_spr_loss_grad_multi.  Fused: K0 = X X^T / d and its diagonal, K by the stand-alone recursion straight
@@ -717,6 +906,7 @@ extern "C" int smn_spr_loss_grad_batch(smn_ctx* ctx, int dtype, int net, int act
     return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty batch or null parameter array");
   if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_grad_batch: empty");
   SMN_CHECK_LD(ctx, "smn_spr_loss_grad_batch", ldx, d);
+  SMN_TRY(no_ntk_net(ctx, "smn_spr_loss_grad_batch", net));
   if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", net);
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "num_hiddens < 0");

@@ -62,7 +62,8 @@ namespace {
 // diagonal for a relative ridge.
 int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, int64_t ldx, const void* xt,
               int64_t ldxt, int64_t d, int nbatch = 0, const double* bw = nullptr, const double* bb = nullptr,
-              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false, const GramPlan* gram = nullptr) {
+              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false, const GramPlan* gram = nullptr,
+              bool ntk = false) {   // ntk (SMN_NET_NTK): Theta lands where K would, alone
   const int64_t kp = k_pad(spec.dtype, d);
   const int gmode = gram ? gram->mode : GRAM_CALL_NONE;
   void* xs = nullptr;
@@ -82,8 +83,8 @@ int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, 
   c.symmetric = 1; c.mirror = 0; c.exact_diag = 1;
   c.store_mode = STORE_PAD_IDENTITY;
   c.nv0 = g.n; c.aug0 = g.n_pad; c.nv1 = g.t;
-  c.get_mask = SMN_GET_NNGP;
-  c.out_k = g.a; c.ldo = g.lda;
+  c.get_mask = ntk ? SMN_GET_NTK : SMN_GET_NNGP;
+  c.out_k = ntk ? nullptr : g.a; c.out_t = ntk ? g.a : nullptr; c.ldo = g.lda;
   c.nbatch = nbatch; c.bw = bw; c.bb = bb; c.blw = blw; c.out_bs = g.n_total * g.lda;   // batched: problem b at a + b * n_total^2
   // (not while pieces of a column-first exchange are still landing in this workspace)
   c.split_corner = (out && nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
@@ -591,10 +592,10 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
 int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
                          double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
                          double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h, int64_t c) {
+                         int* info_h, int64_t c, bool ntk) {
   const KernelInto build = [&](void* k_d, int64_t ldk) {
     return smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
-                         SMN_GET_NNGP, k_d, nullptr, ldk);
+                         ntk ? SMN_GET_NTK : SMN_GET_NNGP, ntk ? nullptr : k_d, ntk ? k_d : nullptr, ldk);
   };
   return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, c);
 }
@@ -622,10 +623,12 @@ int posterior_storage(smn_ctx* ctx, int dtype, int64_t n, int64_t c, bool with_g
 int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
                      const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
                      void* ninv_d, int64_t ldinv, void* alpha_d) {
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
   SMN_TRY(posterior_storage(ctx, dtype, n, c, true, p, ninv_d, ldinv, alpha_d));
   SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, p->k0, p->ld0, p->q));   // (lower tiles: all the recursion and the contraction read)
   return factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, p->k0, p->ld0, p->q, n, y_d, eps_abs,
-                              p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info, c);
+                              p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info, c, ntk);
 }
 
 int posterior_from_build(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c, double eps_abs,
@@ -684,18 +687,25 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   if (n <= 0 || d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss: empty");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss: scale must be > 0");
   SMN_CHECK_LD(ctx, "smn_spr_loss", ldx, d);
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
-  // the input Gram depends on x only: reused from the context's cache while x is unchanged (decided by content, on the device)
-  const GramPlan gram = gram_cache_plan(ctx, dtype, net, n, d, k_pad(dtype, d), g.n_total);
   double quad = 0.0, ld = 0.0;
   int info = 0;
-  int rc = aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, &gram);
-  if (rc == SMN_OK) rc = aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info);
-  gram_cache_settle(ctx, gram, rc);
-  if (rc != SMN_OK) return rc;
+  if (ntk) {   // Theta: the plain fused build from workspace slot 0; the Gram cache is neither read nor written
+    SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, nullptr, true));
+    SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
+  } else {
+    // the input Gram depends on x only: reused from the context's cache while x is unchanged (decided by content, on the device)
+    const GramPlan gram = gram_cache_plan(ctx, dtype, net, n, d, k_pad(dtype, d), g.n_total);
+    int rc = aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, &gram);
+    if (rc == SMN_OK) rc = aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info);
+    gram_cache_settle(ctx, gram, rc);
+    if (rc != SMN_OK) return rc;
+  }
   if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
   if (quad_h) *quad_h = quad;
   if (logdet_h) *logdet_h = ld;
@@ -715,13 +725,15 @@ extern "C" int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_loss_multi: more than 48 output columns");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_multi: scale must be > 0");
   SMN_CHECK_LD(ctx, "smn_spr_loss_multi", ldx, d);
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
   double quad[48], ld = 0.0;
   int info = 0;
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built));
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, nullptr, ntk));
   SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
   publish_head(quad, c, true, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
@@ -933,6 +945,7 @@ extern "C" int smn_spr_loss_batch(smn_ctx* ctx, int dtype, int net, int act, int
   if (!ctx || !x_d || !y_d) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (nprob <= 0 || !eps_abs) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_batch: empty batch or null eps_abs");
+  SMN_TRY(no_ntk_net(ctx, "smn_spr_loss_batch", net));
   for (int b = 0; b < nprob && df; ++b)
     if (df[b] > 0.0 && !(scale && scale[b] > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loss_batch: scale must be > 0");
   std::vector<double> quad((size_t)nprob), ld((size_t)nprob);
@@ -956,6 +969,7 @@ extern "C" int smn_spr_predict_batch(smn_ctx* ctx, int dtype, int net, int act, 
   if (!ctx || !x_d || !y_d || (t > 0 && !xt_d)) return SMN_EINVAL;
   SMN_ENTER(ctx);
   if (nprob <= 0 || !ridge_rel) return smn_fail(ctx, SMN_EINVAL, "smn_spr_predict_batch: empty batch or null ridge_rel");
+  SMN_TRY(no_ntk_net(ctx, "smn_spr_predict_batch", net));
   std::vector<double> zero;
   if (!ridge_abs) {
     zero.assign((size_t)nprob, 0.0);
@@ -977,10 +991,13 @@ extern "C" int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int nu
   SMN_CHECK_LD(ctx, "smn_spr_predict", ldx, d);
   if (t > 0) SMN_CHECK_LD(ctx, "smn_spr_predict", ldxt, d);
   if (cov_d) SMN_CHECK_LD(ctx, "smn_spr_predict", ldcov, t);
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, 0, nullptr, nullptr, nullptr, &built, ridge_rel != 0.0));
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, 0, nullptr, nullptr, nullptr, &built, ridge_rel != 0.0,
+                    nullptr, ntk));
   return aug_finish(ctx, dtype, g, built, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
 }

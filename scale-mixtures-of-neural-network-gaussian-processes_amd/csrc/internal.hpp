@@ -32,6 +32,23 @@ struct BuildSpec {
   double w_std, b_std, last_w_std;
 };
 
+// The `net` argument of the model entries: SMN_NET_MLP or SMN_NET_DENSE_RESNET, with SMN_NET_NTK OR-ed in where the entry's
+// covariance is the tangent kernel Theta instead of the NNGP kernel K.  split_net leaves the architecture in *net and the flag in
+// *ntk; any other bit is SMN_EINVAL naming the value.  no_ntk_net: entries that have no Theta form (the batched and grid ones).
+inline int split_net(smn_ctx* ctx, int* net, bool* ntk) {
+  const int base = *net & ~SMN_NET_NTK;
+  if (base != SMN_NET_MLP && base != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "unknown net %d", *net);
+  *ntk = (*net & SMN_NET_NTK) != 0;
+  *net = base;
+  return SMN_OK;
+}
+inline int no_ntk_net(smn_ctx* ctx, const char* who, int net) {
+  const int base = net & ~SMN_NET_NTK;
+  if ((net & SMN_NET_NTK) && (base == SMN_NET_MLP || base == SMN_NET_DENSE_RESNET))
+    return smn_fail(ctx, SMN_ENOTSUP, "%s: no SMN_NET_NTK form (net %d)", who, net);
+  return SMN_OK;   // (any other value is the entry's own SMN_EINVAL)
+}
+
 enum { STORE_BOUNDS = 0, STORE_PAD_IDENTITY = 1 };
 
 // One fused Gram + layer-recursion launch.  Operands are PADDED copies (rows a multiple of 128,
@@ -129,7 +146,7 @@ int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int
 int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
                          double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
                          double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h, int64_t c = 1);
+                         int* info_h, int64_t c = 1, bool ntk = false);   // ntk: Theta by the same recursion instead of K
 // the same with K written by the caller: build(k_d, ldk) fills the lower triangle of K (n rows) in the factorisation workspace
 using KernelInto = std::function<int(void* k_d, int64_t ldk)>;
 int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
@@ -175,6 +192,7 @@ struct Posterior {
   double quad[48]; double logdet = 0.0; int info = 0;
 };
 // from x [n, d]: gram_lower + factor_with_identity.  ninv_d / alpha_d: the caller's storage (ld = ldinv) instead of slot 7.
+// net may carry SMN_NET_NTK: the posterior is then that of Theta~ = Theta + eps I.
 int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
                      const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
                      void* ninv_d = nullptr, int64_t ldinv = 0, void* alpha_d = nullptr);

@@ -788,7 +788,9 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
                      c.q1, c.rows1, prog, tab1, tlen, dg1, dgt1, progs_d, tab_bs);
   SMN_CHECK_LAUNCH(ctx);
   if (c.want_trace && c.symmetric && c.exact_diag && c.nbatch == 0 && !c.shard && c.nv0 > 0) {
-    hipLaunchKernelGGL(table_trace_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, dg1, c.nv0, ctx->d_scal + 1);
+    // (an NTK-only build: the matrix the trace belongs to is Theta, its exact diagonal the second table)
+    hipLaunchKernelGGL(table_trace_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, (c.get_mask & SMN_GET_NNGP) ? dg1 : dgt1, c.nv0,
+                       ctx->d_scal + 1);
     SMN_CHECK_LAUNCH(ctx);
     if (out) out->trace = true;
   }

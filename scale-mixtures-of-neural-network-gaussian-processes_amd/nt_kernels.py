@@ -47,15 +47,30 @@ def _parse_get(get):
 class KernelFn:
     """kernel_fn of an MLP-family architecture (net = MLP or dense ResNet)."""
 
-    def __init__(self, net, num_hiddens, act, w_std, b_std, last_w_std, ctx=None):
+    def __init__(self, net, num_hiddens, act, w_std, b_std, last_w_std, ctx=None, cov="nngp"):
         self.net, self.num_hiddens = int(net), int(num_hiddens)
         self.act_name, self.act = act, get_act_class(act)
         self.w_std, self.b_std, self.last_w_std = float(w_std), float(b_std), float(last_w_std)
         self.ctx = ctx
+        if cov not in ("nngp", "ntk"):
+            raise ValueError("cov must be 'nngp' or 'ntk', got %r" % (cov,))
+        self.cov = cov
 
     @property
     def params(self):
-        return (self.net, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std)
+        """What the model entries of the C ABI take in front of the data: (net, act, num_hiddens, w_std, b_std,
+        last_w_std).  In covariance mode "ntk" net carries SMN_NET_NTK, and those entries work on Theta instead of K."""
+        net = self.net | _lib.NET_NTK if self.cov == "ntk" else self.net
+        return (net, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std)
+
+    def with_cov(self, cov):
+        """The same kernel function in covariance mode `cov` ("nngp" or "ntk"): which of its two kernels a model built on
+        it (spax.kernels.NNGPKernel / NTKKernel) takes as the covariance function of its GP.  `__call__` is unaffected."""
+        return KernelFn(self.net, self.num_hiddens, self.act_name, self.w_std, self.b_std, self.last_w_std, self.ctx, cov)
+
+    def cov_matrix(self, x1, x2=None, fill="full"):
+        """The matrix of the covariance mode: K or Theta of x1 against x2."""
+        return self(x1, x2, get=self.cov, fill=fill)
 
     def __call__(self, x1, x2=None, get="nngp", fill="full"):
         ctx = self.ctx or (x1.ctx if isinstance(x1, DeviceArray) else default_context())

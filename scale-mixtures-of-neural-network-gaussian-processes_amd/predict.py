@@ -1,5 +1,6 @@
 """neural_tangents.predict.gradient_descent_mse_ensemble look-alike (t = None: NNGP posterior fused on the
-device, NTK posterior composed from the public entry points; t = times: the finite-time ensemble through the
+device -- and, as get="ntk_gp", the same posterior with Theta as the covariance function --, NTK posterior composed from
+the public entry points; t = times: the finite-time ensemble through the
 device eigensolver, smn_predict_gd).
 
 Called by spax/kernels.py:30-31 and experiments/regression/find.py:75-76 as
@@ -43,8 +44,11 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
             return _predict_gd(t, x_test, get, compute_cov)
         if get == "ntk":
             return _predict_ntk(x_test, compute_cov)
-        if get != "nngp":
-            raise NotImplementedError("get must be 'nngp' or 'ntk'")
+        if get not in ("nngp", "ntk_gp"):
+            raise NotImplementedError("get must be 'nngp', 'ntk' or 'ntk_gp'")
+        # "ntk_gp" (spax.kernels.NTKKernel.predict): the exact GP whose covariance function is Theta -- the "nngp" posterior
+        # with Theta in place of K everywhere, NOT the ensemble covariance of get="ntk" (their means coincide)
+        mode = "ntk" if get == "ntk_gp" else "nngp"
         xt = x if x_test is None else as_device(x_test, ctx, dtype=x.dtype)
         tt = xt.shape[0]
         mean = ctx.empty((tt, c), x.dtype)
@@ -54,12 +58,12 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
         info = C.c_int()
         rel, ab = (0.0, float(diag_reg)) if diag_reg_absolute_scale else (float(diag_reg), 0.0)
         if isinstance(kernel_fn, KernelFn):
-            net, act, L, w, b, lw = kernel_fn.params
+            net, act, L, w, b, lw = kernel_fn.with_cov(mode).params       # "ntk": net carries SMN_NET_NTK
             ctx.call("smn_spr_predict", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], xt.ptr, tt, xt.shape[1],
                      x.shape[1], y.ptr, c, rel, ab, mean.ptr, cov.ptr, tt, quad, C.byref(logdet), C.byref(info))
         else:  # any other kernel_fn: build the joint kernel with it, then the same factorisation
             xa = np.concatenate([np.asarray(x), np.asarray(xt)], axis=0)
-            kj = as_device(kernel_fn(xa, None, "nngp"), ctx, dtype=x.dtype)
+            kj = as_device(kernel_fn(xa, None, mode), ctx, dtype=x.dtype)
             ctx.call("smn_predict", x.dcode, kj.ptr, n, tt, n + tt, y.ptr, c, rel, ab, mean.ptr, cov.ptr, tt,
                      quad, C.byref(logdet), C.byref(info))
         if info.value != 0:       # JAX semantics: a failed Cholesky is silent NaN

@@ -7,11 +7,12 @@ Nothing numerical happens here: a kernel function built by `nt_kernels` is a han
 """
 from __future__ import annotations
 
+from ..nt_kernels import CnnKernelFn, KernelFn
 from ..predict import gradient_descent_mse_ensemble
 from .base import ConstraintTrainVar, Module
 from .bijectors import positive
 
-__all__ = ["NNGPKernel"]
+__all__ = ["NNGPKernel", "NTKKernel"]
 
 _TRAINABLES = ("w_std", "b_std", "last_w_std")
 
@@ -50,3 +51,40 @@ class NNGPKernel(Module):
         RELATIVE ridge (diag_reg), not the absolute jitter of the likelihood heads."""
         posterior = gradient_descent_mse_ensemble(kernel_fn, x, y, diag_reg=eps)
         return tuple(posterior(x_test=x_test, get="nngp", compute_cov=True))
+
+
+class NTKKernel(NNGPKernel):
+    """Drop-in sibling of NNGPKernel whose covariance function is the neural tangent kernel Theta of the same architecture:
+    same trainables, names, get_params, get_kernel_fn, K and predict.  With it SPR / MultiSPR are exact GPs (or Student-t
+    processes) on Theta~ = Theta(X,X) + eps I: loss, gradients, leave-one-out, predictions, draws and classification.
+
+    The semantics are "a GP whose covariance function is Theta": posterior mean Theta_td Theta~^-1 y and covariance
+    Theta_tt - Theta_td Theta~^-1 Theta_dt.  This is deliberately NOT neural_tangents' get="ntk" ensemble covariance
+    (K_tt + a^T K_dd a - a^T K_dt - K_td a, the spread of an ensemble of trained networks), which stays where it is:
+    gradient_descent_mse_ensemble(...)(get="ntk").  The two means coincide.
+
+    get_mlp_kernel and get_dense_resnet_kernel are fused on the device (the SMN_NET_NTK flag of the C ABI).  The conv
+    factories have no Theta: NotImplementedError, before any device call.  Any other callable is asked for get="ntk", as
+    NNGPKernel asks such a callable for get="nngp"."""
+
+    def get_kernel_fn(self):
+        kernel_fn = super().get_kernel_fn()
+        if isinstance(kernel_fn, CnnKernelFn):
+            raise NotImplementedError("NTKKernel: the conv kernels are NNGP-only (get_mlp_kernel / get_dense_resnet_kernel "
+                                      "have the tangent kernel)")
+        return kernel_fn.with_cov("ntk") if isinstance(kernel_fn, KernelFn) else kernel_fn
+
+    def K(self, kernel_fn, x, x2=None):
+        """Theta of x against x2 (against itself when x2 is None)."""
+        if isinstance(kernel_fn, CnnKernelFn):
+            raise NotImplementedError("NTKKernel: the conv kernels are NNGP-only")
+        other = None if (x2 is None or x2 is x) else x2
+        return kernel_fn(x, other, get="ntk")
+
+    def predict(self, kernel_fn, x, y, x_test, eps=1e-6):
+        """Posterior mean [T, C] and covariance [T, T] of the GP with covariance function Theta at x_test, with the relative
+        ridge of NNGPKernel.predict: Theta~ = Theta_dd + eps tr(Theta_dd)/N I."""
+        if isinstance(kernel_fn, CnnKernelFn):
+            raise NotImplementedError("NTKKernel: the conv kernels are NNGP-only")
+        posterior = gradient_descent_mse_ensemble(kernel_fn, x, y, diag_reg=eps)
+        return tuple(posterior(x_test=x_test, get="ntk_gp", compute_cov=True))

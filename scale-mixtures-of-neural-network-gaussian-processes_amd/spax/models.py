@@ -90,7 +90,8 @@ class _LooMixin:
             raise NotImplementedError("leave-one-out is wired for the nt_kernels factories; got %s" % type(kernel_fn).__name__)
         x, ctx = self.x_data, self.x_data.ctx
         n, c = self._loo_shape()
-        k = kernel_fn(x, None, get="nngp", fill="lower")
+        # the matrix of the kernel function's covariance mode (KernelFn under NTKKernel: Theta); the conv kernels have K only
+        k = kernel_fn.cov_matrix(x, None, fill="lower") if isinstance(kernel_fn, KernelFn) else kernel_fn(x, None, get="nngp", fill="lower")
         mean = ctx.empty((n, c), x.dtype) if want_pred else None
         scale2 = ctx.empty((n,), x.dtype) if want_pred else None
         lam, info = C.c_double(), C.c_int()
@@ -145,7 +146,7 @@ class _DrawsMixin:
     per draw, shared by all its points and outputs (csrc/draws.hip)."""
 
     def predict(self, x):
-        """(mean [T,C], cov [T,T]) of NNGPKernel.predict (relative ridge eps) as device arrays in normalised units: one
+        """(mean [T,C], cov [T,T]) of the kernel's predict (NNGPKernel / NTKKernel, relative ridge eps) as device arrays in normalised units: one
         covariance shared by the outputs (C = 1 for SPR)."""
         return self.kernel.predict(self.kernel.get_kernel_fn(), self.x_data, self.y_data, x, eps=self.eps.safe_value)
 

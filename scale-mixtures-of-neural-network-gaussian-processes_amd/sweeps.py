@@ -25,6 +25,24 @@ __all__ = ["find_grid", "loss_batch", "loss_and_grad_batch", "predict_batch"]
 _NET = {"mlp": _lib.NET_MLP, None: _lib.NET_MLP, "resnet": _lib.NET_DENSE_RESNET}
 
 
+def _net_code(network, covariance):
+    """The `net` argument: the architecture, with SMN_NET_NTK for covariance="ntk".  The batched entries have no Theta form
+    (multi-start and grid search on the tangent kernel are not implemented): they answer the flag with SMN_ENOTSUP, which
+    _batched turns into NotImplementedError."""
+    if covariance not in ("nngp", "ntk"):
+        raise ValueError("covariance must be 'nngp' or 'ntk', got %r" % (covariance,))
+    return _NET[network] | (_lib.NET_NTK if covariance == "ntk" else 0)
+
+
+def _batched(ctx, name, *args):
+    try:
+        ctx.call(name, *args)
+    except _lib.SmnError as e:
+        if e.code == _lib.ENOTSUP and "SMN_NET_NTK" in str(e):
+            raise NotImplementedError(str(e)) from e
+        raise
+
+
 def _norm_logpdf(x, mean, sigma):
     z = (x - mean) / sigma
     return -0.5 * z * z - np.log(sigma) - 0.5 * math.log(2 * math.pi)
@@ -35,9 +53,11 @@ def _darr(values):
     return arr, arr.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0, scale=1.0):
+def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0, scale=1.0,
+               covariance="nngp"):
     """G x SPR.loss on one data set in one batched pass (smn_spr_loss_batch).  w_std, b_std, last_w_std, eps, df, scale:
     scalars or sequences of one common length G.  x, y: DeviceArrays of ctx (float32 or float64, the compute type).
+    covariance="ntk" (here and in the two functions below) raises NotImplementedError: the batched entries are NNGP-only.
     Returns (logpdf[G], quad[G], logdet[G], info[G]) as NumPy arrays; logpdf is NaN where info != 0."""
     g = max(np.size(v) for v in (w_std, b_std, last_w_std, eps, df, scale))
     cols = [_darr(np.broadcast_to(np.asarray(v, dtype=np.float64), (g,))) for v in (w_std, b_std, last_w_std, eps, df, scale)]
@@ -45,14 +65,14 @@ def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_
     lp, quad, logdet = np.empty(g), np.empty(g), np.empty(g)
     info = np.zeros(g, dtype=np.int32)
     pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))    # noqa: E731
-    ctx.call("smn_spr_loss_batch", x.dcode, _NET[network], _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1], cols[2][1],
+    _batched(ctx, "smn_spr_loss_batch", x.dcode, _net_code(network, covariance), _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1], cols[2][1],
              x.ptr, n, x.ld, d, y.ptr, cols[3][1], cols[4][1], cols[5][1], pd(lp), pd(quad), pd(logdet),
              info.ctypes.data_as(C.POINTER(C.c_int)))
     return lp, quad, logdet, info
 
 
 def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0,
-                        scale=1.0):
+                        scale=1.0, covariance="nngp"):
     """G x SPR.loss_and_grad's device call on one data set in one batched pass (smn_spr_loss_grad_batch): multi-start
     training (train.build_multistart_step) and gradient refinement of the cells of a grid search.  Arguments as for
     loss_batch (MLP and dense-ResNet kernels).  Returns (logpdf[G], quad[G], logdet[G], info[G], terms[G, 4]) as NumPy
@@ -66,7 +86,7 @@ def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="
     terms = np.empty((g, 4))
     info = np.zeros(g, dtype=np.int32)
     pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))    # noqa: E731
-    ctx.call("smn_spr_loss_grad_batch", x.dcode, _NET[network], _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1],
+    _batched(ctx, "smn_spr_loss_grad_batch", x.dcode, _net_code(network, covariance), _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1],
              cols[2][1], x.ptr, n, x.ld, d, y.ptr, cols[3][1], cols[4][1], cols[5][1], pd(quad), pd(logdet),
              info.ctypes.data_as(C.POINTER(C.c_int)), pd(terms))
     lp = np.full(g, np.nan)
@@ -78,7 +98,7 @@ def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="
 
 
 def predict_batch(ctx, x, y, x_test, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0,
-                  diag_reg, full_cov=False, on_device=False):
+                  diag_reg, full_cov=False, on_device=False, covariance="nngp"):
     """G x NNGPKernel.predict (relative ridge diag_reg, spax/kernels.py:29-32) on one data set in one batched pass
     (smn_spr_predict_batch).  y: DeviceArray [n, c].  Returns (mean [G,t,c], var [G,t] or cov [G,t,t], info[G]); the first
     two as DeviceArrays when on_device."""
@@ -90,7 +110,7 @@ def predict_batch(ctx, x, y, x_test, *, network="mlp", num_hiddens=4, activation
     mean = ctx.empty((g, t, c), x.dtype)
     out = ctx.empty((g, t, t) if full_cov else (g, t), x.dtype)
     info = np.zeros(g, dtype=np.int32)
-    ctx.call("smn_spr_predict_batch", x.dcode, _NET[network], _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1], cols[2][1],
+    _batched(ctx, "smn_spr_predict_batch", x.dcode, _net_code(network, covariance), _lib.ACT[activation], num_hiddens, g, cols[0][1], cols[1][1], cols[2][1],
              x.ptr, n, x.ld, x_test.ptr, t, x_test.ld, d, y.ptr, c, cols[3][1], None, mean.ptr,
              out.ptr if full_cov else None, t, None if full_cov else out.ptr, None, None, info.ctypes.data_as(C.POINTER(C.c_int)))
     return (mean, out, info) if on_device else (mean.numpy(), out.numpy(), info)

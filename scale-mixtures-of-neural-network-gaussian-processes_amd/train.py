@@ -163,6 +163,9 @@ class MultiStartStep:
             raise ValueError("every entry of starts needs the same number G >= 1 of raw values")
         self.num_starts = sizes.pop()
         net, act, self._layers = kernel_fn.params[:3]
+        if net & _lib.NET_NTK:   # what smn_spr_loss_grad_batch answers with SMN_ENOTSUP (sweeps.loss_and_grad_batch, covariance="ntk")
+            raise NotImplementedError("multi-start training on the tangent kernel (NTKKernel) is not implemented: the batched "
+                                      "gradient entry has no SMN_NET_NTK form; use build_train_step per start")
         self._network = "mlp" if net == _lib.NET_MLP else "resnet"
         self._activation = {v: k for k, v in _lib.ACT.items()}[act]
         owners = {"w_std": model.kernel.w_std, "b_std": model.kernel.b_std, "last_w_std": model.kernel.last_w_std, "eps": model.eps}
@@ -230,7 +233,7 @@ class MultiStartStep:
 def build_multistart_step(model, starts, optimizer=None):
     """step(learning_rate) -> losses[G] before the update, for G starts of `model` trained side by side (MultiStartStep).
     starts: {name in model.vars(): array of G raw values}.  MLP and dense-ResNet kernels with a Gaussian or Student-t
-    likelihood; conv kernels raise NotImplementedError (use build_train_step per start)."""
+    likelihood; conv kernels and NTKKernel models raise NotImplementedError (use build_train_step per start)."""
     return MultiStartStep(model, starts, optimizer)
 
 
