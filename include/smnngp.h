@@ -267,6 +267,45 @@ int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
                     void* mean_d, void* cov_d, int64_t ldcov,
                     double* quad_h, double* logdet_h, int* info_h);
 
+/* ---- fit once, predict many: a device-resident posterior (csrc/fit.hip) ----
+ * Every entry above refactors the training kernel for each prediction.  A fitted state keeps the Cholesky factor L of
+ * K~ = K_dd + (ridge_abs + ridge_rel tr(K_dd) / n) I -- the posterior of smn_spr_predict -- and beta^T = Y^T L^-T, and answers
+ * prediction calls of any size t >= 1 at O(n^2 t): chunks of at most `capacity` test rows go through the cross kernel (written
+ * straight into the state), one triangular solve and one read-out pass (mean = V^T beta, var = k_tt - |L^-1 k|^2, fp64 sums in
+ * a fixed order: the same arguments give the same bits).  The state owns its memory ([n_pad + round_up(capacity, 128) + 128]^2
+ * elements plus, in the fused form, a padded copy of x), uses no workspace slot of the context between calls, and is immutable:
+ * later changes to x_d, y_d or the hyper-parameters do not reach it.  dtype is fixed at creation; 1 <= c <= 48 (SMN_ENOTSUP
+ * above); capacity >= 1.
+ *   smn_fit_create              fused form (SMN_NET_MLP / SMN_NET_DENSE_RESNET, optionally | SMN_NET_NTK: the GP of Theta);
+ *                               y_d [n, c] row-major; quad_h [c], logdet_h, info_h (any may be NULL) as smn_spr_predict.
+ *   smn_fit_create_from_kernel  matrix form: k_d [n, n] lower, NOT modified.
+ *   smn_fit_predict             fused states: xt_d [t, ldxt] -> mean_d [t, c], var_d [t] and / or cov_d [t, ldcov] (full,
+ *                               symmetric); var_d and cov_d may be NULL.  cov_d needs t <= capacity (SMN_EINVAL otherwise:
+ *                               the Schur block K_tt - V^T V sits behind the factor); the diagonal path never forms a t x t
+ *                               object.  No host synchronisation once the context's workspace has reached the call's size (the first
+ *                               call of a shape grows it, before anything is launched).
+ *   smn_fit_apply               either kind of state, the caller supplies k_td_d [t, n] and ktt_diag_d [t] and / or k_tt_d
+ *                               [t, t] (lower): var_d needs one of the two (the diagonal is taken from ktt_diag_d when both are
+ *                               given), cov_d needs k_tt_d.
+ *   smn_fit_info                sizes and the bytes the state owns (NULL outputs are skipped).
+ *   smn_fit_destroy             synchronises the context's stream and frees the state.
+ * Not positive definite: *info_h = the failing pivot, the state is still returned (SMN_OK) and every prediction from it is NaN.
+ * A state must be destroyed before its context; using it after smn_fit_destroy is undefined. */
+typedef struct smn_fit smn_fit;
+int smn_fit_create(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
+                   double w_std, double b_std, double last_w_std,
+                   const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                   double ridge_rel, double ridge_abs, int64_t capacity,
+                   smn_fit** out, double* quad_h, double* logdet_h, int* info_h);
+int smn_fit_create_from_kernel(smn_ctx* ctx, int dtype, const void* k_d, int64_t n, int64_t ldk, const void* y_d, int64_t c,
+                               double ridge_rel, double ridge_abs, int64_t capacity,
+                               smn_fit** out, double* quad_h, double* logdet_h, int* info_h);
+int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* mean_d, void* var_d, void* cov_d, int64_t ldcov);
+int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, const void* ktt_diag_d, const void* k_tt_d, int64_t ldtt,
+                  void* mean_d, void* var_d, void* cov_d, int64_t ldcov);
+int smn_fit_info(smn_fit* fit, int64_t* n, int64_t* c, int64_t* capacity, size_t* bytes);
+int smn_fit_destroy(smn_fit* fit);
+
 /* ---- batched small problems: G evaluations on ONE data set in one sequence of launches (grid.y = G) ----
  * The reference's real workloads are small and many: experiments/regression/find.py:134-199 factors the kernel of one data
  * set 2 x 99 times under a grid of (w_std, b_std, eps), train.py:178-212 takes thousands of steps at N = 245, where one

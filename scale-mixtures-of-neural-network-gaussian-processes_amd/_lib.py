@@ -137,6 +137,12 @@ PROTOTYPES = {
     "smn_shard_wait": [_vp],
     "smn_lml_from_shards": [_vp, _i, _i64, _vp, _d, _d, _pd, _pd, _pd, _pi],
     "smn_debug_delay": [_vp, _i, _i64],
+    "smn_fit_create": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _i64, _pvp, _pd, _pd, _pi],
+    "smn_fit_create_from_kernel": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _d, _d, _i64, _pvp, _pd, _pd, _pi],
+    "smn_fit_predict": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64],
+    "smn_fit_apply": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64],
+    "smn_fit_info": [_vp, _pi64, _pi64, _pi64, C.POINTER(C.c_size_t)],
+    "smn_fit_destroy": [_vp],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing
@@ -176,6 +182,14 @@ class Context:
 
     def call(self, name, *args):
         rc = getattr(_lib, name)(self.handle, *args)
+        if rc != OK:
+            buf = C.create_string_buffer(512)
+            _lib.smn_last_error(self.handle, buf, 512)
+            raise SmnError(rc, "%s: %s" % (name, buf.value.decode(errors="replace")))
+
+    def call_on(self, name, handle, *args):
+        """An entry whose first argument is an object made on this context (smn_fit_*), not the context itself."""
+        rc = getattr(_lib, name)(handle, *args)
         if rc != OK:
             buf = C.create_string_buffer(512)
             _lib.smn_last_error(self.handle, buf, 512)

@@ -1631,6 +1631,27 @@ int solve_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t
   return SMN_OK;
 }
 
+// The trailing block of solved appended rows (internal.hpp): what the factorisation's far update does to them, column
+// super-panel by column super-panel in a fixed order.
+int schur_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda) {
+  if (n_total % kTile || n_factor % kTile || n_factor <= 0 || n_total <= n_factor)
+    return smn_fail(ctx, SMN_EINVAL, "schur_rows_padded: padding");
+  const int64_t tm = (n_total - n_factor) / kTile;
+  int64_t S = ctx->super_panel / PB * PB;
+  if (S < PB) S = PB;
+  const FactorCall plain{};
+  if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx));
+  else SMN_TRY(set_lds_attrs<float>(ctx));
+  for (int64_t k0 = 0; k0 < n_factor; k0 += S) {
+    const int64_t K = n_factor - k0 < S ? n_factor - k0 : S;
+    if (dtype == SMN_F64)
+      SMN_TRY(launch_update<double>(ctx, plain, ctx->stream, static_cast<double*>(a), lda, n_factor, n_factor, k0, K, tm, tm, 1));
+    else
+      SMN_TRY(launch_update<float>(ctx, plain, ctx->stream, static_cast<float*>(a), lda, n_factor, n_factor, k0, K, tm, tm, 1));
+  }
+  return SMN_OK;
+}
+
 namespace {
 // mail[0] = logdet, mail[1] = info, mail[2 .. 2+nq) = the quadratic forms: written straight into pinned host memory
 __global__ void publish_kernel(const double* __restrict__ scal, const int* __restrict__ info,

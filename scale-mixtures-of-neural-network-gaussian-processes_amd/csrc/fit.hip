@@ -1,0 +1,447 @@
+// fit.hip — fit once, predict many: a device-resident posterior (smn_fit_*).
+//
+// Every other predictive entry factors the joint kernel of [x_train; x_test] from scratch.  A state keeps what does not
+// depend on the test points -- the Cholesky factor L of K~ = K_dd + (ridge_abs + ridge_rel tr(K_dd) / n) I and beta^T =
+// Y^T L^-T -- and answers a prediction call with the cross kernel, one triangular solve and one read-out pass:
+//
+//        [ L             .            .  ]   rows 0 .. n_pad              (factor, identity padding)
+//   A =  [ K_td -> V^T   K_tt -> S    .  ]   rows n_pad .. + cap_pad      (one chunk of test rows; cap_pad = round_up(capacity, 128))
+//        [ beta^T        0            0  ]   rows n_pad + cap_pad .. +128 (c <= 48 of them used)
+//
+//   V^T = K_td L^-T (solve_rows_padded on the chunk's tile rows only), mean = V^T beta, var = k_tt - |V_r|^2,
+//   S = K_tt - V^T V (schur_rows_padded, the factorisation's far update) when the full covariance is asked for.
+//
+// beta^T sits in a tile row of its own BEHIND the test rows: the solve and the Schur update work on whole 128-row tiles of
+// [n_pad, n_pad + round_up(rows, 128)), and a right-hand-side row sharing a tile with test rows would be solved a second time.
+// The matrix is therefore [n_pad + cap_pad + 128]^2, at most one tile row more than [n_pad + round_up(capacity + c, 128)]^2.
+// The state owns A and (fused form) its padded copy of x with the row norms q; the context's workspace slots are used only
+// inside a call (padded test chunk: slot 0, layer tables: slot 1, factored diagonal blocks: slot 3), so a state survives any
+// other call on its context.  Nothing in it changes after creation.
+//
+// Why trsm on L and not the explicit -K~^-1 the gradient pipeline leaves behind: k^T K~^-1 k through an explicit inverse loses
+// cond(K~) u in fp32, while k_tt - |L^-1 k|^2 is a difference of two non-negative numbers each good to n u of k_tt.
+//
+// Read-out kernel (the hot path of a diag-only call once the cross kernel is solved): a fixed group of four waves per test
+// row (a chunk of 2048 rows puts 8192 waves on the chip; one wave per row would leave it at two waves per SIMD with one load
+// each in flight), 16-byte loads of the row (n_pad is a multiple of 128 elements), fp64 accumulation per lane in column order,
+// the fixed xor tree over each wave, the four waves added in wave order -- the order of every sum depends on n_pad alone, not
+// on the grid, the chunking or c, so repeated calls give the same bits.  The mean of c columns is taken in the same kernel,
+// CB columns per pass over the row (CB = 1, 4 or 8 by c): for c = 1 -- SPR, the flagship -- the row is streamed from HBM
+// exactly once.  For wide Y (c up to 48) the alternative is the NT tile engine (gemm_nt.hpp, as smn_gram uses it) for V^T beta
+// with the kernel keeping only the sum of squares.  Both were timed on an MI355X in fp32 at T = 2048, c = 48
+// (profiles/r18_fit_predict.txt): this kernel, six passes of eight columns, 0.301 ms at N = 16384 and 0.092 ms at N = 4096;
+// the sum-of-squares pass (0.027 / 0.012 ms) plus the tile engine on [T, n_pad] x [48, n_pad] operands (1.049 / 0.273 ms of
+// kernel time) 1.076 / 0.285 ms -- a 128-column tile holds 48 live columns and the launch is 16 workgroups on a 256-CU chip,
+// while the extra passes here re-read a row (n_pad * es <= 64 KB) that the first pass left in L2.  So the mean stays in this
+// kernel, in fp64, for every c.  Compiler figures (HIP 7.2, gfx950, -O3), VGPRs / waves per SIMD, no scratch in any form:
+// f32 CB = 1: 53 / 8, CB = 4: 75 / 6, CB = 8: 107 / 4; f64 40 / 8, 50 / 8, 70 / 7.
+#include <algorithm>
+#include <cmath>
+#include <new>
+
+#include "internal.hpp"
+
+struct smn_fit {
+  smn_ctx* ctx = nullptr;
+  int dtype = 0, net = 0, act = 0, num_hiddens = 0;
+  bool ntk = false, fused = false;
+  double w_std = 0.0, b_std = 0.0, last_w_std = 0.0;
+  int64_t n = 0, n_pad = 0, c = 0, capacity = 0, cap_pad = 0, n_total = 0, lda = 0, d = 0, kp = 0;
+  void* a = nullptr;    // [n_total, lda]
+  void* xs = nullptr;   // fused form: q [n_pad] doubles, then the padded x [n_pad, kp]
+  size_t bytes = 0;
+  int info = 0;
+  size_t es() const { return dtype_size(dtype); }
+  char* at(int64_t r, int64_t col) const { return static_cast<char*>(a) + es() * (size_t)(r * lda + col); }
+  double* q() const { return static_cast<double*>(xs); }
+  char* xp() const { return reinterpret_cast<char*>(q() + n_pad); }
+  int64_t beta_row() const { return n_pad + cap_pad; }
+};
+
+namespace {
+
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<float> { using type = float4; static constexpr int N = 4; };
+template <>
+struct Vec16<double> { using type = double2; static constexpr int N = 2; };
+
+// One workgroup (four waves) per solved test row r:
+//   var[r] = ktt[r * ktt_stride] - sum_j v[r, j]^2,   mean[r, k] = sum_j v[r, j] beta[k, j]   (j < n_pad, k < c)
+// Each lane walks the row in 16-byte pieces 256 lanes apart and adds in fp64 in that order; a wave's 64 partial sums meet in
+// the xor tree and the four waves' sums are added in wave order by one thread.  Column k's sum does not depend on CB (the
+// columns of a group are independent accumulators), on the grid or on which rows share a call.
+template <typename T, int CB>
+__global__ void __launch_bounds__(256) fit_readout_kernel(const T* __restrict__ v, int64_t lda, int64_t n_pad,
+                                                          const T* __restrict__ beta, int c, const T* __restrict__ ktt,
+                                                          int64_t ktt_stride, T* __restrict__ mean, T* __restrict__ var) {
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  __shared__ double red[4][CB + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = blockIdx.x;
+  const T* vr = v + row * lda;
+  for (int c0 = 0; c0 < c; c0 += CB) {
+    double s[CB];
+#pragma unroll
+    for (int e = 0; e < CB; ++e) s[e] = 0.0;
+    double ss = 0.0;
+#pragma unroll 2
+    for (int64_t k = (int64_t)threadIdx.x * VN; k < n_pad; k += 256 * VN) {
+      const V xv = *reinterpret_cast<const V*>(vr + k);
+      const T* xe = reinterpret_cast<const T*>(&xv);
+      if (c0 == 0) {
+#pragma unroll
+        for (int u = 0; u < VN; ++u) ss += (double)xe[u] * (double)xe[u];
+      }
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        const int ce = c0 + e < c ? c0 + e : c - 1;
+        const V bv = *reinterpret_cast<const V*>(beta + (int64_t)ce * lda + k);
+        const T* be = reinterpret_cast<const T*>(&bv);
+#pragma unroll
+        for (int u = 0; u < VN; ++u) s[e] += (double)xe[u] * (double)be[u];
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+#pragma unroll
+    for (int e = 0; e < CB; ++e) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[e] += __shfl_xor(s[e], o);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int e = 0; e < CB; ++e) red[wave][e] = s[e];
+      red[wave][CB] = ss;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (c0 == 0 && var) var[row] = (T)((double)ktt[row * ktt_stride] - (((red[0][CB] + red[1][CB]) + red[2][CB]) + red[3][CB]));
+      for (int e = 0; e < CB && c0 + e < c; ++e) mean[row * c + c0 + e] = (T)(((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]);
+    }
+    __syncthreads();   // (the next group of columns rewrites red)
+  }
+}
+
+template <typename T>
+__global__ void fit_nan_kernel(T* __restrict__ p, int64_t rows, int64_t cols, int64_t ld) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cols) return;
+  for (int64_t i = blockIdx.y; i < rows; i += gridDim.y) p[i * ld + j] = (T)NAN;
+}
+
+template <typename T>
+int readout_t(smn_fit* f, int64_t rows, const void* ktt, int64_t ktt_stride, void* mean, void* var) {
+  smn_ctx* ctx = f->ctx;
+  const T* v = reinterpret_cast<const T*>(f->at(f->n_pad, 0));
+  const T* beta = reinterpret_cast<const T*>(f->at(f->beta_row(), 0));
+  const dim3 g((unsigned)rows), b(256);
+  ProfScope ps(ctx, PROF_MISC, ctx->stream);
+#define SMN_FIT_READOUT(CB)                                                                                                  \
+  hipLaunchKernelGGL((fit_readout_kernel<T, CB>), g, b, 0, ctx->stream, v, f->lda, f->n_pad, beta, (int)f->c,                 \
+                     static_cast<const T*>(ktt), ktt_stride, static_cast<T*>(mean), static_cast<T*>(var))
+  if (f->c == 1) SMN_FIT_READOUT(1);
+  else if (f->c <= 4) SMN_FIT_READOUT(4);
+  else SMN_FIT_READOUT(8);
+#undef SMN_FIT_READOUT
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
+int readout(smn_fit* f, int64_t rows, const void* ktt, int64_t ktt_stride, void* mean, void* var) {
+  return f->dtype == SMN_F64 ? readout_t<double>(f, rows, ktt, ktt_stride, mean, var)
+                             : readout_t<float>(f, rows, ktt, ktt_stride, mean, var);
+}
+
+int fill_nan(smn_fit* f, void* p, int64_t rows, int64_t cols, int64_t ld) {
+  if (!p || rows <= 0 || cols <= 0) return SMN_OK;
+  smn_ctx* ctx = f->ctx;
+  const dim3 g((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
+  if (f->dtype == SMN_F64)
+    hipLaunchKernelGGL(fit_nan_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(p), rows, cols, ld);
+  else
+    hipLaunchKernelGGL(fit_nan_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(p), rows, cols, ld);
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
+void fit_free(smn_fit* f) {
+  if (!f) return;
+  if (f->a) (void)hipFree(f->a);
+  if (f->xs) (void)hipFree(f->xs);
+  delete f;
+}
+
+// frees a half-made state on every error return of a create entry
+struct FitGuard {
+  smn_fit* f;
+  ~FitGuard() { fit_free(f); }
+  smn_fit* release() { smn_fit* r = f; f = nullptr; return r; }
+};
+
+int fit_alloc(smn_ctx* ctx, const char* who, int dtype, int64_t n, int64_t c, int64_t capacity, int64_t d, bool fused,
+              smn_fit** out) {
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "%s: bad dtype %d", who, dtype);
+  if (n <= 0 || c <= 0) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes (n = %lld, c = %lld)", who, (long long)n, (long long)c);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: c = %lld: more than 48 output columns", who, (long long)c);
+  if (capacity < 1) return smn_fail(ctx, SMN_EINVAL, "%s: capacity = %lld must be at least 1", who, (long long)capacity);
+  smn_fit* f = new (std::nothrow) smn_fit;
+  if (!f) return smn_fail(ctx, SMN_ENOMEM, "%s: out of host memory", who);
+  FitGuard guard{f};
+  f->ctx = ctx; f->dtype = dtype; f->fused = fused;
+  f->n = n; f->c = c; f->capacity = capacity; f->d = d;
+  f->n_pad = round_up(n, kTile);
+  f->cap_pad = round_up(capacity, kTile);
+  f->n_total = f->n_pad + f->cap_pad + kTile;
+  f->lda = f->n_total;
+  const size_t abytes = f->es() * (size_t)f->n_total * (size_t)f->lda;
+  SMN_HIP(ctx, hipMalloc(&f->a, abytes));
+  f->bytes = abytes;
+  if (fused) {
+    f->kp = k_pad(dtype, d);
+    const size_t xbytes = sizeof(double) * (size_t)f->n_pad + f->es() * (size_t)f->n_pad * (size_t)f->kp;
+    SMN_HIP(ctx, hipMalloc(&f->xs, xbytes));
+    f->bytes += xbytes;
+  }
+  SMN_HIP(ctx, hipMemsetAsync(f->a, 0, abytes, ctx->stream));
+  *out = guard.release();
+  return SMN_OK;
+}
+
+// The factorisation of the leading block with Y^T as its only appended rows (in the test rows' first tile row), the heads'
+// scalars, then beta^T moved behind the test rows, whose tile rows are cleared.  prepped: aug_prep has written Y^T and shifted
+// the diagonal already.
+int fit_factor(smn_fit* f, const void* y_d, bool prepped, double ridge_rel, double ridge_abs, double* quad_h, double* logdet_h,
+               int* info_h) {
+  smn_ctx* ctx = f->ctx;
+  if (!prepped) SMN_TRY(set_aug_rows(ctx, f->dtype, f->a, f->lda, f->n_pad, f->n_pad + kTile, y_d, f->n, f->c, f->c));
+  FactorCall fc{f->dtype, f->a, f->n_pad + kTile, f->n_pad, f->lda, f->n, ridge_abs, ridge_rel, true};
+  fc.prepped = prepped;
+  SMN_TRY(cholesky_padded(ctx, fc));
+  SMN_TRY(extract_posterior(ctx, f->dtype, f->a, f->lda, f->n_pad, 0, f->c, nullptr, nullptr, 0, ctx->d_scal + 8, true));
+  double quad[48], ld = 0.0;
+  int info = 0;
+  SMN_TRY(fetch_mail(ctx, (int)f->c, quad, &ld, &info));
+  f->info = info;
+  if (info != 0) ld = std::nan("");
+  for (int64_t k = 0; k < f->c && quad_h; ++k) quad_h[k] = info != 0 ? std::nan("") : quad[k];
+  if (logdet_h) *logdet_h = ld;
+  if (info_h) *info_h = info;
+  // (columns [0, n_pad) only: what lies behind them is the creation-time Schur block -beta beta^T, which stays out of the beta rows)
+  const size_t pitch = f->es() * (size_t)f->lda;
+  SMN_HIP(ctx, hipMemcpy2DAsync(f->at(f->beta_row(), 0), pitch, f->at(f->n_pad, 0), pitch, f->es() * (size_t)f->n_pad, (size_t)kTile,
+                                hipMemcpyDeviceToDevice, ctx->stream));
+  SMN_HIP(ctx, hipMemsetAsync(f->at(f->n_pad, 0), 0, f->es() * (size_t)f->cap_pad * (size_t)f->lda, ctx->stream));
+  return SMN_OK;
+}
+
+// rows [r, round_up(r, 128)) of the test block: cleared, so that the tile-wise solve carries zeros and not an earlier chunk
+int clear_tail_rows(smn_fit* f, int64_t r) {
+  const int64_t rp = round_up(r, kTile);
+  if (rp == r) return SMN_OK;
+  SMN_HIP(f->ctx, hipMemsetAsync(f->at(f->n_pad + r, 0), 0, f->es() * (size_t)(rp - r) * (size_t)f->lda, f->ctx->stream));
+  return SMN_OK;
+}
+
+// solved rows -> outputs of one chunk.  ktt: the chunk's prior variances (stride ktt_stride).  cov: the trailing block holds
+// the lower triangle of K_tt.
+int finish_chunk(smn_fit* f, int64_t r, const void* ktt, int64_t ktt_stride, void* mean, void* var, void* cov, int64_t ldcov) {
+  smn_ctx* ctx = f->ctx;
+  const int64_t rp = round_up(r, kTile);
+  SMN_TRY(solve_rows_padded(ctx, f->dtype, f->a, f->n_pad + rp, f->n_pad, f->lda));
+  SMN_TRY(readout(f, r, ktt, ktt_stride, mean, var));
+  if (cov) {
+    SMN_TRY(schur_rows_padded(ctx, f->dtype, f->a, f->n_pad + rp, f->n_pad, f->lda));
+    SMN_TRY(extract_posterior(ctx, f->dtype, f->a, f->lda, f->n_pad, r, 0, nullptr, cov, ldcov, nullptr, false));
+  }
+  return SMN_OK;
+}
+
+int check_outputs(smn_fit* f, const char* who, int64_t t, const void* mean_d, const void* cov_d, int64_t ldcov) {
+  smn_ctx* ctx = f->ctx;
+  if (!mean_d) return smn_fail(ctx, SMN_EINVAL, "%s: mean_d is NULL", who);
+  if (t <= 0) return smn_fail(ctx, SMN_EINVAL, "%s: t = %lld must be at least 1", who, (long long)t);
+  if (cov_d) {
+    if (t > f->capacity)
+      return smn_fail(ctx, SMN_EINVAL, "%s: cov_d needs t = %lld <= capacity = %lld (the Schur block sits behind the factor)", who,
+                      (long long)t, (long long)f->capacity);
+    SMN_CHECK_LD(ctx, who, ldcov, t);
+  }
+  return SMN_OK;
+}
+
+int nan_outputs(smn_fit* f, int64_t t, void* mean_d, void* var_d, void* cov_d, int64_t ldcov) {
+  SMN_TRY(fill_nan(f, mean_d, t, f->c, f->c));
+  SMN_TRY(fill_nan(f, var_d, 1, t, t));
+  return fill_nan(f, cov_d, t, t, ldcov);
+}
+
+}  // namespace
+
+extern "C" int smn_fit_create(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                              double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                              double ridge_rel, double ridge_abs, int64_t capacity, smn_fit** out, double* quad_h,
+                              double* logdet_h, int* info_h) {
+  if (!ctx || !x_d || !y_d || !out) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  *out = nullptr;
+  if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_fit_create: d = %lld", (long long)d);
+  SMN_CHECK_LD(ctx, "smn_fit_create", ldx, d);
+  bool ntk = false;
+  SMN_TRY(split_net(ctx, &net, &ntk));
+  smn_fit* f = nullptr;
+  SMN_TRY(fit_alloc(ctx, "smn_fit_create", dtype, n, c, capacity, d, true, &f));
+  FitGuard guard{f};
+  f->net = net; f->act = act; f->num_hiddens = num_hiddens; f->ntk = ntk;
+  f->w_std = w_std; f->b_std = b_std; f->last_w_std = last_w_std;
+  SMN_TRY(pad_rows(ctx, dtype, x_d, n, ldx, d, f->xp(), f->n_pad, f->kp, f->q()));
+  BuildCall b{};
+  b.spec = BuildSpec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
+  b.x1p = f->xp(); b.ld1 = f->kp; b.rows1 = f->n_pad; b.q1 = f->q();
+  b.x2p = f->xp(); b.ld2 = f->kp; b.rows2 = f->n_pad; b.q2 = f->q();
+  b.kp = (int)f->kp; b.d = d;
+  b.symmetric = 1; b.exact_diag = 1;
+  b.store_mode = STORE_PAD_IDENTITY;
+  b.nv0 = n; b.aug0 = f->n_pad; b.nv1 = 0;
+  b.get_mask = ntk ? SMN_GET_NTK : SMN_GET_NNGP;
+  b.out_k = ntk ? nullptr : f->a; b.out_t = ntk ? f->a : nullptr; b.ldo = f->lda;
+  b.want_trace = ridge_rel != 0.0 ? 1 : 0;
+  BuildOut built;
+  SMN_TRY(run_build(ctx, b, &built));
+  const bool prepped = ridge_rel == 0.0 || built.trace;
+  if (prepped) {
+    const int64_t n_sh = (ridge_abs != 0.0 || ridge_rel != 0.0) ? n : 0;
+    SMN_TRY(aug_prep(ctx, dtype, f->a, f->lda, f->n_pad, f->n_pad + kTile, y_d, n, c, c, n_sh, ridge_abs, 0, nullptr, ridge_rel, n));
+  }
+  SMN_TRY(fit_factor(f, y_d, prepped, ridge_rel, ridge_abs, quad_h, logdet_h, info_h));
+  *out = guard.release();
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_create_from_kernel(smn_ctx* ctx, int dtype, const void* k_d, int64_t n, int64_t ldk, const void* y_d,
+                                          int64_t c, double ridge_rel, double ridge_abs, int64_t capacity, smn_fit** out,
+                                          double* quad_h, double* logdet_h, int* info_h) {
+  if (!ctx || !k_d || !y_d || !out) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  *out = nullptr;
+  SMN_CHECK_LD(ctx, "smn_fit_create_from_kernel", ldk, n);
+  smn_fit* f = nullptr;
+  SMN_TRY(fit_alloc(ctx, "smn_fit_create_from_kernel", dtype, n, c, capacity, 0, false, &f));
+  FitGuard guard{f};
+  SMN_TRY(copy_matrix(ctx, dtype, f->a, f->lda, k_d, ldk, n, n, 1));
+  SMN_TRY(fill_identity_pad(ctx, dtype, f->a, f->lda, f->n_pad, n));
+  SMN_TRY(fit_factor(f, y_d, false, ridge_rel, ridge_abs, quad_h, logdet_h, info_h));
+  *out = guard.release();
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* mean_d, void* var_d, void* cov_d,
+                               int64_t ldcov) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  if (!fit->fused) return smn_fail(ctx, SMN_EINVAL, "smn_fit_predict: the state was made from a kernel matrix (use smn_fit_apply)");
+  if (!xt_d) return smn_fail(ctx, SMN_EINVAL, "smn_fit_predict: xt_d is NULL");
+  SMN_TRY(check_outputs(fit, "smn_fit_predict", t, mean_d, cov_d, ldcov));
+  SMN_CHECK_LD(ctx, "smn_fit_predict", ldxt, fit->d);
+  if (fit->info != 0) return nan_outputs(fit, t, mean_d, var_d, cov_d, ldcov);
+  const size_t es = fit->es();
+  const BuildSpec spec{fit->dtype, fit->net, fit->act, fit->num_hiddens, fit->w_std, fit->b_std, fit->last_w_std};
+  {
+    // Workspace of the largest chunk, taken before anything is launched: the padded chunk (slot 0) and the cross build's
+    // per-row tables (slot 1: 2 (activation layers) + 2 rows of rows1 + rows2 elements, run_build; larger than the K_tt
+    // build's).  A slot that has to grow synchronises the stream, so it grows here and not between two launches of the call.
+    const int64_t rp_max = round_up(std::min(fit->capacity, t), kTile);
+    void* w = nullptr;
+    SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp_max + es * (size_t)rp_max * (size_t)fit->kp, &w));
+    SMN_TRY(smn_workspace(ctx, 1, es * (size_t)(2 * (fit->num_hiddens + 1) + 2) * (size_t)(rp_max + fit->n_pad), &w));
+  }
+  for (int64_t start = 0; start < t; start += fit->capacity) {
+    const int64_t r = std::min(fit->capacity, t - start), rp = round_up(r, kTile);
+    void* xs = nullptr;
+    SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp + es * (size_t)rp * (size_t)fit->kp, &xs));
+    double* q = static_cast<double*>(xs);
+    char* xp = reinterpret_cast<char*>(q + rp);
+    SMN_TRY(pad_rows(ctx, fit->dtype, static_cast<const char*>(xt_d) + es * (size_t)(start * ldxt), r, ldxt, fit->d, xp, rp, fit->kp, q));
+    SMN_TRY(clear_tail_rows(fit, r));
+    BuildCall b{};
+    b.spec = spec;
+    b.kp = (int)fit->kp; b.d = fit->d;
+    b.get_mask = fit->ntk ? SMN_GET_NTK : SMN_GET_NNGP;
+    b.store_mode = STORE_BOUNDS;
+    b.ldo = fit->lda;
+    b.x1p = xp; b.ld1 = fit->kp; b.rows1 = rp; b.q1 = q;
+    if (cov_d) {   // K_tt (lower tiles, exact diagonal) into the trailing block; the cross build after it leaves the same table
+      BuildCall s = b;
+      s.x2p = xp; s.ld2 = fit->kp; s.rows2 = rp; s.q2 = q;
+      s.symmetric = 1; s.exact_diag = 1;
+      s.out_rows = r; s.out_cols = r;
+      void* dst = fit->at(fit->n_pad, fit->n_pad);
+      s.out_k = fit->ntk ? nullptr : dst; s.out_t = fit->ntk ? dst : nullptr;
+      SMN_TRY(run_build(ctx, s));
+    }
+    // the cross kernel K(x_chunk, X) straight into the appended rows
+    b.x2p = fit->xp(); b.ld2 = fit->kp; b.rows2 = fit->n_pad; b.q2 = fit->q();
+    b.symmetric = 0; b.exact_diag = 0;
+    b.out_rows = r; b.out_cols = fit->n;
+    void* dst = fit->at(fit->n_pad, 0);
+    b.out_k = fit->ntk ? nullptr : dst; b.out_t = fit->ntk ? dst : nullptr;
+    BuildOut built;
+    SMN_TRY(run_build(ctx, b, &built));
+    // k_tt: the closed-form diagonal of the chunk's rows from the build's own table (what exact_diag writes)
+    const void* ktt = fit->ntk ? built.diag_t : built.diag_k;
+    SMN_TRY(finish_chunk(fit, r, ktt, 1, static_cast<char*>(mean_d) + es * (size_t)(start * fit->c),
+                         var_d ? static_cast<char*>(var_d) + es * (size_t)start : nullptr, cov_d, ldcov));
+  }
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, const void* ktt_diag_d, const void* k_tt_d,
+                             int64_t ldtt, void* mean_d, void* var_d, void* cov_d, int64_t ldcov) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  if (!k_td_d) return smn_fail(ctx, SMN_EINVAL, "smn_fit_apply: k_td_d is NULL");
+  SMN_TRY(check_outputs(fit, "smn_fit_apply", t, mean_d, cov_d, ldcov));
+  SMN_CHECK_LD(ctx, "smn_fit_apply", ldk, fit->n);
+  if (k_tt_d) SMN_CHECK_LD(ctx, "smn_fit_apply", ldtt, t);
+  if (cov_d && !k_tt_d) return smn_fail(ctx, SMN_EINVAL, "smn_fit_apply: cov_d needs k_tt_d");
+  if (var_d && !ktt_diag_d && !k_tt_d) return smn_fail(ctx, SMN_EINVAL, "smn_fit_apply: var_d needs ktt_diag_d or k_tt_d");
+  if (fit->info != 0) return nan_outputs(fit, t, mean_d, var_d, cov_d, ldcov);
+  const size_t es = fit->es();
+  for (int64_t start = 0; start < t; start += fit->capacity) {
+    const int64_t r = std::min(fit->capacity, t - start);
+    SMN_TRY(clear_tail_rows(fit, r));
+    SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(fit->n_pad, 0), fit->lda, static_cast<const char*>(k_td_d) + es * (size_t)(start * ldk),
+                        ldk, r, fit->n, 0));
+    if (cov_d) SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(fit->n_pad, fit->n_pad), fit->lda, k_tt_d, ldtt, r, r, 1));
+    const void* ktt = nullptr;
+    int64_t stride = 1;
+    if (ktt_diag_d) ktt = static_cast<const char*>(ktt_diag_d) + es * (size_t)start;
+    else if (k_tt_d) { ktt = static_cast<const char*>(k_tt_d) + es * (size_t)(start * ldtt + start); stride = ldtt + 1; }
+    SMN_TRY(finish_chunk(fit, r, ktt, stride, static_cast<char*>(mean_d) + es * (size_t)(start * fit->c),
+                         (var_d && ktt) ? static_cast<char*>(var_d) + es * (size_t)start : nullptr, cov_d, ldcov));
+  }
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_info(smn_fit* fit, int64_t* n, int64_t* c, int64_t* capacity, size_t* bytes) {
+  if (!fit) return SMN_EINVAL;
+  if (n) *n = fit->n;
+  if (c) *c = fit->c;
+  if (capacity) *capacity = fit->capacity;
+  if (bytes) *bytes = fit->bytes;
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_destroy(smn_fit* fit) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  (void)hipStreamSynchronize(ctx->stream);   // nothing the state's calls issued may still run on its memory
+  fit->ctx = nullptr;
+  fit_free(fit);
+  return SMN_OK;
+}

@@ -103,6 +103,9 @@ void gram_cache_drop(smn_ctx* ctx, bool free_memory);
 struct BuildOut {
   int64_t corner_col = 0;   // first column of the corner of a split build, still being built on the bulk stream (0: none)
   bool trace = false;       // the trace of the kernel's diagonal is in ctx->d_scal[1]
+  // the closed-form diagonals K(x1_i, x1_i) / Theta(x1_i, x1_i) of the rows1 operand (the table exact_diag reads, element type
+  // = the build's; diag_t is Theta only under SMN_GET_NTK): in workspace slot 1, valid until the context's next build
+  const void* diag_k = nullptr; const void* diag_t = nullptr;
 };
 int run_build(smn_ctx* ctx, const BuildCall& c, BuildOut* out = nullptr);   // out: needed by split_corner
 // TB for a split build of T tile rows on this context (0: do not split)
@@ -243,6 +246,9 @@ int aug_prep(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, int64_
 // the mailbox after a launch that published into it (extract_posterior(..., publish = true)): synchronise and read
 int fetch_mail(smn_ctx* ctx, int nq, double* quad_h, double* logdet, int* info);
 int solve_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda);
+// Schur update of solved appended rows: the lower tiles of a[n_factor:n_total, n_factor:n_total] -= R R^T with R = rows
+// [n_factor, n_total) x columns [0, n_factor) -- the far update of cholesky_padded, one launch per super-panel of columns
+int schur_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda);
 int transpose_matrix(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* src, int64_t lds,
                      int64_t rows, int64_t cols);   // dst[c, r] = src[r, c]
 // dst[i, j] = src[n-1-j, n-1-i] for j <= i  (J L^T J);  transpose with the src rows / dst rows reversed

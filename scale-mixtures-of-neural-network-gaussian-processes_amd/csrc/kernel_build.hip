@@ -787,6 +787,9 @@ int run_build_t(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
   hipLaunchKernelGGL(diag_tables_kernel<T>, dim3((unsigned)((c.rows1 + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
                      c.q1, c.rows1, prog, tab1, tlen, dg1, dgt1, progs_d, tab_bs);
   SMN_CHECK_LAUNCH(ctx);
+  if (out) {
+    out->diag_k = dg1; out->diag_t = dgt1;
+  }
   if (c.want_trace && c.symmetric && c.exact_diag && c.nbatch == 0 && !c.shard && c.nv0 > 0) {
     // (an NTK-only build: the matrix the trace belongs to is Theta, its exact diagonal the second table)
     hipLaunchKernelGGL(table_trace_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, (c.get_mask & SMN_GET_NNGP) ? dg1 : dgt1, c.nv0,

@@ -1,0 +1,265 @@
+"""Fit once, predict many: a fitted exact-GP posterior that lives on the device (csrc/fit.hip, the smn_fit_* entries).
+
+`SPR.posterior()` / `MultiSPR.posterior()` factor K~ = K_dd + eps tr(K_dd)/N I once -- the posterior of the models' own
+`predict` -- and return a FittedPosterior that answers `predict`, `test_nll`, `sample`, `classify` for test sets of any size at
+O(N^2 T) per call instead of O(N^3).  The object is a snapshot: the hyper-parameters, the ridge, the likelihood's (df, scale)
+and the Student-t quadratic form are those of the moment it was made; moving the model's variables afterwards does not reach
+it.  `gradient_descent_mse_ensemble(..., cache=True)` serves its t = None posterior from one of these.
+
+MLP / dense-ResNet kernel functions (under NNGPKernel or NTKKernel) take the fused entries: the cross kernel K(x_chunk, X) is
+built straight into the state.  The conv kernels and any other callable take the matrix form: K_dd once at creation, then per
+chunk of test points kernel_fn(x_chunk, x_train), the prior variances (smn_kernel_conv_diag for the conv kernels) and, for
+cov="full", kernel_fn(x_chunk, None).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import DeviceArray, as_device
+from .nt_kernels import CnnKernelFn, KernelFn
+
+__all__ = ["FittedPosterior", "chunks"]
+
+
+def chunks(T, capacity):
+    """[(start, rows)] covering T test rows in order, at most `capacity` rows each: the chunking of smn_fit_predict."""
+    T, capacity = int(T), int(capacity)
+    if T < 0 or capacity < 1:
+        raise ValueError("chunks: T must be >= 0 and capacity >= 1, got T = %d, capacity = %d" % (T, capacity))
+    return [(s, min(capacity, T - s)) for s in range(0, T, capacity)]
+
+
+def _rows(arr, start, rows):
+    """Rows [start, start + rows) of a host array or of a plain row-major DeviceArray (a view: no copy)."""
+    if not isinstance(arr, DeviceArray):
+        return arr[start:start + rows]
+    per_row = int(np.prod(arr.shape[1:])) if len(arr.shape) > 1 else 1
+    view = DeviceArray(arr.ctx, (rows,) + tuple(arr.shape[1:]), arr.dtype,
+                       ptr=C.c_void_p(arr.ptr.value + start * per_row * arr.dtype.itemsize), owner=False)
+    view._base = arr if arr._base is None else arr._base
+    return view
+
+
+def _as2d(arr):
+    """[N, ...] -> [N, features] of a plain row-major DeviceArray, as a view (what KernelFn does by a host round trip)."""
+    if len(arr.shape) == 2:
+        return arr
+    view = DeviceArray(arr.ctx, (arr.shape[0], int(np.prod(arr.shape[1:])) if len(arr.shape) > 1 else 1), arr.dtype, ptr=arr.ptr,
+                       owner=False)
+    view._base = arr if arr._base is None else arr._base
+    return view
+
+
+def _at(arr, elems):
+    return C.c_void_p(arr.ptr.value + int(elems) * arr.dtype.itemsize)
+
+
+class FittedPosterior:
+    """See the module docstring.  Attributes: quad [C] (y_k^T K~^-1 y_k), logdet (log det K~), info (0, or the failing pivot
+    of a matrix that is not positive definite: every prediction is then NaN), num_data, num_outputs, capacity, nbytes (device
+    memory the state owns), hyper (the snapshot: w_std, b_std, last_w_std, eps, df, scale)."""
+
+    def __init__(self, kernel_fn, x, y, *, ridge_rel=0.0, ridge_abs=0.0, capacity=2048, mode="nngp", ctx=None):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be at least 1, got %d" % capacity)
+        if mode not in ("nngp", "ntk"):
+            raise ValueError("mode must be 'nngp' or 'ntk', got %r" % (mode,))
+        self.ctx = ctx or getattr(kernel_fn, "ctx", None) or getattr(x, "ctx", None) or _lib.default_context()
+        self._handle = None
+        self.kernel_fn, self.mode, self.capacity = kernel_fn, mode, capacity
+        self.x_train = x
+        self.dtype = np.dtype(x.dtype)
+        self.num_data = int(x.shape[0])
+        self.num_outputs = int(y.shape[1]) if len(y.shape) > 1 else 1
+        self.fused = isinstance(kernel_fn, KernelFn)
+        self.multi = False
+        self.y_mean, self.y_std = 0.0, 1.0
+        self.df, self.scale, self.student_quad = 0.0, 1.0, None
+        self.hyper = {"eps": float(ridge_rel)}
+        for name in ("w_std", "b_std", "last_w_std"):
+            if hasattr(kernel_fn, name):
+                self.hyper[name] = float(getattr(kernel_fn, name))
+        n, c, code = self.num_data, self.num_outputs, _lib.dtype_code(self.dtype)
+        quad, logdet, info, handle = (C.c_double * c)(), C.c_double(), C.c_int(), C.c_void_p()
+        if self.fused:
+            x2 = _as2d(x)
+            self.num_features = int(x2.shape[1])
+            net, act, depth, w, b, lw = kernel_fn.with_cov(mode).params      # "ntk": net carries SMN_NET_NTK
+            self.ctx.call("smn_fit_create", code, net, act, depth, w, b, lw, x2.ptr, n, self.num_features, self.num_features,
+                          y.ptr, c, float(ridge_rel), float(ridge_abs), capacity, C.byref(handle), quad, C.byref(logdet),
+                          C.byref(info))
+        else:
+            k_dd = self._kernel(x, None, fill="lower")
+            self.ctx.call("smn_fit_create_from_kernel", code, k_dd.ptr, n, n, y.ptr, c, float(ridge_rel), float(ridge_abs),
+                          capacity, C.byref(handle), quad, C.byref(logdet), C.byref(info))
+        self._handle = handle
+        self.quad = np.array(list(quad), dtype=np.float64)
+        self.logdet, self.info = float(logdet.value), int(info.value)
+        nbytes = C.c_size_t()
+        self.ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
+        self.nbytes = int(nbytes.value)
+
+    @classmethod
+    def from_model(cls, model, capacity=2048):
+        """The posterior of `model.predict` at the model's current hyper-parameters (SPR or MultiSPR)."""
+        from .spax.kernels import NTKKernel
+        if not hasattr(model.likelihood, "lml_params"):
+            raise NotImplementedError("posterior() needs a Gaussian or Student-t likelihood")
+        kernel_fn = model.kernel.get_kernel_fn()
+        mode = "ntk" if isinstance(model.kernel, NTKKernel) else "nngp"
+        df, scale = model.likelihood.lml_params()
+        student_quad = model._draws_quad(kernel_fn, scale) if df > 0.0 else None
+        post = cls(kernel_fn, model.x_data, model.y_data, ridge_rel=model.eps.safe_value, capacity=capacity, mode=mode,
+                   ctx=model.x_data.ctx)
+        post.multi = hasattr(model, "num_outputs")
+        post.y_mean, post.y_std = float(model.y_mean), float(model.y_std)
+        post.df, post.scale, post.student_quad = float(df), float(scale), student_quad
+        post.hyper.update(df=float(df), scale=float(scale))
+        return post
+
+    # ---- lifetime
+    def close(self):
+        """Free the device state (idempotent).  A state whose context is already closed is left to the driver."""
+        handle, self._handle = getattr(self, "_handle", None), None
+        if handle is not None and getattr(self.ctx, "handle", None):
+            self.ctx.call_on("smn_fit_destroy", handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- kernel pieces of the matrix form
+    def _kernel(self, x1, x2, fill="full"):
+        if isinstance(self.kernel_fn, CnnKernelFn):
+            if self.mode != "nngp":
+                raise NotImplementedError("the conv kernels are NNGP-only")
+            return self.kernel_fn(x1, x2, get="nngp", fill=fill)
+        host = lambda a: None if a is None else np.asarray(a)   # noqa: E731  (what predict_fn hands such a callable)
+        return as_device(self.kernel_fn(host(x1), host(x2), self.mode), self.ctx, dtype=self.dtype)
+
+    def _prior_var(self, xc):
+        """K(x_t, x_t) [rows] for the matrix form: the per-image pass of the conv kernels (the bits of their symmetric
+        diagonal); for any other callable the diagonal of kernel_fn(x, None)."""
+        fn = self.kernel_fn
+        if isinstance(fn, CnnKernelFn):
+            xd = as_device(xc, self.ctx, dtype=self.dtype)
+            out = self.ctx.empty((xd.shape[0],), self.dtype)
+            act, depth, w, b, lw = fn.params
+            self.ctx.call("smn_kernel_conv_diag", xd.dcode, 0 if fn.entry == "smn_kernel_cnn" else 1, act, depth, w, b, lw,
+                          xd.ptr, xd.shape[0], xd.shape[1], xd.shape[2], xd.shape[3], out.ptr)
+            return out
+        return self.ctx.to_device(np.ascontiguousarray(self._kernel(xc, None).diagonal(), dtype=self.dtype))
+
+    # ---- predictions
+    def predict(self, x, cov="diag"):
+        """(mean [T,C], var [T]) for cov="diag", (mean, cov [T,T]) for cov="full", mean alone for cov=None: device arrays in
+        normalised units.  Any T for "diag" / None -- nothing of size T x T is formed --; "full" needs T <= capacity."""
+        if cov not in ("diag", "full", None):
+            raise ValueError("cov must be 'diag', 'full' or None, got %r" % (cov,))
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        ctx, c = self.ctx, self.num_outputs
+        xt = as_device(x, ctx, dtype=self.dtype)
+        t = int(xt.shape[0])
+        if t < 1:
+            raise ValueError("predict needs at least one test point")
+        if cov == "full" and t > self.capacity:
+            raise ValueError("cov='full' needs T = %d <= capacity = %d (the T x T Schur block sits behind the factor); make the "
+                             "posterior with a larger capacity or ask for cov='diag'" % (t, self.capacity))
+        mean = ctx.empty((t, c), self.dtype)
+        var = ctx.empty((t,), self.dtype) if cov == "diag" else None
+        full = ctx.empty((t, t), self.dtype) if cov == "full" else None
+        vptr, cptr = (None if var is None else var.ptr), (None if full is None else full.ptr)
+        if self.fused:
+            xt = _as2d(xt)
+            if xt.shape[1] != self.num_features:
+                raise ValueError("x has %d features, the training data %d" % (xt.shape[1], self.num_features))
+            ctx.call_on("smn_fit_predict", self._handle, xt.ptr, t, xt.shape[1], mean.ptr, vptr, cptr, t)
+        else:
+            n = self.num_data
+            for start, rows in chunks(t, self.capacity):
+                xc = _rows(xt, start, rows)
+                k_td = self._kernel(xc, self.x_train)
+                ktt = self._prior_var(xc) if cov == "diag" else None
+                k_tt = self._kernel(xc, None) if cov == "full" else None
+                ctx.call_on("smn_fit_apply", self._handle, k_td.ptr, rows, n, None if ktt is None else ktt.ptr,
+                            None if k_tt is None else k_tt.ptr, rows, _at(mean, start * c),
+                            None if var is None else _at(var, start), cptr, t)
+        if cov is None:
+            return mean
+        return mean, (var if cov == "diag" else full)
+
+    def _marginals(self, x):
+        mean, var = self.predict(x, cov="diag")
+        return (np.asarray(mean.raw_numpy(), dtype=np.float64) * self.y_std + self.y_mean,
+                np.asarray(var.raw_numpy(), dtype=np.float64) * self.y_std ** 2)
+
+    def test_nll(self, x, y):
+        """The model's test_nll (SPR: mean over points; MultiSPR: mean over points of the sum over outputs) from the
+        predictive marginals alone: any number of test points."""
+        from .spax.likelihoods import _norm_logpdf, _t_logpdf
+        ms, var = self._marginals(x)
+        t, c = ms.shape
+        ys = np.asarray(y, dtype=np.float64).reshape(t, c) * self.y_std + self.y_mean
+        if self.df > 0.0:
+            cond_df = self.df + self.num_data * c
+            sigma = np.sqrt((self.df + self.student_quad) / cond_df * self.scale * var)
+            lp = _t_logpdf(ys, cond_df, ms, sigma[:, None])
+        else:
+            lp = _norm_logpdf(ys, ms, np.sqrt(var)[:, None])
+        return -float(np.mean(np.sum(lp, axis=1)))
+
+    def predictive_params(self):
+        """(df_post, shape) of the joint predictive law, as the model's predictive_params."""
+        if not self.df > 0.0:
+            return None, 1.0
+        df_post = self.df + self.num_data * self.num_outputs
+        return df_post, (self.df + self.student_quad) / df_post * self.scale
+
+    def sample(self, key, x, num_samples, jitter=1e-6):
+        """num_samples joint draws of the latent function at x ([S,T], or [S,T,C] from a MultiSPR): sample_posterior's
+        composition -- smn_cholesky of the covariance with the relative ridge `jitter`, then smn_mvn_draws -- on
+        predict(x, cov="full"); T <= capacity."""
+        from .spax.priors import split_key
+        seed, point0 = split_key(key)
+        s = int(num_samples)
+        if s < 1:
+            raise ValueError("num_samples must be at least 1")
+        df_post, shape = self.predictive_params()
+        mean, cov = self.predict(x, cov="full")
+        ctx = self.ctx
+        t, c = mean.shape
+        out_shape = (s, t, c) if self.multi else (s, t)
+        nan = lambda: ctx.to_device(np.full(out_shape, np.nan, dtype=mean.dtype))   # noqa: E731
+        if df_post is not None and not (np.isfinite(shape) and shape > 0.0):
+            return nan()
+        info = C.c_int()
+        ctx.call("smn_cholesky", cov.dcode, cov.ptr, t, t, t, t, 0.0, float(jitter), C.byref(info), None)
+        if info.value != 0:
+            return nan()
+        out = ctx.empty(out_shape, mean.dtype)
+        ctx.call("smn_mvn_draws", mean.dcode, mean.ptr, cov.ptr, t, t, c, s, df_post or 0.0, shape, seed, point0, None, None,
+                 out.ptr)
+        return out
+
+    def classify(self, x):
+        """Predicted labels (a posterior made from a MultiSPR): argmax_c of the posterior mean, first maximum."""
+        if not self.multi:
+            raise NotImplementedError("classify / accuracy belong to a posterior made from a MultiSPR")
+        return np.argmax(np.asarray(self.predict(x, cov=None).raw_numpy(), dtype=np.float64), axis=1)
+
+    def accuracy(self, x, labels):
+        return float(np.mean(self.classify(x) == np.asarray(labels).reshape(-1)))

@@ -30,8 +30,22 @@ class PredictResult(tuple):
     evals = None
 
 
-def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, diag_reg_absolute_scale=False,
-                                  learning_rate=1.0):
+def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, diag_reg_absolute_scale=False, *args,
+                                  cache=False, cache_capacity=2048, learning_rate=1.0):
+    """Returns predict_fn(t=None, x_test=None, get="nngp", compute_cov=True) for the ensemble trained on (x_train, y_train)
+    with the RELATIVE ridge diag_reg (absolute with diag_reg_absolute_scale); learning_rate scales the times of t=....
+    A sixth positional argument is learning_rate, as it always was.
+
+    cache=True: predict_fn(t=None, get="nngp" | "ntk_gp") is served from a fitted state (posterior.FittedPosterior) made
+    on the first such call and kept -- O(N^2 T) per call instead of a factorisation per call.  cache_capacity is that
+    state's capacity (test rows per chunk); a compute_cov=True call with more test points refits it with that many.
+    get="ntk", t=... and the default cache=False take the paths they always took."""
+    if args:
+        if len(args) > 1:
+            raise TypeError("gradient_descent_mse_ensemble() takes at most 6 positional arguments (%d given)" % (5 + len(args)))
+        if learning_rate != 1.0:
+            raise TypeError("gradient_descent_mse_ensemble() got multiple values for argument 'learning_rate'")
+        learning_rate = args[0]
     ctx = getattr(kernel_fn, "ctx", None) or (x_train.ctx if isinstance(x_train, _lib.DeviceArray) else default_context())
     x = as_device(x_train, ctx)
     y = as_device(np.asarray(y_train).reshape(x.shape[0], -1) if not isinstance(y_train, _lib.DeviceArray) else y_train,
@@ -51,6 +65,8 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
         mode = "ntk" if get == "ntk_gp" else "nngp"
         xt = x if x_test is None else as_device(x_test, ctx, dtype=x.dtype)
         tt = xt.shape[0]
+        if cache:
+            return _predict_cached(mode, xt, tt, compute_cov)
         mean = ctx.empty((tt, c), x.dtype)
         cov = ctx.empty((tt, tt), x.dtype)
         quad = (C.c_double * c)()
@@ -73,6 +89,22 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
         res.quad = np.array(list(quad))
         res.logdet = logdet.value
         res.info = info.value
+        return res if compute_cov else res[0]
+
+    fits = {}
+
+    def _predict_cached(mode, xt, tt, compute_cov):
+        from .posterior import FittedPosterior
+        post = fits.get(mode)
+        if post is None or (compute_cov and tt > post.capacity):
+            rel, ab = (0.0, float(diag_reg)) if diag_reg_absolute_scale else (float(diag_reg), 0.0)
+            if post is not None:
+                post.close()
+            post = fits[mode] = FittedPosterior(kernel_fn, x, y, ridge_rel=rel, ridge_abs=ab, mode=mode, ctx=ctx,
+                                                capacity=max(int(cache_capacity), tt if compute_cov else 1))
+        out = post.predict(xt, cov="full" if compute_cov else None)
+        res = PredictResult(out if compute_cov else (out,))
+        res.quad, res.logdet, res.info = post.quad.copy(), post.logdet, post.info
         return res if compute_cov else res[0]
 
     def _predict_gd(t, x_test, get, compute_cov):

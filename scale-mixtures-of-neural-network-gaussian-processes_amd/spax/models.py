@@ -153,6 +153,14 @@ class _DrawsMixin:
     def _draws_quad(self, kernel_fn, scale):
         return self._student_quad_f64(kernel_fn, scale)
 
+    def posterior(self, capacity=2048):
+        """Fit once, predict many: a FittedPosterior (posterior.py) of this model at its current hyper-parameters -- the
+        factor of K~ = K_dd + eps tr(K_dd)/N I stays on the device and predict / test_nll / sample / classify on it cost
+        O(N^2 T) per call, for test sets of any size (chunks of `capacity` points; a full covariance needs T <= capacity).
+        A snapshot: later changes to the model's variables do not reach it.  The model's own methods are unaffected."""
+        from ..posterior import FittedPosterior
+        return FittedPosterior.from_model(self, capacity=capacity)
+
     def predictive_params(self):
         """(df_post, shape) of the predictive law in normalised units.  Gaussian likelihood: (None, 1.0), no device work.
         Student-t: df_post = 2a + N C and shape = (2a + quad) / df_post * b/a with quad = y^T ((b/a) K + 1e-6 I)^-1 y, the
