@@ -13,6 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from _kernel_budget import fast_erf_allowance  # noqa: E402
 from _tol import relerr  # noqa: E402
 
 Z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nngp_mp_golden.npz"))
@@ -221,10 +222,9 @@ def test_composite_kernels_against_mp(name, t, net, act):
                 if lbl == "nngp-only" and t == "f32" and net == "mlp" and act == "erf":
                     # FAST erf (asin_fast): its error is ABSOLUTE, <= 2.6e-7 on asin over [-1, 1] (nngp_math.hpp), not relative
                     # to the entry's scale -- at small row norms it dominates the budget (d1 / norms sets: 0.2 % relative on an
-                    # entry of 2e-5).  Each layer injects lw^2 (2/pi) 2.6e-7 and the next layers amplify it by at most
-                    # w^2 Kdot <= 4 w^2 / pi (Kdot = 4 / (pi sqrt((1+2q)(1+2q') - 4K^2)) <= 4 / pi).
-                    amp = 4 * w * w / np.pi
-                    allow = allow + lw * lw * (2 / np.pi) * 2.6e-7 * sum(amp ** i for i in range(Ln))
+                    # entry of 2e-5).  The allowance (injected per layer, amplified by the layers behind it) is shared with
+                    # test_gpu_kernel_budget.py: _kernel_budget.fast_erf_allowance.
+                    allow = allow + fast_erf_allowance(Ln, w, lw)
                 allows[lbl] = allow
                 r = float(np.max(err / allow))
                 worst = max(worst, r)
