@@ -163,17 +163,13 @@ __global__ void extract_posterior_kernel(const T* __restrict__ a, int64_t lda, i
 
 }  // namespace
 
-#define DISPATCH_T(dtype, expr_f32, expr_f64) \
-  do {                                        \
-    if ((dtype) == SMN_F64) { expr_f64; } else { expr_f32; } \
-  } while (0)
-
 int fill_identity_pad(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t n_pad, int64_t n_valid) {
   if (n_pad <= n_valid) return SMN_OK;
   const unsigned g = (unsigned)((n_pad - n_valid + 255) / 256);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(identity_pad_kernel<float>, dim3(g), dim3(256), 0, ctx->stream, static_cast<float*>(a), lda, n_pad, n_valid),
-             hipLaunchKernelGGL(identity_pad_kernel<double>, dim3(g), dim3(256), 0, ctx->stream, static_cast<double*>(a), lda, n_pad, n_valid));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(identity_pad_kernel<T>, dim3(g), dim3(256), 0, ctx->stream, static_cast<T*>(a), lda, n_pad, n_valid);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -182,9 +178,10 @@ int copy_matrix(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* src
                 int64_t cols, int lower_only) {
   if (rows <= 0 || cols <= 0) return SMN_OK;
   dim3 g((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(copy_matrix_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(dst), ldd, static_cast<const float*>(src), lds, rows, cols, lower_only),
-             hipLaunchKernelGGL(copy_matrix_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(dst), ldd, static_cast<const double*>(src), lds, rows, cols, lower_only));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(copy_matrix_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(dst), ldd, static_cast<const T*>(src), lds, rows, cols, lower_only);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -193,18 +190,20 @@ int transpose_matrix(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void
                      int64_t cols) {
   if (rows <= 0 || cols <= 0) return SMN_OK;
   dim3 g((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), b(32, 8);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(transpose_kernel<float>, g, b, 0, ctx->stream, static_cast<float*>(dst), ldd, static_cast<const float*>(src), lds, rows, cols),
-             hipLaunchKernelGGL(transpose_kernel<double>, g, b, 0, ctx->stream, static_cast<double*>(dst), ldd, static_cast<const double*>(src), lds, rows, cols));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(transpose_kernel<T>, g, b, 0, ctx->stream, static_cast<T*>(dst), ldd, static_cast<const T*>(src), lds, rows, cols);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
 
 int flip_transpose_lower(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* src, int64_t lds, int64_t n) {
   dim3 g((unsigned)((n + 255) / 256), (unsigned)(n < 32768 ? n : 32768));
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(flip_transpose_lower_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(dst), ldd, static_cast<const float*>(src), lds, n),
-             hipLaunchKernelGGL(flip_transpose_lower_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(dst), ldd, static_cast<const double*>(src), lds, n));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(flip_transpose_lower_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(dst), ldd, static_cast<const T*>(src), lds, n);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -213,9 +212,10 @@ int transpose_flip(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* 
                    int64_t cols, int flip_src_rows, int flip_dst_rows) {
   if (rows <= 0 || cols <= 0) return SMN_OK;
   dim3 g((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(transpose_flip_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(dst), ldd, static_cast<const float*>(src), lds, rows, cols, flip_src_rows, flip_dst_rows),
-             hipLaunchKernelGGL(transpose_flip_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(dst), ldd, static_cast<const double*>(src), lds, rows, cols, flip_src_rows, flip_dst_rows));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(transpose_flip_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(dst), ldd, static_cast<const T*>(src), lds, rows, cols, flip_src_rows, flip_dst_rows);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -224,9 +224,10 @@ int set_aug_rows(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, in
                  int64_t c, int64_t ldy) {
   if (c <= 0) return SMN_OK;
   dim3 g((unsigned)((ncols + 255) / 256), (unsigned)c);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(set_aug_rows_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(a), lda, row0, ncols, static_cast<const float*>(y), n, c, ldy),
-             hipLaunchKernelGGL(set_aug_rows_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(a), lda, row0, ncols, static_cast<const double*>(y), n, c, ldy));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(set_aug_rows_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(a), lda, row0, ncols, static_cast<const T*>(y), n, c, ldy);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -236,9 +237,10 @@ int extract_posterior(smn_ctx* ctx, int dtype, const void* a, int64_t lda, int64
   const int64_t w = (t > c ? t : c) > 1 ? (t > c ? t : c) : 1;
   dim3 g((unsigned)((w + 255) / 256), (unsigned)(t + 1 < 32768 ? t + 1 : 32768));
   double* mail = publish ? ctx->d_mail : nullptr;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(extract_posterior_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<const float*>(a), lda, aug0, t, c, static_cast<float*>(mean), static_cast<float*>(cov), ldcov, quad_dev, mail, ctx->d_scal, ctx->d_info),
-             hipLaunchKernelGGL(extract_posterior_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<const double*>(a), lda, aug0, t, c, static_cast<double*>(mean), static_cast<double*>(cov), ldcov, quad_dev, mail, ctx->d_scal, ctx->d_info));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(extract_posterior_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<const T*>(a), lda, aug0, t, c, static_cast<T*>(mean), static_cast<T*>(cov), ldcov, quad_dev, mail, ctx->d_scal, ctx->d_info);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -248,9 +250,10 @@ int aug_prep(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, int64_
   if (c <= 0 || n_shift > ncols || col0 < 0 || col0 >= ncols) return smn_fail(ctx, SMN_EINVAL, "aug_prep: bad sizes");
   if (!st) st = ctx->stream;
   dim3 g((unsigned)((ncols - col0 + 255) / 256), (unsigned)c);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(aug_prep_kernel<float>, g, dim3(256), 0, st, static_cast<float*>(a), lda, row0, col0, ncols, static_cast<const float*>(y), n, c, ldy, n_shift, jitter_abs, ctx->d_scal, ctx->d_info, ridge_rel, n_trace),
-             hipLaunchKernelGGL(aug_prep_kernel<double>, g, dim3(256), 0, st, static_cast<double*>(a), lda, row0, col0, ncols, static_cast<const double*>(y), n, c, ldy, n_shift, jitter_abs, ctx->d_scal, ctx->d_info, ridge_rel, n_trace));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(aug_prep_kernel<T>, g, dim3(256), 0, st, static_cast<T*>(a), lda, row0, col0, ncols, static_cast<const T*>(y), n, c, ldy, n_shift, jitter_abs, ctx->d_scal, ctx->d_info, ridge_rel, n_trace);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }

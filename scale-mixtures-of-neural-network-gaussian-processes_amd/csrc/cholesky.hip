@@ -1537,41 +1537,29 @@ int cholesky_t(smn_ctx* ctx, const FactorCall& f) {
 int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const void* z, int64_t kcols, int64_t n,
                       void* neg_inv, int64_t ldo, void* alpha, double* quad_dev, int64_t c, int64_t ldz) {
   const int64_t t = (n + kTile - 1) / kTile, ntiles = t * (t + 1) / 2;
-  if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx)); else SMN_TRY(set_lds_attrs<float>(ctx));
-  {
-    ProfScope ps(ctx, PROF_TRAIL, ctx->stream);
-    ctx->prof_flops[PROF_TRAIL] += 2.0 * kTile * kTile * (double)kTile * (double)(t * (t + 1) * (t + 2) / 6);
-    if (dtype == SMN_F64) {
-      SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(syrk_rows_kernel<double>), MainTile<double>::LDS_BYTES));
-      hipLaunchKernelGGL(syrk_rows_kernel<double>, dim3((unsigned)ntiles), dim3(256), MainTile<double>::LDS_BYTES, ctx->stream,
-                         static_cast<const double*>(x), ldx, kcols, static_cast<double*>(neg_inv), ldo, n);
-    } else {
-      SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(syrk_rows_kernel<float>), MainTile<float>::LDS_BYTES));
-      hipLaunchKernelGGL(syrk_rows_kernel<float>, dim3((unsigned)ntiles), dim3(256), MainTile<float>::LDS_BYTES, ctx->stream,
-                         static_cast<const float*>(x), ldx, kcols, static_cast<float*>(neg_inv), ldo, n);
+  return by_dtype(dtype, [&](auto e) -> int {
+    using T = decltype(e);
+    SMN_TRY(set_lds_attrs<T>(ctx));
+    {
+      ProfScope ps(ctx, PROF_TRAIL, ctx->stream);
+      ctx->prof_flops[PROF_TRAIL] += 2.0 * kTile * kTile * (double)kTile * (double)(t * (t + 1) * (t + 2) / 6);
+      SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(syrk_rows_kernel<T>), MainTile<T>::LDS_BYTES));
+      hipLaunchKernelGGL(syrk_rows_kernel<T>, dim3((unsigned)ntiles), dim3(256), MainTile<T>::LDS_BYTES, ctx->stream,
+                         static_cast<const T*>(x), ldx, kcols, static_cast<T*>(neg_inv), ldo, n);
     }
-  }
-  SMN_CHECK_LAUNCH(ctx);
-  const unsigned gb = (unsigned)((n + 3) / 4);
-  if (c > 1) {   // c right-hand sides: alpha [n, c], quad_dev [c]
-    const unsigned gm = gb > (unsigned)c ? gb : (unsigned)c;
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL((rows_dot_multi_kernel<double, 8>), dim3(gm), dim3(256), 0, ctx->stream, static_cast<const double*>(x), ldx,
-                         static_cast<const double*>(z), ldz, kcols, n, (int)c, static_cast<double*>(alpha), quad_dev);
-    else
-      hipLaunchKernelGGL((rows_dot_multi_kernel<float, 8>), dim3(gm), dim3(256), 0, ctx->stream, static_cast<const float*>(x), ldx,
-                         static_cast<const float*>(z), ldz, kcols, n, (int)c, static_cast<float*>(alpha), quad_dev);
+    SMN_CHECK_LAUNCH(ctx);
+    const unsigned gb = (unsigned)((n + 3) / 4);
+    if (c > 1) {   // c right-hand sides: alpha [n, c], quad_dev [c]
+      const unsigned gm = gb > (unsigned)c ? gb : (unsigned)c;
+      hipLaunchKernelGGL((rows_dot_multi_kernel<T, 8>), dim3(gm), dim3(256), 0, ctx->stream, static_cast<const T*>(x), ldx,
+                         static_cast<const T*>(z), ldz, kcols, n, (int)c, static_cast<T*>(alpha), quad_dev);
+    } else {
+      hipLaunchKernelGGL(rows_dot_kernel<T>, dim3(gb), dim3(256), 0, ctx->stream, static_cast<const T*>(x), ldx,
+                         static_cast<const T*>(z), kcols, n, static_cast<T*>(alpha), quad_dev);
+    }
     SMN_CHECK_LAUNCH(ctx);
     return SMN_OK;
-  }
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(rows_dot_kernel<double>, dim3(gb), dim3(256), 0, ctx->stream, static_cast<const double*>(x), ldx,
-                       static_cast<const double*>(z), kcols, n, static_cast<double*>(alpha), quad_dev);
-  else
-    hipLaunchKernelGGL(rows_dot_kernel<float>, dim3(gb), dim3(256), 0, ctx->stream, static_cast<const float*>(x), ldx,
-                       static_cast<const float*>(z), kcols, n, static_cast<float*>(alpha), quad_dev);
-  SMN_CHECK_LAUNCH(ctx);
-  return SMN_OK;
+  });
 }
 
 int cholesky_padded(smn_ctx* ctx, const FactorCall& f) {
@@ -1582,7 +1570,7 @@ int cholesky_padded(smn_ctx* ctx, const FactorCall& f) {
     return smn_fail(ctx, SMN_EINVAL, "cholesky_padded: matrix must be 16-byte aligned");
   if (f.id0 >= 0 && (f.id0 < f.n_factor || f.id0 % kTile || f.id1 < f.id0 || f.id1 > f.n_total))
     return smn_fail(ctx, SMN_EINVAL, "cholesky_padded: bad identity-row hint");
-  return f.dtype == SMN_F64 ? cholesky_t<double>(ctx, f) : cholesky_t<float>(ctx, f);
+  return by_dtype(f.dtype, [&](auto e) { return cholesky_t<decltype(e)>(ctx, f); });
 }
 
 // Solve-only sweep: rows [n_factor, n_total) of `a` <- rows * L^-T with L = the (already factored)
@@ -1598,37 +1586,30 @@ int solve_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t
   int64_t S = ctx->super_panel / PB * PB;
   if (S < PB) S = PB;
   const FactorCall plain{};   // one problem, no identity rows
-  auto upd = [&](int64_t c0, int64_t k0, int64_t K, int64_t tiles_n) -> int {
-    const int tag = K >= 256 ? 1 : 0;   // the pipelined K loop from K = 256 on (profile category: trailing update)
-    if (dtype == SMN_F64) return launch_update<double>(ctx, plain, st, static_cast<double*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
-    return launch_update<float>(ctx, plain, st, static_cast<float*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
-  };
-  if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx));
-  else SMN_TRY(set_lds_attrs<float>(ctx));
-  for (int64_t s0 = 0; s0 < n_factor; s0 += S) {
-    const int64_t s_end = (n_factor - s0 < S) ? n_factor : s0 + S;
-    for (int64_t js = s0; js < s_end; js += PB) {
-      // appended rows only: C = a[n_factor:, js:js+128] -= a[n_factor:, s0:js] * a[js:js+128, s0:js]^T
-      if (js > s0) SMN_TRY(upd(js, s0, js - s0, 1));
-      // panel solve against the prefactored diagonal block; row blocks start at n_factor
-      if (dtype == SMN_F64) {
-        constexpr int XR = PanelCfg<double>::XR;
+  return by_dtype(dtype, [&](auto e) -> int {
+    using T = decltype(e);
+    auto upd = [&](int64_t c0, int64_t k0, int64_t K, int64_t tiles_n) -> int {
+      const int tag = K >= 256 ? 1 : 0;   // the pipelined K loop from K = 256 on (profile category: trailing update)
+      return launch_update<T>(ctx, plain, st, static_cast<T*>(a), lda, n_factor, c0, k0, K, tm, tiles_n, 0, tag);
+    };
+    SMN_TRY(set_lds_attrs<T>(ctx));
+    for (int64_t s0 = 0; s0 < n_factor; s0 += S) {
+      const int64_t s_end = (n_factor - s0 < S) ? n_factor : s0 + S;
+      for (int64_t js = s0; js < s_end; js += PB) {
+        // appended rows only: C = a[n_factor:, js:js+128] -= a[n_factor:, s0:js] * a[js:js+128, s0:js]^T
+        if (js > s0) SMN_TRY(upd(js, s0, js - s0, 1));
+        // panel solve against the prefactored diagonal block; row blocks start at n_factor
+        constexpr int XR = PanelCfg<T>::XR;
         const unsigned grid = (unsigned)((n_total - n_factor + XR - 1) / XR);
-        hipLaunchKernelGGL(panel_kernel<double>, dim3(grid), dim3(panel_threads(XR)),
-                           panel_lds_bytes<double>(), st, static_cast<double*>(a), lda, js, n_factor,
-                           n_total, 1, ctx->d_scal, ctx->d_info, static_cast<double*>(nullptr), (int64_t)-1, (int64_t)-1, (int64_t)0, (int64_t)0);
-      } else {
-        constexpr int XR = PanelCfg<float>::XR;
-        const unsigned grid = (unsigned)((n_total - n_factor + XR - 1) / XR);
-        hipLaunchKernelGGL(panel_kernel<float>, dim3(grid), dim3(panel_threads(XR)),
-                           panel_lds_bytes<float>(), st, static_cast<float*>(a), lda, js, n_factor,
-                           n_total, 1, ctx->d_scal, ctx->d_info, static_cast<float*>(nullptr), (int64_t)-1, (int64_t)-1, (int64_t)0, (int64_t)0);
+        hipLaunchKernelGGL(panel_kernel<T>, dim3(grid), dim3(panel_threads(XR)), panel_lds_bytes<T>(), st, static_cast<T*>(a),
+                           lda, js, n_factor, n_total, 1, ctx->d_scal, ctx->d_info, static_cast<T*>(nullptr), (int64_t)-1,
+                           (int64_t)-1, (int64_t)0, (int64_t)0);
+        SMN_CHECK_LAUNCH(ctx);
       }
-      SMN_CHECK_LAUNCH(ctx);
+      if (s_end < n_factor) SMN_TRY(upd(s_end, s0, s_end - s0, (n_factor - s_end) / kTile));
     }
-    if (s_end < n_factor) SMN_TRY(upd(s_end, s0, s_end - s0, (n_factor - s_end) / kTile));
-  }
-  return SMN_OK;
+    return SMN_OK;
+  });
 }
 
 // The trailing block of solved appended rows (internal.hpp): what the factorisation's far update does to them, column
@@ -1640,16 +1621,15 @@ int schur_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t
   int64_t S = ctx->super_panel / PB * PB;
   if (S < PB) S = PB;
   const FactorCall plain{};
-  if (dtype == SMN_F64) SMN_TRY(set_lds_attrs<double>(ctx));
-  else SMN_TRY(set_lds_attrs<float>(ctx));
-  for (int64_t k0 = 0; k0 < n_factor; k0 += S) {
-    const int64_t K = n_factor - k0 < S ? n_factor - k0 : S;
-    if (dtype == SMN_F64)
-      SMN_TRY(launch_update<double>(ctx, plain, ctx->stream, static_cast<double*>(a), lda, n_factor, n_factor, k0, K, tm, tm, 1));
-    else
-      SMN_TRY(launch_update<float>(ctx, plain, ctx->stream, static_cast<float*>(a), lda, n_factor, n_factor, k0, K, tm, tm, 1));
-  }
-  return SMN_OK;
+  return by_dtype(dtype, [&](auto e) -> int {
+    using T = decltype(e);
+    SMN_TRY(set_lds_attrs<T>(ctx));
+    for (int64_t k0 = 0; k0 < n_factor; k0 += S) {
+      const int64_t K = n_factor - k0 < S ? n_factor - k0 : S;
+      SMN_TRY(launch_update<T>(ctx, plain, ctx->stream, static_cast<T*>(a), lda, n_factor, n_factor, k0, K, tm, tm, 1));
+    }
+    return SMN_OK;
+  });
 }
 
 namespace {
@@ -1663,33 +1643,17 @@ __global__ void publish_kernel(const double* __restrict__ scal, const int* __res
 }
 }  // namespace
 
-int fetch_results(smn_ctx* ctx, const double* quad_dev, int nq, double* quad_h, double* logdet, int* info) {
-  if (nq < 0 || nq > 62) return smn_fail(ctx, SMN_EINVAL, "fetch_results: %d values", nq);
+int fetch_mail(smn_ctx* ctx, int nq, HeadScalars* h) {
+  if (nq < 0 || nq > 48) return smn_fail(ctx, SMN_EINVAL, "fetch_mail: %d values", nq);
+  SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  head_decode(ctx->h_mail, nq, h);
+  return SMN_OK;
+}
+
+int fetch_results(smn_ctx* ctx, const double* quad_dev, int nq, HeadScalars* h) {
+  if (nq < 0 || nq > 48) return smn_fail(ctx, SMN_EINVAL, "fetch_results: %d values", nq);
   hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_scal, ctx->d_info, quad_dev, nq,
                      ctx->d_mail);
   SMN_CHECK_LAUNCH(ctx);
-  SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const volatile double* m = ctx->h_mail;
-  int inf = (int)m[1];
-  if (inf == INT_MAX) inf = 0;
-  if (logdet) *logdet = m[0];
-  if (info) *info = inf;
-  for (int i = 0; i < nq && quad_h; ++i) quad_h[i] = m[2 + i];
-  return SMN_OK;
-}
-
-int fetch_mail(smn_ctx* ctx, int nq, double* quad_h, double* logdet, int* info) {
-  if (nq < 0 || nq > 62) return smn_fail(ctx, SMN_EINVAL, "fetch_mail: %d values", nq);
-  SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const volatile double* m = ctx->h_mail;
-  int inf = (int)m[1];
-  if (inf == INT_MAX) inf = 0;
-  if (logdet) *logdet = m[0];
-  if (info) *info = inf;
-  for (int i = 0; i < nq && quad_h; ++i) quad_h[i] = m[2 + i];
-  return SMN_OK;
-}
-
-int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info) {
-  return fetch_results(ctx, nullptr, 0, nullptr, logdet, info);
+  return fetch_mail(ctx, nq, h);
 }

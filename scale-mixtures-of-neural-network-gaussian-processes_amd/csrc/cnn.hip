@@ -478,8 +478,9 @@ int cnn_diag_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw,
 int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,
              int64_t H, int64_t W, int64_t C, void* diag_d) {
   SMN_TRY(conv_check(ctx, "smn_kernel_conv_diag", dtype, act, layers, n, H, W, C, 64 * kMaxPix));
-  if (dtype == SMN_F64) return cnn_diag_t<double>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
-  return cnn_diag_t<float>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
+  return by_dtype(dtype, [&](auto e) {
+    return cnn_diag_t<decltype(e)>(ctx, act, layers, w, b, lw, x_d, n, H, W, C, diag_d);
+  });
 }
 
 extern "C" int smn_kernel_cnn(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
@@ -491,7 +492,7 @@ extern "C" int smn_kernel_cnn(smn_ctx* ctx, int dtype, int act, int num_hiddens,
   if (x2_d && n2 <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_kernel_cnn: bad sizes");
   if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_cnn", ldk, n2);
   else SMN_CHECK_LD(ctx, "smn_kernel_cnn", ldk, n1);
-  if (dtype == SMN_F64)
-    return cnn_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
-  return cnn_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
+  return by_dtype(dtype, [&](auto e) {
+    return cnn_t<decltype(e)>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
+  });
 }

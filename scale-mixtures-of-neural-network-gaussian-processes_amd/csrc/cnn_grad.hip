@@ -336,11 +336,10 @@ int cnn_grad_terms(smn_ctx* ctx, const char* who, bool multi, int dtype, int act
   SMN_CHECK_LD(ctx, who, ldkinv, n);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
   const int nc = multi ? (int)c : 0;
-  if (dtype == SMN_F64)
-    return cgrad_terms_t<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
+  return by_dtype(dtype, [&](auto e) {
+    return cgrad_terms_t<decltype(e)>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
                                  coef, terms_h, nc);
-  return cgrad_terms_t<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, neg_kinv_d, ldkinv, alpha_d,
-                              coef, terms_h, nc);
+  });
 }
 
 // smn_spr_cnn_loss_grad / smn_spr_cnn_loss_grad_multi.  Fused: the forward conv build of the lower triangle straight into the
@@ -356,10 +355,10 @@ int spr_cnn_loss_grad(smn_ctx* ctx, const char* who, bool multi, int dtype, int 
   if (c < 1) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes", who);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
+  const BuildSpec spec{dtype, SMN_NET_MLP, act, num_hiddens, w_std, b_std, last_w_std};   // (net: not read by the conv build)
   Posterior p;
-  SMN_TRY(posterior_from_images(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, y_d, c, eps_abs, &p));
-  const double tot = publish_head(p.quad, c, multi, p.logdet, p.info, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h,
-                                  terms_h);
+  SMN_TRY(posterior_from_images(ctx, spec, x_d, n, H, W, C, y_d, c, eps_abs, &p));
+  const double tot = publish_head(p, c, multi, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h, terms_h);
   if (p.info != 0) return SMN_OK;
   return cnn_grad_terms(ctx, multi ? "smn_kernel_cnn_grad_terms_multi" : "smn_kernel_cnn_grad_terms", multi, dtype, act,
                         num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, p.ninv, p.ldinv, p.alpha, c,

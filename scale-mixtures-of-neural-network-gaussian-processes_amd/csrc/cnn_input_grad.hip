@@ -298,7 +298,7 @@ extern "C" int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int n
   SMN_CHECK_LD(ctx, who, ldg, n);
   if (n_grad < 1 || n_grad > n)
     return smn_fail(ctx, SMN_EINVAL, "%s: n_grad = %lld outside [1, n = %lld]", who, (long long)n_grad, (long long)n);
-  if (dtype == SMN_F64)
-    return cig_run<double>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, gbar_d, ldg, n_grad, gx_d);
-  return cig_run<float>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, gbar_d, ldg, n_grad, gx_d);
+  return by_dtype(dtype, [&](auto e) {
+    return cig_run<decltype(e)>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, gbar_d, ldg, n_grad, gx_d);
+  });
 }

@@ -357,8 +357,9 @@ int resnet_diag_t(smn_ctx* ctx, int act, int block_size, double w, double b, dou
 
 int conv_resnet_diag(smn_ctx* ctx, int dtype, int act, int block_size, double w, double b, double lw, const void* x_d,
                      int64_t n, int64_t H, int64_t W, int64_t C, void* diag_d) {
-  if (dtype == SMN_F64) return resnet_diag_t<double>(ctx, act, block_size, w, b, lw, x_d, n, H, W, C, diag_d);
-  return resnet_diag_t<float>(ctx, act, block_size, w, b, lw, x_d, n, H, W, C, diag_d);
+  return by_dtype(dtype, [&](auto e) {
+    return resnet_diag_t<decltype(e)>(ctx, act, block_size, w, b, lw, x_d, n, H, W, C, diag_d);
+  });
 }
 
 extern "C" int smn_kernel_conv_resnet(smn_ctx* ctx, int dtype, int act, int block_size, double w_std, double b_std,
@@ -372,7 +373,7 @@ extern "C" int smn_kernel_conv_resnet(smn_ctx* ctx, int dtype, int act, int bloc
     return smn_fail(ctx, SMN_EINVAL, "smn_kernel_conv_resnet: bad sizes");
   if (x2_d) SMN_CHECK_LD(ctx, "smn_kernel_conv_resnet", ldk, n2);
   else SMN_CHECK_LD(ctx, "smn_kernel_conv_resnet", ldk, n1);
-  if (dtype == SMN_F64)
-    return resnet_t<double>(ctx, act, block_size, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
-  return resnet_t<float>(ctx, act, block_size, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
+  return by_dtype(dtype, [&](auto e) {
+    return resnet_t<decltype(e)>(ctx, act, block_size, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, fill, nngp_d, ldk);
+  });
 }

@@ -200,3 +200,12 @@ int smn_workspace(smn_ctx* ctx, int slot, size_t bytes, void** out);
 int smn_allow_lds(smn_ctx* ctx, const void* kernel, size_t lds);
 
 inline size_t dtype_size(int dtype) { return dtype == SMN_F64 ? 8 : 4; }
+
+// THE dispatch on the element type: f is a generic lambda called with a value of the type, which launches kernel<T> with
+// static_cast<T*> operands -- grid, stream and arguments are stated once.
+//   by_dtype(dtype, [&](auto e) { using T = decltype(e); hipLaunchKernelGGL(k<T>, g, b, 0, st, static_cast<T*>(a), ...); });
+// A site that picks different kernels, constants or conditions per type keeps its own two branches.
+template <class F>
+auto by_dtype(int dtype, F&& f) {
+  return dtype == SMN_F64 ? f(double{}) : f(float{});
+}

@@ -236,7 +236,7 @@ extern "C" int smn_mvn_draws(smn_ctx* ctx, int dtype, const void* mean_d, const 
   if (point0 < 0 || T > ((int64_t)1 << 32) || point0 + T > ((int64_t)1 << 32) || S > ((int64_t)1 << 32))
     return smn_fail(ctx, SMN_EINVAL, "smn_mvn_draws: bad sizes (point indices and draws are 32-bit counter words)");
   SMN_CHECK_LD(ctx, "smn_mvn_draws", ldl, T);
-  if (dtype == SMN_F64)
-    return mvn_draws_t<double>(ctx, mean_d, l_d, ldl, T, (int)C, S, df, shape, seed, point0, noise_d, mix_d, out_d);
-  return mvn_draws_t<float>(ctx, mean_d, l_d, ldl, T, (int)C, S, df, shape, seed, point0, noise_d, mix_d, out_d);
+  return by_dtype(dtype, [&](auto e) {
+    return mvn_draws_t<decltype(e)>(ctx, mean_d, l_d, ldl, T, (int)C, S, df, shape, seed, point0, noise_d, mix_d, out_d);
+  });
 }

@@ -134,10 +134,10 @@ __global__ void fill_kernel(T* __restrict__ dst, int64_t ld, int64_t rows, int64
 int fill_matrix(smn_ctx* ctx, int dtype, void* dst, int64_t ld, int64_t rows, int64_t cols, double value) {
   if (rows <= 0 || cols <= 0) return SMN_OK;
   dim3 g((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(fill_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(dst), ld, rows, cols, value);
-  else
-    hipLaunchKernelGGL(fill_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(dst), ld, rows, cols, (float)value);
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(fill_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(dst), ld, rows, cols, (T)value);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -171,9 +171,9 @@ int eigh_core(smn_ctx* ctx, int dtype, const void* a_d, int64_t n, int64_t lda, 
   SMN_TRY(copy_matrix(ctx, dtype, lw, np, a_d, lda, n, n, 1));
   SMN_TRY(fill_identity_pad(ctx, dtype, lw, np, np, n));
   SMN_TRY(cholesky_padded(ctx, FactorCall{dtype, lw, np, np, np, n, jitter_abs, ridge_rel, true}));
-  double logdet = 0.0;
-  int info = 0;
-  SMN_TRY(fetch_logdet_info(ctx, &logdet, &info));
+  HeadScalars head;
+  SMN_TRY(fetch_results(ctx, nullptr, 0, &head));
+  const int info = head.info;
   if (sweeps_h) *sweeps_h = 0;
   if (info != 0) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -186,10 +186,10 @@ int eigh_core(smn_ctx* ctx, int dtype, const void* a_d, int64_t n, int64_t lda, 
 
   {
     dim3 g((unsigned)((n + 31) / 32), (unsigned)((n + 31) / 32)), b(32, 8);
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL(factor_rows_kernel<double>, g, b, 0, ctx->stream, m_d, n, static_cast<const double*>(lw), np);
-    else
-      hipLaunchKernelGGL(factor_rows_kernel<float>, g, b, 0, ctx->stream, m_d, n, static_cast<const float*>(lw), np);
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
+      hipLaunchKernelGGL(factor_rows_kernel<T>, g, b, 0, ctx->stream, m_d, n, static_cast<const T*>(lw), np);
+    });
     SMN_CHECK_LAUNCH(ctx);
   }
   const double u = dtype == SMN_F64 ? DBL_EPSILON : (double)FLT_EPSILON;
@@ -221,12 +221,11 @@ int eigh_core(smn_ctx* ctx, int dtype, const void* a_d, int64_t n, int64_t lda, 
   std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return nrm[(size_t)x] < nrm[(size_t)y]; });
   SMN_HIP(ctx, hipMemcpyAsync(perm_d, perm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   void* w_out = w_d ? w_d : static_cast<void*>(nrm_d);   // (never the case for the public entry)
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(eig_store_kernel<double>, dim3((unsigned)n), dim3(256), 0, ctx->stream, m_d, n, nrm_d, perm_d,
-                       static_cast<double*>(w_out), static_cast<double*>(vt_d));
-  else
-    hipLaunchKernelGGL(eig_store_kernel<float>, dim3((unsigned)n), dim3(256), 0, ctx->stream, m_d, n, nrm_d, perm_d,
-                       static_cast<float*>(w_out), static_cast<float*>(vt_d));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(eig_store_kernel<T>, dim3((unsigned)n), dim3(256), 0, ctx->stream, m_d, n, nrm_d, perm_d,
+                       static_cast<T*>(w_out), static_cast<T*>(vt_d));
+  });
   SMN_CHECK_LAUNCH(ctx);
   if (v_d) SMN_TRY(transpose_matrix(ctx, dtype, v_d, ldv, vt_d, n, n, n));
   SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));   // perm is host memory of this frame
@@ -282,12 +281,11 @@ struct Gd {
   int nt(const void* a, int64_t ra, int64_t lda, const void* b, int64_t rb, int64_t ldb, int64_t k, void* out, int64_t ldo,
          int mode = SCALE_NONE, const void* lam = nullptr, double s = 0.0) const {
     dim3 g((unsigned)((k + 255) / 256), (unsigned)(ra < 32768 ? ra : 32768));
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL(scale_cols_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(scratch), k,
-                         static_cast<const double*>(a), lda, ra, k, static_cast<const double*>(lam), mode, s, (double)k);
-    else
-      hipLaunchKernelGGL(scale_cols_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(scratch), k,
-                         static_cast<const float*>(a), lda, ra, k, static_cast<const float*>(lam), mode, s, (double)k);
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
+      hipLaunchKernelGGL(scale_cols_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(scratch), k,
+                         static_cast<const T*>(a), lda, ra, k, static_cast<const T*>(lam), mode, s, (double)k);
+    });
     SMN_CHECK_LAUNCH(ctx);
     return smn_gram(ctx, dtype, scratch, ra, k, b, rb, ldb, k, out, ldo, nullptr, nullptr);
   }
@@ -358,10 +356,10 @@ extern "C" int smn_predict_gd(smn_ctx* ctx, int dtype, const void* k_joint_d, co
   SMN_TRY(gd.nt(yt, c, n, vt, n, n, n, zt, n));
   if (ntk && cov_d) {
     dim3 g((unsigned)((n + 255) / 256), (unsigned)(n < 32768 ? n : 32768));
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL(sym_copy_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(kdd), n, static_cast<const double*>(k_joint_d), ld, n);
-    else
-      hipLaunchKernelGGL(sym_copy_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(kdd), n, static_cast<const float*>(k_joint_d), ld, n);
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
+      hipLaunchKernelGGL(sym_copy_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(kdd), n, static_cast<const T*>(k_joint_d), ld, n);
+    });
     SMN_CHECK_LAUNCH(ctx);
     SMN_TRY(gd.nt(vt, n, n, kdd, n, n, n, u, n));
     SMN_TRY(gd.nt(u, n, n, vt, n, n, n, khat, n));
@@ -383,12 +381,11 @@ extern "C" int smn_predict_gd(smn_ctx* ctx, int dtype, const void* k_joint_d, co
       sg1 = 1.0;
     }
     dim3 g((unsigned)((t + 255) / 256), (unsigned)(t < 32768 ? t : 32768));
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL(gd_cov_kernel<double>, g, dim3(256), 0, ctx->stream, reinterpret_cast<double*>(cov_j), ldc,
-                         static_cast<const double*>(at(kj, n, n)), ld, static_cast<const double*>(s1), static_cast<const double*>(s2), t, sg1);
-    else
-      hipLaunchKernelGGL(gd_cov_kernel<float>, g, dim3(256), 0, ctx->stream, reinterpret_cast<float*>(cov_j), ldc,
-                         static_cast<const float*>(at(kj, n, n)), ld, static_cast<const float*>(s1), static_cast<const float*>(s2), t, sg1);
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
+      hipLaunchKernelGGL(gd_cov_kernel<T>, g, dim3(256), 0, ctx->stream, reinterpret_cast<T*>(cov_j), ldc,
+                         static_cast<const T*>(at(kj, n, n)), ld, static_cast<const T*>(s1), static_cast<const T*>(s2), t, sg1);
+    });
     SMN_CHECK_LAUNCH(ctx);
   }
   return SMN_OK;

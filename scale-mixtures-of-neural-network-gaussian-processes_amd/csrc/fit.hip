@@ -151,18 +151,17 @@ int readout_t(smn_fit* f, int64_t rows, const void* ktt, int64_t ktt_stride, voi
 }
 
 int readout(smn_fit* f, int64_t rows, const void* ktt, int64_t ktt_stride, void* mean, void* var) {
-  return f->dtype == SMN_F64 ? readout_t<double>(f, rows, ktt, ktt_stride, mean, var)
-                             : readout_t<float>(f, rows, ktt, ktt_stride, mean, var);
+  return by_dtype(f->dtype, [&](auto e) { return readout_t<decltype(e)>(f, rows, ktt, ktt_stride, mean, var); });
 }
 
 int fill_nan(smn_fit* f, void* p, int64_t rows, int64_t cols, int64_t ld) {
   if (!p || rows <= 0 || cols <= 0) return SMN_OK;
   smn_ctx* ctx = f->ctx;
   const dim3 g((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
-  if (f->dtype == SMN_F64)
-    hipLaunchKernelGGL(fit_nan_kernel<double>, g, dim3(256), 0, ctx->stream, static_cast<double*>(p), rows, cols, ld);
-  else
-    hipLaunchKernelGGL(fit_nan_kernel<float>, g, dim3(256), 0, ctx->stream, static_cast<float*>(p), rows, cols, ld);
+  by_dtype(f->dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(fit_nan_kernel<T>, g, dim3(256), 0, ctx->stream, static_cast<T*>(p), rows, cols, ld);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -221,14 +220,10 @@ int fit_factor(smn_fit* f, const void* y_d, bool prepped, double ridge_rel, doub
   fc.prepped = prepped;
   SMN_TRY(cholesky_padded(ctx, fc));
   SMN_TRY(extract_posterior(ctx, f->dtype, f->a, f->lda, f->n_pad, 0, f->c, nullptr, nullptr, 0, ctx->d_scal + 8, true));
-  double quad[48], ld = 0.0;
-  int info = 0;
-  SMN_TRY(fetch_mail(ctx, (int)f->c, quad, &ld, &info));
-  f->info = info;
-  if (info != 0) ld = std::nan("");
-  for (int64_t k = 0; k < f->c && quad_h; ++k) quad_h[k] = info != 0 ? std::nan("") : quad[k];
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
+  HeadScalars h;
+  SMN_TRY(fetch_mail(ctx, (int)f->c, &h));
+  f->info = h.info;
+  publish_head(h, f->c, true, f->n, 0.0, 1.0, nullptr, nullptr, quad_h, logdet_h, info_h);   // (the per-column forms only)
   // (columns [0, n_pad) only: what lies behind them is the creation-time Schur block -beta beta^T, which stays out of the beta rows)
   const size_t pitch = f->es() * (size_t)f->lda;
   SMN_HIP(ctx, hipMemcpy2DAsync(f->at(f->beta_row(), 0), pitch, f->at(f->n_pad, 0), pitch, f->es() * (size_t)f->n_pad, (size_t)kTile,

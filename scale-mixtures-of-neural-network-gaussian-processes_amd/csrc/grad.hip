@@ -701,7 +701,7 @@ int grad_batch_launch(smn_ctx* ctx, const GradBatchArgs<T>& b, int nb, const dou
   return SMN_OK;
 }
 
-// The joint route of smn_spr_loss_grad for nprob problems at once (heads.hip factor_built_with_identity, batched the way
+// The joint route of smn_spr_loss_grad for nprob problems at once (heads.hip posterior_from_x, batched the way
 // spr_batch batches the loss): K0 and its diagonal once; per chunk the G joint matrices [[K~, .], [I, 0], [y^T, 0, 0]] side by
 // side in workspace slot 2, ONE factorisation with grid.y = G, and the contraction reading -K~^-1 and alpha where it left them.
 template <typename T>
@@ -741,6 +741,7 @@ int grad_batch_t(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int
   // drains the stream before they go, below), so neither upload needs a synchronisation of its own
   std::vector<GradProb> prob_h((size_t)chunk);
   std::vector<char> progs_h;
+  const BuildSpec spec{dtype, net, act, num_hiddens, w_std[0], b_std[0], last_w_std[0]};
   std::vector<double> res_h((size_t)chunk * kBatchRes);
   struct Drain {   // an error return: nothing in flight may still read the vectors above
     smn_ctx* c; bool armed = true;
@@ -748,8 +749,7 @@ int grad_batch_t(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int
   } drain{ctx};
   for (int p0 = 0; p0 < nprob; p0 += chunk) {
     const int nb = std::min(chunk, nprob - p0);
-    SMN_TRY(recursion_lower_batch(ctx, dtype, net, act, num_hiddens, nb, w_std + p0, b_std + p0, last_w_std + p0, k0, n, ld0, q, av,
-                                  lda, bstride, progs_h));
+    SMN_TRY(recursion_lower_batch(ctx, spec, nb, w_std + p0, b_std + p0, last_w_std + p0, k0, n, ld0, q, av, lda, bstride, progs_h));
     for (int b = 0; b < nb; ++b) {
       const int g = p0 + b;
       prob_h[(size_t)b] = GradProb{w_std[g] * w_std[g], b_std[g] * b_std[g], last_w_std[g] * last_w_std[g], df ? df[g] : 0.0,
@@ -825,11 +825,10 @@ int lml_grad_terms(smn_ctx* ctx, const char* who, bool multi, int dtype, int net
   if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "Unsupported act %d", act);
   if (num_hiddens < 0 || !(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: bad hyper-parameters", who);
   const int nc = multi ? (int)c : 0;
-  if (dtype == SMN_F64)
-    return grad_terms_t<double>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
+  return by_dtype(dtype, [&](auto e) {
+    return grad_terms_t<decltype(e)>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d,
                                 ldkinv, alpha_d, coef, terms_h, nc, ntk);
-  return grad_terms_t<float>(ctx, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, neg_kinv_d, ldkinv,
-                             alpha_d, coef, terms_h, nc, ntk);
+  });
 }
 
 // smn_spr_loss_grad / smn_spr_loss_grad_multi.  Fused: K0 = X X^T / d and its diagonal, K by the stand-alone recursion straight
@@ -847,10 +846,10 @@ int spr_loss_grad(smn_ctx* ctx, const char* who, bool multi, int dtype, int net,
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
   SMN_CHECK_LD(ctx, who, ldx, d);
+  const BuildSpec spec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   Posterior p;
-  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p));
-  const double tot = publish_head(p.quad, c, multi, p.logdet, p.info, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h,
-                                  terms_h);
+  SMN_TRY(posterior_from_x(ctx, spec, x_d, n, ldx, d, y_d, c, eps_abs, &p));
+  const double tot = publish_head(p, c, multi, n, df, scale, nullptr, quad_h, quad_cols_h, logdet_h, info_h, terms_h);
   if (p.info != 0) return SMN_OK;
   return lml_grad_terms(ctx, multi ? "smn_lml_grad_terms_multi" : "smn_lml_grad_terms", multi, dtype, net, act, num_hiddens, w_std,
                         b_std, last_w_std, p.k0, n, p.ld0, p.q, p.ninv, p.ldinv, p.alpha, c, lml_coef(df, scale, tot, n, c),
@@ -921,9 +920,8 @@ extern "C" int smn_spr_loss_grad_batch(smn_ctx* ctx, int dtype, int net, int act
                                 logdet_h ? logdet_h + b : nullptr, info_h ? info_h + b : nullptr, terms_h + (size_t)b * 4));
     return SMN_OK;
   }
-  if (dtype == SMN_F64)
-    return grad_batch_t<double>(ctx, dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, eps_abs, df,
+  return by_dtype(dtype, [&](auto e) {
+    return grad_batch_t<decltype(e)>(ctx, dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, eps_abs, df,
                                 scale, quad_h, logdet_h, info_h, terms_h);
-  return grad_batch_t<float>(ctx, dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, eps_abs, df, scale,
-                             quad_h, logdet_h, info_h, terms_h);
+  });
 }

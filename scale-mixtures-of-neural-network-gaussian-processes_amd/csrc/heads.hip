@@ -13,6 +13,15 @@
 //   NNGPKernel.predict            spax/kernels.py:29-32  (neural_tangents gradient_descent_mse_ensemble)
 //   the quadratic form of StudentTLikelihood.logpdf      spax/likelihoods.py:60-61
 // The closed-form log-pdf arithmetic on the resulting scalars is done on the host (lgamma etc.).
+//
+// ONE stage owns that matrix and the protocol around it; an entry that returns a value or a prediction is a few lines on it:
+//   aug_shape / aug_alloc   the layout for (dtype, n, t, c) and its workspace (slot 2); spr_batch takes chunk x the shape
+//   aug_place               a kernel that exists already: clear rows [n, n_total), the entry's fill callback, identity padding
+//   aug_build (AugBuild)    or the fused build straight from the inputs: batch, trace, Gram plan, Theta as named fields
+//   aug_finish (AugFinish)  Y^T and the shifts (one prep launch), factor, read out; outputs, identity-row hint, arrivals named
+//   HeadScalars             quad[c], logdet, info under the NaN convention (internal.hpp head_decode, the one place it lives)
+//   publish_head            the joint head into whichever outputs the caller wants
+// A new value-side entry picks a fill callback or build options and a head; it restates none of the steps.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -22,20 +31,41 @@
 
 namespace {
 
+// ---- the stage every value-side entry runs on: shape -> place (or build) -> finish -> publish_head ----
 struct Aug {
+  int dtype;
   int64_t n, n_pad, t, c, n_total, lda;
   void* a;
   size_t es;
   char* at(int64_t r, int64_t col) const { return static_cast<char*>(a) + es * (size_t)(r * lda + col); }
+  size_t bytes() const { return es * (size_t)n_total * (size_t)n_total; }
 };
 
+// THE layout decision: n training rows, t test rows, c rows of Y^T (a = nullptr: no storage yet)
+Aug aug_shape(int dtype, int64_t n, int64_t t, int64_t c) {
+  Aug g{};
+  g.dtype = dtype; g.n = n; g.t = t; g.c = c;
+  g.n_pad = round_up(n, kTile);
+  g.n_total = g.n_pad + round_up(t + c, kTile);
+  g.lda = g.n_total;
+  g.es = dtype_size(dtype);
+  return g;
+}
+
 int aug_alloc(smn_ctx* ctx, int dtype, int64_t n, int64_t t, int64_t c, Aug* g) {
-  g->n = n; g->t = t; g->c = c;
-  g->n_pad = round_up(n, kTile);
-  g->n_total = g->n_pad + round_up(t + c, kTile);
-  g->lda = g->n_total;
-  g->es = dtype_size(dtype);
-  return smn_workspace(ctx, 2, g->es * (size_t)g->n_total * (size_t)g->n_total, &g->a);
+  *g = aug_shape(dtype, n, t, c);
+  return smn_workspace(ctx, 2, g->bytes(), &g->a);
+}
+
+// Placement of a kernel that exists already: the matrix up, rows [n, n_total) cleared, K (and whatever else the entry keeps
+// below it) written by `fill` -- none: the pieces of a column-first exchange land later --, identity padding.
+// Only rows >= n (identity padding + appended rows) need clearing: above them just the lower triangle is ever read (tests:
+// test_cholesky_reads_the_lower_triangle_only), and that is what fill writes.
+int aug_place(smn_ctx* ctx, int dtype, int64_t n, int64_t t, int64_t c, const KernelInto& fill, Aug* g) {
+  SMN_TRY(aug_alloc(ctx, dtype, n, t, c, g));
+  SMN_HIP(ctx, hipMemsetAsync(g->at(n, 0), 0, g->es * (size_t)(g->n_total - n) * (size_t)g->lda, ctx->stream));
+  if (fill) SMN_TRY(fill(g->a, g->lda));
+  return fill_identity_pad(ctx, dtype, g->a, g->lda, g->n_pad, n);
 }
 
 }  // namespace
@@ -60,11 +90,18 @@ namespace {
 // out: the caller goes on to aug_finish with it.  Under the look-ahead the bottom-right corner of the matrix is then built
 // on the bulk stream beside the first super-panel's panel chain (run_build); want_trace leaves the trace of the kernel's
 // diagonal for a relative ridge.
-int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, int64_t ldx, const void* xt,
-              int64_t ldxt, int64_t d, int nbatch = 0, const double* bw = nullptr, const double* bb = nullptr,
-              const double* blw = nullptr, BuildOut* out = nullptr, bool want_trace = false, const GramPlan* gram = nullptr,
-              bool ntk = false) {   // ntk (SMN_NET_NTK): Theta lands where K would, alone
+struct AugBuild {   // what a call of aug_build may set beyond its operands; the defaults: one problem, K, slot 0, no report
+  int nbatch = 0; const double* bw = nullptr; const double* bb = nullptr; const double* blw = nullptr;   // BuildCall::nbatch
+  BuildOut* out = nullptr;        // where the build reports what it left (a split build needs it)
+  bool want_trace = false;
+  const GramPlan* gram = nullptr;
+  bool ntk = false;               // SMN_NET_NTK: Theta lands where K would, alone
+};
+
+int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, int64_t ldx, const void* xt, int64_t ldxt,
+              int64_t d, const AugBuild& o) {
   const int64_t kp = k_pad(spec.dtype, d);
+  const GramPlan* gram = o.gram;
   const int gmode = gram ? gram->mode : GRAM_CALL_NONE;
   void* xs = nullptr;
   // Gram cache (smn_spr_loss): the operand is the cache's own copy, not workspace slot 0 (which every other entry point rewrites)
@@ -83,21 +120,28 @@ int aug_build(smn_ctx* ctx, const BuildSpec& spec, const Aug& g, const void* x, 
   c.symmetric = 1; c.mirror = 0; c.exact_diag = 1;
   c.store_mode = STORE_PAD_IDENTITY;
   c.nv0 = g.n; c.aug0 = g.n_pad; c.nv1 = g.t;
-  c.get_mask = ntk ? SMN_GET_NTK : SMN_GET_NNGP;
-  c.out_k = ntk ? nullptr : g.a; c.out_t = ntk ? g.a : nullptr; c.ldo = g.lda;
-  c.nbatch = nbatch; c.bw = bw; c.bb = bb; c.blw = blw; c.out_bs = g.n_total * g.lda;   // batched: problem b at a + b * n_total^2
+  c.get_mask = o.ntk ? SMN_GET_NTK : SMN_GET_NNGP;
+  c.out_k = o.ntk ? nullptr : g.a; c.out_t = o.ntk ? g.a : nullptr; c.ldo = g.lda;
+  c.nbatch = o.nbatch; c.bw = o.bw; c.bb = o.bb; c.blw = o.blw; c.out_bs = g.n_total * g.lda;   // batched: problem b at a + b * n_total^2
   // (not while pieces of a column-first exchange are still landing in this workspace)
-  c.split_corner = (out && nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
-  c.want_trace = (want_trace && nbatch == 0) ? 1 : 0;   // (relative ridge: the prep launch then carries the shift, aug_finish)
+  c.split_corner = (o.out && o.nbatch == 0 && ctx->split_build && ctx->arrivals.empty()) ? split_corner_tiles(ctx, g.n_total / kTile) : 0;
+  c.want_trace = (o.want_trace && o.nbatch == 0) ? 1 : 0;   // (relative ridge: the prep launch then carries the shift, aug_finish)
   c.gram_mode = gmode; c.gram_gen = gram ? gram->gen : 0u;
-  return run_build(ctx, c, out);
+  return run_build(ctx, c, o.out);
 }
 
-// built: what the build in front left behind (none: {}).  shards: the pieces of a column-first exchange still landing in
-// the workspace (smn_lml_from_shards).
-int aug_finish(smn_ctx* ctx, int dtype, const Aug& g, const BuildOut& built, const void* y, int64_t ldy, int64_t n_shift,
-               double jitter_abs, double ridge_rel, void* mean, void* cov, int64_t ldcov, double* quad_h, double* logdet_h,
-               int* info_h, bool td_identity = false, const std::vector<smn_ctx::Arrival>* shards = nullptr) {
+struct AugFinish {   // what a call of aug_finish sets: Y and the shifts always, the rest where the entry has it
+  const void* y = nullptr;                                    // [n, c] row-major (ld = c)
+  double jitter_abs = 0.0, ridge_rel = 0.0;                   // the shift of the first n diagonal entries
+  void* mean = nullptr; void* cov = nullptr; int64_t ldcov = 0;   // predictive outputs (t rows)
+  bool td_identity = false;                                   // the test rows are an identity block (FactorCall::id0)
+  const std::vector<smn_ctx::Arrival>* shards = nullptr;      // pieces of a column-first exchange still landing in the workspace
+};
+
+// built: what the build in front left behind (none: {}).  h: the c quadratic forms, logdet, info under the NaN convention.
+int aug_finish(smn_ctx* ctx, const Aug& g, const BuildOut& built, const AugFinish& o, HeadScalars* h) {
+  const int dtype = g.dtype;
+  const int64_t ldy = g.c, n_shift = g.n;   // Y is packed; the shift covers the n training rows
   // a split build (aug_build): the corner is still being built on the bulk stream; joined on every way out until the
   // factorisation takes it over
   const int64_t corner = built.corner_col;
@@ -105,8 +149,8 @@ int aug_finish(smn_ctx* ctx, int dtype, const Aug& g, const BuildOut& built, con
   if (g.c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");   // the mailbox holds 62 doubles
   // the right-hand-side rows, the diagonal shift and the scalar reset are one launch: with an absolute jitter only, or with the
   // relative ridge when the build in front left the trace of the kernel's diagonal (aug_build want_trace)
-  const bool prepped = g.c > 0 && (ridge_rel == 0.0 || built.trace);
-  const int64_t n_sh = (jitter_abs != 0.0 || ridge_rel != 0.0) ? n_shift : 0;
+  const bool prepped = g.c > 0 && (o.ridge_rel == 0.0 || built.trace);
+  const int64_t n_sh = (o.jitter_abs != 0.0 || o.ridge_rel != 0.0) ? n_shift : 0;
   // the corner's columns are prepped behind the corner's own launch, on the bulk stream, and the factorisation takes them as
   // ONE arrival (cholesky.hip need_columns: whoever first touches those columns waits for it)
   if (corner > 0 && !prepped) SMN_HIP(ctx, hipStreamSynchronize(ctx->stream_bulk));   // (no caller does this: the trace needs every column)
@@ -114,44 +158,33 @@ int aug_finish(smn_ctx* ctx, int dtype, const Aug& g, const BuildOut& built, con
   const smn_ctx::Arrival corner_arrival{corner, g.n_total, ctx->ev_corner};
   if (split) {
     const int64_t sh = n_sh;
-    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, corner, y, g.n, g.c, ldy, std::min(sh, corner), jitter_abs, 0, nullptr, ridge_rel, n_shift));
-    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy, sh, jitter_abs, corner, ctx->stream_bulk, ridge_rel, n_shift));
+    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, corner, o.y, g.n, g.c, ldy, std::min(sh, corner), o.jitter_abs, 0, nullptr, o.ridge_rel, n_shift));
+    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, o.y, g.n, g.c, ldy, sh, o.jitter_abs, corner, ctx->stream_bulk, o.ridge_rel, n_shift));
     SMN_HIP(ctx, hipEventRecord(ctx->ev_corner, ctx->stream_bulk));
   } else if (prepped) {
     if (corner > 0) SMN_HIP(ctx, hipStreamSynchronize(ctx->stream_bulk));
-    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy, n_sh, jitter_abs, 0, nullptr, ridge_rel, n_shift));
+    SMN_TRY(aug_prep(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, o.y, g.n, g.c, ldy, n_sh, o.jitter_abs, 0, nullptr, o.ridge_rel, n_shift));
   } else {
-    SMN_TRY(set_aug_rows(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, y, g.n, g.c, ldy));
+    SMN_TRY(set_aug_rows(ctx, dtype, g.a, g.lda, g.n_pad + g.t, g.n_total, o.y, g.n, g.c, ldy));
   }
-  FactorCall f{dtype, g.a, g.n_total, g.n_pad, g.lda, n_shift, jitter_abs, ridge_rel, false};
+  FactorCall f{dtype, g.a, g.n_total, g.n_pad, g.lda, n_shift, o.jitter_abs, o.ridge_rel, false};
   f.prepped = prepped;
-  if (td_identity) {   // identity test rows (the small-N gradient route): whole 128-row tiles of them are skipped where they are structurally zero
+  if (o.td_identity) {   // identity test rows (the small-N gradient route): whole 128-row tiles of them are skipped where they are structurally zero
     f.id0 = g.n_pad;
     f.id1 = g.n_pad + g.t / kTile * kTile;
   }
   if (split) {
     f.arrivals = &corner_arrival; f.n_arrivals = 1; f.arrivals_on = ctx->stream_bulk;
-  } else if (shards) {
-    f.arrivals = shards->data(); f.n_arrivals = shards->size(); f.arrivals_on = ctx->stream_scatter;
+  } else if (o.shards) {
+    f.arrivals = o.shards->data(); f.n_arrivals = o.shards->size(); f.arrivals_on = ctx->stream_scatter;
   }
   SMN_TRY(cholesky_padded(ctx, f));
   corner_join.release();   // the factorisation has left the caller's stream behind the corner
   // a column-first exchange: the factorisation has waited for the pieces of the workspace; pieces scattered elsewhere (the NTK
   // of config 5, smn_shard_exchange_cols_to) ride the same scatter stream -- the call returns behind all of them
-  if (shards) SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
-  double* quad_dev = ctx->d_scal + 8;
-  SMN_TRY(extract_posterior(ctx, dtype, g.a, g.lda, g.n_pad, g.t, g.c, mean, cov, ldcov, quad_dev, true));
-  double ld = 0.0;
-  int info = 0;
-  SMN_TRY(fetch_mail(ctx, quad_h ? (int)g.c : 0, quad_h, &ld, &info));
-  if (info != 0) {
-    ld = std::nan("");
-    if (quad_h)
-      for (int64_t k = 0; k < g.c; ++k) quad_h[k] = std::nan("");
-  }
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
-  return SMN_OK;
+  if (o.shards) SMN_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
+  SMN_TRY(extract_posterior(ctx, dtype, g.a, g.lda, g.n_pad, g.t, g.c, o.mean, o.cov, o.ldcov, ctx->d_scal + 8, true));
+  return fetch_mail(ctx, (int)g.c, h);
 }
 
 }  // namespace
@@ -186,12 +219,10 @@ extern "C" int smn_cholesky(smn_ctx* ctx, int dtype, void* a_d, int64_t n_total,
     SMN_TRY(copy_matrix(ctx, dtype, ao + es * (size_t)(n_factor * lda), lda, wb + es * (size_t)(nfp * ntp), ntp, m, n_factor, 0));
     SMN_TRY(copy_matrix(ctx, dtype, ao + es * (size_t)(n_factor * lda + n_factor), lda, wb + es * (size_t)(nfp * ntp + nfp), ntp, m, m, 1));
   }
-  double ld = 0.0;
-  int info = 0;
-  SMN_TRY(fetch_logdet_info(ctx, &ld, &info));
-  if (info != 0) ld = std::nan("");
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
+  HeadScalars h;
+  SMN_TRY(fetch_results(ctx, nullptr, 0, &h));
+  if (logdet_h) *logdet_h = h.logdet;
+  if (info_h) *info_h = h.info;
   return SMN_OK;
 }
 
@@ -250,16 +281,12 @@ int lml_entry(smn_ctx* ctx, const char* who, bool multi, int dtype, void* k_d, i
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: scale must be > 0", who);
   Aug g;
-  SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
-  // only rows >= n (identity padding + appended rows) need clearing: above them just the lower triangle is ever
-  // read (tests: test_cholesky_reads_the_lower_triangle_only), and that is copied in below
-  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-  SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, k_d, ldk, n, n, 1));
-  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-  double quad[48], ld = 0.0;
-  int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
-  publish_head(quad, c, multi, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
+  SMN_TRY(aug_place(ctx, dtype, n, 0, c, [&](void* a, int64_t lda) { return copy_matrix(ctx, dtype, a, lda, k_d, ldk, n, n, 1); }, &g));
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = eps_abs;
+  HeadScalars h;
+  SMN_TRY(aug_finish(ctx, g, {}, fin, &h));
+  publish_head(h, c, multi, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
 }
 }  // namespace
@@ -288,17 +315,13 @@ extern "C" int smn_lml_from_blocks(smn_ctx* ctx, int dtype, const void* stage_d,
   if (n <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_lml_from_blocks: empty");
   if (df > 0.0 && !(scale > 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_lml_from_blocks: scale must be > 0");
   Aug g;
-  SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
-  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-  SMN_TRY(smn_unpack_lower_blocks(ctx, dtype, stage_d, n, nranks, block_rows, g.a, g.lda));
-  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-  double quad = 0.0, ld = 0.0;
-  int info = 0;
-  SMN_TRY(aug_finish(ctx, dtype, g, {}, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
-  if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
+  SMN_TRY(aug_place(ctx, dtype, n, 0, 1,
+                    [&](void* a, int64_t lda) { return smn_unpack_lower_blocks(ctx, dtype, stage_d, n, nranks, block_rows, a, lda); }, &g));
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = eps_abs;
+  HeadScalars h;
+  SMN_TRY(aug_finish(ctx, g, {}, fin, &h));
+  publish_head(h, 1, false, n, df, scale, logpdf_h, quad_h, nullptr, logdet_h, info_h);
   return SMN_OK;
 }
 
@@ -399,9 +422,7 @@ extern "C" int smn_shard_begin(smn_ctx* ctx, int dtype, int64_t n, double eps_ab
   }
   ctx->ev_pool_used = 0;
   Aug g;
-  SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
-  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
+  SMN_TRY(aug_place(ctx, dtype, n, 0, 1, nullptr, &g));
   ctx->shard_a = g.a; ctx->shard_lda = g.lda; ctx->shard_n = n; ctx->shard_dtype = dtype; ctx->shard_eps = eps_abs;
   return SMN_OK;
 }
@@ -487,18 +508,16 @@ extern "C" int smn_lml_from_shards(smn_ctx* ctx, int dtype, int64_t n, const voi
     for (int64_t c = 0; c < (n + kTile - 1) / kTile; ++c)
       if (!have[(size_t)c]) return smn_fail(ctx, SMN_EINVAL, "smn_lml_from_shards: tile column %lld was never exchanged", (long long)c);
   }
-  double quad = 0.0, ld = 0.0;
-  int info = 0;
-  // jitter_abs = 0: the scatter added it already.  The factorisation consumes the Arrivals and leaves the main stream behind
+  // no jitter_abs: the scatter added it already.  The factorisation consumes the Arrivals and leaves the main stream behind
   // all of them.
-  const int rc = aug_finish(ctx, dtype, g, {}, y_d, 1, n, 0.0, 0.0, nullptr, nullptr, 0, &quad, &ld, &info, false, &ctx->arrivals);
+  AugFinish fin;
+  fin.y = y_d; fin.shards = &ctx->arrivals;
+  HeadScalars h;
+  const int rc = aug_finish(ctx, g, {}, fin, &h);
   ctx->arrivals.clear();
   ctx->shard_a = nullptr;
   SMN_TRY(rc);
-  if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
+  publish_head(h, 1, false, n, df, scale, logpdf_h, quad_h, nullptr, logdet_h, info_h);
   return SMN_OK;
 }
 
@@ -530,30 +549,39 @@ __global__ void identity_block_kernel(T* __restrict__ a, int64_t lda, int64_t n)
 constexpr int64_t kGradRectFromN = 8192;
 bool grad_uses_rectangle(int64_t n) { return round_up(n, kTile) >= kGradRectFromN; }
 
+namespace {
+
+// the identity block of either route: rows [0, n) of the matrix at `rows` get a one on their diagonal
+int identity_block(smn_ctx* ctx, int dtype, void* rows, int64_t lda, int64_t n) {
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(identity_block_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<T*>(rows), lda, n);
+  });
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
 // `build` writes the lower triangle of K (n rows, exact diagonal, no jitter) into the matrix it is handed: the layer recursion of
-// a Gram matrix for the MLP family (factor_with_identity below), the conv pair build for smn_spr_cnn_loss_grad (cnn_grad.hip).
+// a Gram matrix for the MLP family (posterior_from_x), the conv pair build for smn_spr_cnn_loss_grad (cnn_grad.hip).
 // c target columns (y_d [n, c] row-major): c rows Y^T behind the identity block, n_total = n_pad + round_up(n + c, 128);
-// alpha_d [n, c] row-major and one quadratic form per column in quad_h [c].
-int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
-                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h,
-                               int64_t c) {
+// p->alpha [n, c] row-major, p->ninv, and one quadratic form per column in p->quad [c]  (storage: posterior_storage).
+int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c,
+                               double eps_abs, Posterior* p) {
   if (c < 1 || c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");   // the mailbox holds 62 doubles
-  if (round_up(n, kTile) < kGradRectFromN) {
-    Aug g;
-    SMN_TRY(aug_alloc(ctx, dtype, n, n, c, &g));
-    SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-    SMN_TRY(build(g.a, g.lda));
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL(identity_block_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                         reinterpret_cast<double*>(g.at(g.n_pad, 0)), g.lda, n);
-    else
-      hipLaunchKernelGGL(identity_block_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                         reinterpret_cast<float*>(g.at(g.n_pad, 0)), g.lda, n);
-    SMN_CHECK_LAUNCH(ctx);
-    SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-    return aug_finish(ctx, dtype, g, {}, y_d, c, n, eps_abs, 0.0, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, true);
-  }
   const size_t es = dtype_size(dtype);
+  if (!grad_uses_rectangle(n)) {
+    Aug g;
+    const KernelInto fill = [&](void* a, int64_t lda) {
+      SMN_TRY(build(a, lda));
+      return identity_block(ctx, dtype, static_cast<char*>(a) + es * (size_t)(round_up(n, kTile) * lda), lda, n);
+    };
+    SMN_TRY(aug_place(ctx, dtype, n, n, c, fill, &g));
+    AugFinish fin;
+    fin.y = y_d; fin.jitter_abs = eps_abs;
+    fin.mean = p->alpha; fin.cov = p->ninv; fin.ldcov = p->ldinv;
+    fin.td_identity = true;
+    return aug_finish(ctx, g, {}, fin, p);
+  }
   const int64_t n_pad = round_up(n, kTile), n_app = round_up(n + c, kTile), n_total = n_pad + n_app, lda = n_pad;
   void* av = nullptr;
   SMN_TRY(smn_workspace(ctx, 2, es * (size_t)n_total * (size_t)lda, &av));
@@ -561,13 +589,7 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
   SMN_HIP(ctx, hipMemsetAsync(a + es * (size_t)n * (size_t)lda, 0, es * (size_t)(n_total - n) * (size_t)lda, ctx->stream));
   SMN_TRY(build(a, lda));
   char* xrows = a + es * (size_t)n_pad * (size_t)lda;
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(identity_block_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<double*>(xrows), lda, n);
-  else
-    hipLaunchKernelGGL(identity_block_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<float*>(xrows), lda, n);
-  SMN_CHECK_LAUNCH(ctx);
+  SMN_TRY(identity_block(ctx, dtype, xrows, lda, n));
   SMN_TRY(fill_identity_pad(ctx, dtype, a, lda, n_pad, n));
   // Y^T in the rows behind the identity block, the absolute jitter on the diagonal, logdet / info reset: one launch
   SMN_TRY(aug_prep(ctx, dtype, a, lda, n_pad + n, n_pad, y_d, n, c, c, eps_abs != 0.0 ? n : 0, eps_abs));
@@ -577,30 +599,11 @@ int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelI
   f.prepped = f.noschur = true;
   SMN_TRY(cholesky_padded(ctx, f));
   double* quad_dev = ctx->d_scal + 8;
-  SMN_TRY(inverse_from_rows(ctx, dtype, xrows, lda, xrows + es * (size_t)n * (size_t)lda, n_pad, n, ninv_d, ldinv, alpha_d, quad_dev,
-                            c, lda));
-  double ld = 0.0, quad[48];
-  int info = 0;
-  SMN_TRY(fetch_results(ctx, quad_dev, (int)c, quad, &ld, &info));
-  if (info != 0) ld = std::nan("");
-  for (int64_t k = 0; k < c && quad_h; ++k) quad_h[k] = info != 0 ? std::nan("") : quad[k];
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
-  return SMN_OK;
+  SMN_TRY(inverse_from_rows(ctx, dtype, xrows, lda, xrows + es * (size_t)n * (size_t)lda, n_pad, n, p->ninv, p->ldinv, p->alpha,
+                            quad_dev, c, lda));
+  return fetch_results(ctx, quad_dev, (int)c, p);
 }
 
-int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
-                         double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
-                         double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h, int64_t c, bool ntk) {
-  const KernelInto build = [&](void* k_d, int64_t ldk) {
-    return smn_recursion(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, k0_d, n, n, ldk0, q_d, q_d, 1,
-                         ntk ? SMN_GET_NTK : SMN_GET_NNGP, ntk ? nullptr : k_d, ntk ? k_d : nullptr, ldk);
-  };
-  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, alpha_d, ninv_d, ldinv, quad_h, logdet_h, info_h, c);
-}
-
-namespace {
 // The storage of a Posterior, in today's order of allocations: workspace slot 5 as k0 | q (with_gram), then -K~^-1 | alpha in the
 // caller's buffers or in slot 7 carved with ld0.  The slots only grow: sizes and order are part of what a context allocates.
 int posterior_storage(smn_ctx* ctx, int dtype, int64_t n, int64_t c, bool with_gram, Posterior* p, void* ninv_d = nullptr,
@@ -620,61 +623,60 @@ int posterior_storage(smn_ctx* ctx, int dtype, int64_t n, int64_t c, bool with_g
 }
 }  // namespace
 
-int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
-                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
-                     void* ninv_d, int64_t ldinv, void* alpha_d) {
+int posterior_from_x(smn_ctx* ctx, const BuildSpec& spec, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
+                     int64_t c, double eps_abs, Posterior* p, void* ninv_d, int64_t ldinv, void* alpha_d) {
+  int net = spec.net;
   bool ntk = false;
   SMN_TRY(split_net(ctx, &net, &ntk));
-  SMN_TRY(posterior_storage(ctx, dtype, n, c, true, p, ninv_d, ldinv, alpha_d));
-  SMN_TRY(gram_lower(ctx, dtype, x_d, n, ldx, d, p->k0, p->ld0, p->q));   // (lower tiles: all the recursion and the contraction read)
-  return factor_with_identity(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, p->k0, p->ld0, p->q, n, y_d, eps_abs,
-                              p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info, c, ntk);
+  SMN_TRY(posterior_storage(ctx, spec.dtype, n, c, true, p, ninv_d, ldinv, alpha_d));
+  SMN_TRY(gram_lower(ctx, spec.dtype, x_d, n, ldx, d, p->k0, p->ld0, p->q));   // (lower tiles: all the recursion and the contraction read)
+  const KernelInto build = [&](void* k_d, int64_t ldk) {
+    return smn_recursion(ctx, spec.dtype, net, spec.act, spec.num_hiddens, spec.w_std, spec.b_std, spec.last_w_std, p->k0, n, n,
+                         p->ld0, p->q, p->q, 1, ntk ? SMN_GET_NTK : SMN_GET_NNGP, ntk ? nullptr : k_d, ntk ? k_d : nullptr, ldk);
+  };
+  return factor_built_with_identity(ctx, spec.dtype, n, build, y_d, c, eps_abs, p);
 }
 
 int posterior_from_build(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c, double eps_abs,
                          Posterior* p) {
   SMN_TRY(posterior_storage(ctx, dtype, n, c, false, p));
-  return factor_built_with_identity(ctx, dtype, n, build, y_d, eps_abs, p->alpha, p->ninv, p->ldinv, p->quad, &p->logdet, &p->info,
-                                    c);
+  return factor_built_with_identity(ctx, dtype, n, build, y_d, c, eps_abs, p);
 }
 
-int posterior_from_images(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
-                          const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c, double eps_abs,
-                          Posterior* p) {
+int posterior_from_images(smn_ctx* ctx, const BuildSpec& spec, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                          const void* y_d, int64_t c, double eps_abs, Posterior* p) {
   const KernelInto build = [&](void* k_d, int64_t ldk) {
-    return smn_kernel_cnn(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, nullptr, 0, H, W, C, SMN_FILL_LOWER, k_d,
-                          ldk);
+    return smn_kernel_cnn(ctx, spec.dtype, spec.act, spec.num_hiddens, spec.w_std, spec.b_std, spec.last_w_std, x_d, n, nullptr, 0,
+                          H, W, C, SMN_FILL_LOWER, k_d, ldk);
   };
-  return posterior_from_build(ctx, dtype, n, build, y_d, c, eps_abs, p);
+  return posterior_from_build(ctx, spec.dtype, n, build, y_d, c, eps_abs, p);
 }
 
-int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,
-                  double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov, double* quad_h,
-                  double* logdet_h, int* info_h) {
+extern "C" int smn_predict(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d,
+                           int64_t c, double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov,
+                           double* quad_h, double* logdet_h, int* info_h) {
   if (!ctx || !kj_d || !y_d) return SMN_EINVAL;
+  SMN_ENTER(ctx);
   if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "bad dtype");
   if (n <= 0 || t < 0 || c <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_predict: bad sizes");
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "more than 48 output columns");
   SMN_CHECK_LD(ctx, "smn_predict", ldk, n + t);
   if (cov_d) SMN_CHECK_LD(ctx, "smn_predict", ldcov, t);
   Aug g;
-  SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
-  const char* kb = static_cast<const char*>(kj_d);
-  SMN_HIP(ctx, hipMemsetAsync(g.at(n, 0), 0, g.es * (size_t)(g.n_total - n) * (size_t)g.lda, ctx->stream));
-  SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, kb, ldk, n, n, 1));
-  SMN_TRY(copy_matrix(ctx, dtype, g.at(g.n_pad, 0), g.lda, kb + g.es * (size_t)(n * ldk), ldk, t, n, 0));
-  SMN_TRY(copy_matrix(ctx, dtype, g.at(g.n_pad, g.n_pad), g.lda, kb + g.es * (size_t)(n * ldk + n), ldk, t, t, 1));
-  SMN_TRY(fill_identity_pad(ctx, dtype, g.a, g.lda, g.n_pad, n));
-  return aug_finish(ctx, dtype, g, {}, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
-}
-
-extern "C" int smn_predict(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d,
-                           int64_t c, double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov,
-                           double* quad_h, double* logdet_h, int* info_h) {
-  if (!ctx) return SMN_EINVAL;
-  SMN_ENTER(ctx);
-  return predict_joint(ctx, dtype, kj_d, n, t, ldk, y_d, c, ridge_rel, ridge_abs, mean_d, cov_d, ldcov, quad_h, logdet_h,
-                       info_h);
+  const KernelInto fill = [&](void*, int64_t) {   // K_dd, K_td and K_tt of the joint kernel, each into its block
+    const char* kb = static_cast<const char*>(kj_d);
+    SMN_TRY(copy_matrix(ctx, dtype, g.a, g.lda, kb, ldk, n, n, 1));
+    SMN_TRY(copy_matrix(ctx, dtype, g.at(g.n_pad, 0), g.lda, kb + g.es * (size_t)(n * ldk), ldk, t, n, 0));
+    return copy_matrix(ctx, dtype, g.at(g.n_pad, g.n_pad), g.lda, kb + g.es * (size_t)(n * ldk + n), ldk, t, t, 1);
+  };
+  SMN_TRY(aug_place(ctx, dtype, n, t, c, fill, &g));
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = ridge_abs; fin.ridge_rel = ridge_rel;
+  fin.mean = mean_d; fin.cov = cov_d; fin.ldcov = ldcov;
+  HeadScalars h;
+  SMN_TRY(aug_finish(ctx, g, {}, fin, &h));
+  publish_head(h, c, true, n, 0.0, 1.0, nullptr, nullptr, quad_h, logdet_h, info_h);   // (a predictive entry: the per-column forms only)
+  return SMN_OK;
 }
 
 extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
@@ -692,24 +694,20 @@ extern "C" int smn_spr_loss(smn_ctx* ctx, int dtype, int net, int act, int num_h
   Aug g;
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, 1, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
+  // the input Gram depends on x only: reused from the context's cache while x is unchanged (decided by content, on the device).
+  // Theta: the plain fused build from workspace slot 0; the Gram cache is neither read nor written
+  const GramPlan gram = ntk ? GramPlan{} : gram_cache_plan(ctx, dtype, net, n, d, k_pad(dtype, d), g.n_total);
   BuildOut built;
-  double quad = 0.0, ld = 0.0;
-  int info = 0;
-  if (ntk) {   // Theta: the plain fused build from workspace slot 0; the Gram cache is neither read nor written
-    SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, nullptr, true));
-    SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info));
-  } else {
-    // the input Gram depends on x only: reused from the context's cache while x is unchanged (decided by content, on the device)
-    const GramPlan gram = gram_cache_plan(ctx, dtype, net, n, d, k_pad(dtype, d), g.n_total);
-    int rc = aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, &gram);
-    if (rc == SMN_OK) rc = aug_finish(ctx, dtype, g, built, y_d, 1, n, eps_abs, 0.0, nullptr, nullptr, 0, &quad, &ld, &info);
-    gram_cache_settle(ctx, gram, rc);
-    if (rc != SMN_OK) return rc;
-  }
-  if (logpdf_h) *logpdf_h = logpdf_from(quad, ld, n, df, scale, info);
-  if (quad_h) *quad_h = quad;
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
+  AugBuild bld;
+  bld.out = &built; bld.gram = &gram; bld.ntk = ntk;
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = eps_abs;
+  HeadScalars h;
+  int rc = aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, bld);
+  if (rc == SMN_OK) rc = aug_finish(ctx, g, built, fin, &h);
+  gram_cache_settle(ctx, gram, rc);
+  if (rc != SMN_OK) return rc;
+  publish_head(h, 1, false, n, df, scale, logpdf_h, quad_h, nullptr, logdet_h, info_h);
   return SMN_OK;
 }
 
@@ -731,11 +729,14 @@ extern "C" int smn_spr_loss_multi(smn_ctx* ctx, int dtype, int net, int act, int
   SMN_TRY(aug_alloc(ctx, dtype, n, 0, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
-  double quad[48], ld = 0.0;
-  int info = 0;
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, 0, nullptr, nullptr, nullptr, &built, false, nullptr, ntk));
-  SMN_TRY(aug_finish(ctx, dtype, g, built, y_d, c, n, eps_abs, 0.0, nullptr, nullptr, 0, quad, &ld, &info));
-  publish_head(quad, c, true, ld, info, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
+  AugBuild bld;
+  bld.out = &built; bld.ntk = ntk;
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = eps_abs;
+  HeadScalars h;
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, x_d, ldx, d, bld));
+  SMN_TRY(aug_finish(ctx, g, built, fin, &h));
+  publish_head(h, c, true, n, df, scale, logpdf_h, quad_h, quad_cols_h, logdet_h, info_h);
   return SMN_OK;
 }
 
@@ -825,13 +826,8 @@ int spr_batch(smn_ctx* ctx, const char* who, int dtype, int net, int act, int nu
   if (t > 0) SMN_CHECK_LD(ctx, who, ldxt, d);
   if (cov_d) SMN_CHECK_LD(ctx, who, ldcov, t);
   const size_t es = dtype_size(dtype);
-  Aug g;
-  g.n = n; g.t = t; g.c = c;
-  g.n_pad = round_up(n, kTile);
-  g.n_total = g.n_pad + round_up(t + c, kTile);
-  g.lda = g.n_total;
-  g.es = es;
-  const size_t per = es * (size_t)g.n_total * (size_t)g.n_total;
+  Aug g = aug_shape(dtype, n, t, c);   // one problem; `chunk` of them side by side below
+  const size_t per = g.bytes();
   int chunk = (int)std::min<size_t>((size_t)nprob, std::max<size_t>(1, ctx->batch_bytes / per));
   if (chunk > 65535) chunk = 65535;   // grid.y / grid.z
   SMN_TRY(smn_workspace(ctx, 2, per * (size_t)chunk, &g.a));
@@ -850,52 +846,46 @@ int spr_batch(smn_ctx* ctx, const char* who, int dtype, int net, int act, int nu
   BuildSpec spec{dtype, net, act, num_hiddens, w_std[0], b_std[0], last_w_std[0]};
   for (int p0 = 0; p0 < nprob; p0 += chunk) {
     const int nb = std::min(chunk, nprob - p0);
-    SMN_TRY(aug_build(ctx, spec, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, nb, w_std + p0, b_std + p0, last_w_std + p0));
+    AugBuild bld;
+    bld.nbatch = nb; bld.bw = w_std + p0; bld.bb = b_std + p0; bld.blw = last_w_std + p0;
+    SMN_TRY(aug_build(ctx, spec, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, bld));
     SMN_HIP(ctx, hipMemcpyAsync(sh_d, shift_abs + p0, sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
     if (ridge_rel) {
       SMN_HIP(ctx, hipMemcpyAsync(rel_d, ridge_rel + p0, sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-      if (dtype == SMN_F64)
-        hipLaunchKernelGGL(batch_trace_kernel<double>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, static_cast<const double*>(g.a), g.lda, bstride, n, tr_d);
-      else
-        hipLaunchKernelGGL(batch_trace_kernel<float>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, static_cast<const float*>(g.a), g.lda, bstride, n, tr_d);
+      by_dtype(dtype, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL(batch_trace_kernel<T>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, static_cast<const T*>(g.a), g.lda, bstride, n, tr_d);
+      });
     }
-    {
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
       dim3 gp((unsigned)((g.n_total + 255) / 256), (unsigned)c, (unsigned)nb);
-      if (dtype == SMN_F64)
-        hipLaunchKernelGGL(batch_prep_kernel<double>, gp, dim3(256), 0, ctx->stream, static_cast<double*>(g.a), g.lda, bstride, g.n_pad + t, g.n_total,
-                           static_cast<const double*>(y_d), n, c, c, n, sh_d, ridge_rel ? rel_d : nullptr, tr_d, ld_d, info_d);
-      else
-        hipLaunchKernelGGL(batch_prep_kernel<float>, gp, dim3(256), 0, ctx->stream, static_cast<float*>(g.a), g.lda, bstride, g.n_pad + t, g.n_total,
-                           static_cast<const float*>(y_d), n, c, c, n, sh_d, ridge_rel ? rel_d : nullptr, tr_d, ld_d, info_d);
-    }
+      hipLaunchKernelGGL(batch_prep_kernel<T>, gp, dim3(256), 0, ctx->stream, static_cast<T*>(g.a), g.lda, bstride, g.n_pad + t, g.n_total,
+                         static_cast<const T*>(y_d), n, c, c, n, sh_d, ridge_rel ? rel_d : nullptr, tr_d, ld_d, info_d);
+    });
     SMN_CHECK_LAUNCH(ctx);
     FactorCall f{dtype, g.a, g.n_total, g.n_pad, g.lda, n, 0.0, 0.0, false};
     f.prepped = true;
     f.batch = nb; f.batch_stride = bstride; f.batch_logdet = ld_d; f.batch_info = info_d;
     SMN_TRY(cholesky_padded(ctx, f));
-    {
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
       const int64_t w = std::max<int64_t>(std::max(t, c), 1);
       dim3 ge((unsigned)((w + 255) / 256), (unsigned)std::min<int64_t>(t + 1, 4096), (unsigned)nb);
       char* mean_p = mean_d ? static_cast<char*>(mean_d) + es * (size_t)p0 * (size_t)t * (size_t)c : nullptr;
       char* cov_p = cov_d ? static_cast<char*>(cov_d) + es * (size_t)p0 * (size_t)t * (size_t)ldcov : nullptr;
       char* var_p = var_d ? static_cast<char*>(var_d) + es * (size_t)p0 * (size_t)t : nullptr;
-      if (dtype == SMN_F64)
-        hipLaunchKernelGGL(batch_extract_kernel<double>, ge, dim3(256), 0, ctx->stream, static_cast<const double*>(g.a), g.lda, bstride, g.n_pad, t, c,
-                           reinterpret_cast<double*>(mean_p), reinterpret_cast<double*>(cov_p), ldcov, reinterpret_cast<double*>(var_p), res_d, ld_d, info_d);
-      else
-        hipLaunchKernelGGL(batch_extract_kernel<float>, ge, dim3(256), 0, ctx->stream, static_cast<const float*>(g.a), g.lda, bstride, g.n_pad, t, c,
-                           reinterpret_cast<float*>(mean_p), reinterpret_cast<float*>(cov_p), ldcov, reinterpret_cast<float*>(var_p), res_d, ld_d, info_d);
-    }
+      hipLaunchKernelGGL(batch_extract_kernel<T>, ge, dim3(256), 0, ctx->stream, static_cast<const T*>(g.a), g.lda, bstride, g.n_pad, t, c,
+                         reinterpret_cast<T*>(mean_p), reinterpret_cast<T*>(cov_p), ldcov, reinterpret_cast<T*>(var_p), res_d, ld_d, info_d);
+    });
     SMN_CHECK_LAUNCH(ctx);
     SMN_HIP(ctx, hipMemcpyAsync(res_h.data(), res_d, sizeof(double) * (size_t)nb * (2 + (size_t)c), hipMemcpyDeviceToHost, ctx->stream));
     SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < nb; ++b) {
-      const double* r = &res_h[(size_t)b * (2 + (size_t)c)];
-      int info = (int)r[1];
-      if (info == INT_MAX) info = 0;
-      if (info_h) info_h[p0 + b] = info;
-      if (logdet_h) logdet_h[p0 + b] = info ? std::nan("") : r[0];
-      for (int64_t k = 0; k < c && quad_h; ++k) quad_h[(size_t)(p0 + b) * (size_t)c + (size_t)k] = info ? std::nan("") : r[2 + k];
+      HeadScalars h;
+      head_decode(&res_h[(size_t)b * (2 + (size_t)c)], (int)c, &h);
+      publish_head(h, c, true, n, 0.0, 1.0, nullptr, nullptr, quad_h ? quad_h + (size_t)(p0 + b) * (size_t)c : nullptr,
+                   logdet_h ? logdet_h + p0 + b : nullptr, info_h ? info_h + p0 + b : nullptr);
     }
   }
   return SMN_OK;
@@ -953,10 +943,10 @@ extern "C" int smn_spr_loss_batch(smn_ctx* ctx, int dtype, int net, int act, int
   SMN_TRY(spr_batch(ctx, "smn_spr_loss_batch", dtype, net, act, num_hiddens, nprob, w_std, b_std, last_w_std, x_d, n, ldx, nullptr, 0, 0, d,
                     y_d, 1, nullptr, eps_abs, nullptr, nullptr, 0, nullptr, quad.data(), ld.data(), info.data()));
   for (int b = 0; b < nprob; ++b) {
-    if (logpdf_h) logpdf_h[b] = logpdf_from(quad[(size_t)b], ld[(size_t)b], n, df ? df[b] : 0.0, scale ? scale[b] : 1.0, info[(size_t)b]);
-    if (quad_h) quad_h[b] = quad[(size_t)b];
-    if (logdet_h) logdet_h[b] = ld[(size_t)b];
-    if (info_h) info_h[b] = info[(size_t)b];
+    HeadScalars h;
+    h.quad[0] = quad[(size_t)b]; h.logdet = ld[(size_t)b]; h.info = info[(size_t)b];
+    publish_head(h, 1, false, n, df ? df[b] : 0.0, scale ? scale[b] : 1.0, logpdf_h ? logpdf_h + b : nullptr, quad_h ? quad_h + b : nullptr,
+                 nullptr, logdet_h ? logdet_h + b : nullptr, info_h ? info_h + b : nullptr);
   }
   return SMN_OK;
 }
@@ -997,7 +987,14 @@ extern "C" int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int nu
   SMN_TRY(aug_alloc(ctx, dtype, n, t, c, &g));
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   BuildOut built;
-  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, 0, nullptr, nullptr, nullptr, &built, ridge_rel != 0.0,
-                    nullptr, ntk));
-  return aug_finish(ctx, dtype, g, built, y_d, c, n, ridge_abs, ridge_rel, mean_d, cov_d, ldcov, quad_h, logdet_h, info_h);
+  AugBuild bld;
+  bld.out = &built; bld.want_trace = ridge_rel != 0.0; bld.ntk = ntk;
+  AugFinish fin;
+  fin.y = y_d; fin.jitter_abs = ridge_abs; fin.ridge_rel = ridge_rel;
+  fin.mean = mean_d; fin.cov = cov_d; fin.ldcov = ldcov;
+  HeadScalars h;
+  SMN_TRY(aug_build(ctx, s, g, x_d, ldx, t > 0 ? xt_d : x_d, t > 0 ? ldxt : ldx, d, bld));
+  SMN_TRY(aug_finish(ctx, g, built, fin, &h));
+  publish_head(h, c, true, n, 0.0, 1.0, nullptr, nullptr, quad_h, logdet_h, info_h);   // (a predictive entry: the per-column forms only)
+  return SMN_OK;
 }

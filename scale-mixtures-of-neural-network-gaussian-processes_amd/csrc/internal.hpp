@@ -1,5 +1,6 @@
 // internal.hpp — C++-side interfaces between the translation units of libsmnngp.so.
 #pragma once
+#include <climits>
 #include <cmath>
 #include <functional>
 
@@ -139,43 +140,44 @@ struct FactorCall {
   const smn_ctx::Arrival* arrivals = nullptr; size_t n_arrivals = 0; hipStream_t arrivals_on = nullptr;
 };
 int cholesky_padded(smn_ctx* ctx, const FactorCall& f);
-int predict_joint(smn_ctx* ctx, int dtype, void* kj_d, int64_t n, int64_t t, int64_t ldk, const void* y_d, int64_t c,
-                  double ridge_rel, double ridge_abs, void* mean_d, void* cov_d, int64_t ldcov, double* quad_h,
-                  double* logdet_h, int* info_h);
-// alpha = K~^-1 y and -K~^-1 for the analytic gradients: a no-Schur factorisation of the rectangle [[K~], [I], [y^T]] (K from
-// the Gram matrix k0 by the layer recursion, in place), then -L^-T L^-1 as one launch (heads.hip)
-// c target columns (y_d [n, c] row-major, 1 <= c <= 48): [[K~], [I], [Y^T]] with n_total = n_pad + round_up(n + c, 128);
-// alpha_d [n, c] row-major, quad_h [c] (one quadratic form per column).
-int factor_with_identity(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
-                         double last_w_std, const void* k0_d, int64_t ldk0, const void* q_d, int64_t n, const void* y_d,
-                         double eps_abs, void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h,
-                         int* info_h, int64_t c = 1, bool ntk = false);   // ntk: Theta by the same recursion instead of K
-// the same with K written by the caller: build(k_d, ldk) fills the lower triangle of K (n rows) in the factorisation workspace
+// K written by the caller: fill(k_d, ldk) puts the lower triangle of K (n rows) into the matrix it is handed (heads.hip)
 using KernelInto = std::function<int(void* k_d, int64_t ldk)>;
-int factor_built_with_identity(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, double eps_abs,
-                               void* alpha_d, void* ninv_d, int64_t ldinv, double* quad_h, double* logdet_h, int* info_h,
-                               int64_t c = 1);
 // Gaussian / multivariate-t log-pdf from (quad = y^T cov^-1 y, logdet = log det cov) in dimension n (heads.hip)
 double logpdf_from(double quad, double logdet, int64_t n, double df, double scale, int info);
+// What a factorisation leaves for the host: one quadratic form per target column, logdet K~ and info (0, or the first failing
+// pivot).  THE NaN CONVENTION: info != 0 makes logdet and every quadratic form NaN -- head_decode applies it to a device record
+// {logdet, info as a double (INT_MAX: never set = 0), quad[0..nq)}, the layout of the mailbox and of a row of spr_batch's res.
+struct HeadScalars {
+  double quad[48]; double logdet = 0.0; int info = 0;
+};
+inline void head_decode(const volatile double* rec, int nq, HeadScalars* h) {
+  h->info = (int)rec[1];
+  if (h->info == INT_MAX) h->info = 0;
+  h->logdet = h->info != 0 ? std::nan("") : rec[0];
+  for (int i = 0; i < nq; ++i) h->quad[i] = h->info != 0 ? std::nan("") : rec[2 + i];
+}
+// The mailbox, decoded.  fetch_mail: after a launch that published into it (extract_posterior(..., publish = true)) -- ONE
+// synchronisation and the read.  fetch_results: the tiny publish launch for nq device doubles (quadratic forms), then that.
+int fetch_mail(smn_ctx* ctx, int nq, HeadScalars* h);
+int fetch_results(smn_ctx* ctx, const double* quad_dev, int nq, HeadScalars* h);
 // The joint head of c target columns from their quadratic forms, published to whichever outputs the caller wants: total quad,
 // log-pdf in dimension n c with logdet c logdet K~, the per-column quads, logdet, info, and NaN terms when the matrix was not
 // positive definite.  Returns the total.  A single-output entry (multi = false) publishes its one quadratic form as it is:
 // 0.0 + quad would turn a -0.0 into +0.0.
-inline double publish_head(const double* quad, int64_t c, bool multi, double ld, int info, int64_t n, double df, double scale,
-                           double* logpdf_h, double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h,
-                           double* terms_h = nullptr) {
-  double tot = quad[0];
+inline double publish_head(const HeadScalars& h, int64_t c, bool multi, int64_t n, double df, double scale, double* logpdf_h,
+                           double* quad_h, double* quad_cols_h, double* logdet_h, int* info_h, double* terms_h = nullptr) {
+  double tot = h.quad[0];
   if (multi) {
     tot = 0.0;
-    for (int64_t k = 0; k < c; ++k) tot += quad[k];
+    for (int64_t k = 0; k < c; ++k) tot += h.quad[k];
   }
-  if (info != 0) tot = std::nan("");
-  if (logpdf_h) *logpdf_h = logpdf_from(tot, (double)c * ld, n * c, df, scale, info);
+  if (h.info != 0) tot = std::nan("");
+  if (logpdf_h) *logpdf_h = logpdf_from(tot, (double)c * h.logdet, n * c, df, scale, h.info);
   if (quad_h) *quad_h = tot;
-  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = info != 0 ? std::nan("") : quad[k];
-  if (logdet_h) *logdet_h = ld;
-  if (info_h) *info_h = info;
-  for (int i = 0; i < 4 && terms_h && info != 0; ++i) terms_h[i] = std::nan("");
+  for (int64_t k = 0; k < c && quad_cols_h; ++k) quad_cols_h[k] = h.info != 0 ? std::nan("") : h.quad[k];
+  if (logdet_h) *logdet_h = h.logdet;
+  if (info_h) *info_h = h.info;
+  for (int i = 0; i < 4 && terms_h && h.info != 0; ++i) terms_h[i] = std::nan("");
   return tot;
 }
 // coef of the Student-t head of c columns, G = coef A A^T - c K~^-1: (df + n c) / ((df + Q / s) s), Q = the total quadratic
@@ -189,42 +191,37 @@ inline double lml_coef(double df, double scale, double quad_total, int64_t n, in
 // (NaN in quad and logdet when info != 0).  The MLP / dense-ResNet builder also leaves the Gram matrix k0 = x x^T / d (ld = ld0)
 // and its diagonal q in slot 5: what the tangent pass of grad.hip reads.  A new objective adds a tail behind one of these, a new
 // kernel family a builder beside them; neither copies the pipeline.
-struct Posterior {
+struct Posterior : HeadScalars {
   void* k0 = nullptr; void* q = nullptr; int64_t ld0 = 0;
   void* ninv = nullptr; int64_t ldinv = 0; void* alpha = nullptr;
-  double quad[48]; double logdet = 0.0; int info = 0;
 };
-// from x [n, d]: gram_lower + factor_with_identity.  ninv_d / alpha_d: the caller's storage (ld = ldinv) instead of slot 7.
-// net may carry SMN_NET_NTK: the posterior is then that of Theta~ = Theta + eps I.
-int posterior_from_x(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
-                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c, double eps_abs, Posterior* p,
-                     void* ninv_d = nullptr, int64_t ldinv = 0, void* alpha_d = nullptr);
-// from K written by `build` into the factorisation workspace (factor_built_with_identity)
+// from x [n, d]: gram_lower, then K (spec.net may carry SMN_NET_NTK: Theta, the posterior is that of Theta~ = Theta + eps I) by
+// the layer recursion of the Gram matrix.  ninv_d / alpha_d: the caller's storage (ld = ldinv) instead of slot 7.
+int posterior_from_x(smn_ctx* ctx, const BuildSpec& spec, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d,
+                     int64_t c, double eps_abs, Posterior* p, void* ninv_d = nullptr, int64_t ldinv = 0, void* alpha_d = nullptr);
+// from K written by `build` into the factorisation workspace
 int posterior_from_build(smn_ctx* ctx, int dtype, int64_t n, const KernelInto& build, const void* y_d, int64_t c, double eps_abs,
                          Posterior* p);
-// from images x [n, H, W, C] under get_cnn_kernel: the lower build of smn_kernel_cnn
-int posterior_from_images(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
-                          const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, const void* y_d, int64_t c, double eps_abs,
-                          Posterior* p);
+// from images x [n, H, W, C] under get_cnn_kernel (spec.net is not read): the lower build of smn_kernel_cnn
+int posterior_from_images(smn_ctx* ctx, const BuildSpec& spec, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
+                          const void* y_d, int64_t c, double eps_abs, Posterior* p);
 // true from the size on at which the gradient takes the rectangle route instead of the joint factorisation (heads.hip)
 bool grad_uses_rectangle(int64_t n);
-int fetch_logdet_info(smn_ctx* ctx, double* logdet, int* info);
 int gram_lower(smn_ctx* ctx, int dtype, const void* x_d, int64_t n, int64_t ldx, int64_t d, void* k0_d, int64_t ldk, void* q_d);
 // smn_recursion's symmetric NNGP form (lower 64x64 tiles + mirror, exact diagonal) for nbatch problems over ONE Gram matrix:
-// problem g runs under (w_std[g], b_std[g], last_w_std[g]) (host arrays) and writes out_d + g * out_bs elements (ld = ldo).
+// problem g runs under (w_std[g], b_std[g], last_w_std[g]) (host arrays; the spec's own three are not read) and writes
+// out_d + g * out_bs elements (ld = ldo).
 // One table launch and one recursion launch with grid.y = nbatch; per problem the bits of the serial call.
 // No synchronisation: the host source of the layer programs' upload is kept in `stage`, which the caller leaves alone until it
 // has synchronised the stream itself.
-int recursion_lower_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nbatch, const double* w_std,
-                          const double* b_std, const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
-                          const void* q_d, void* out_d, int64_t ldo, int64_t out_bs, std::vector<char>& stage);
+int recursion_lower_batch(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const double* w_std, const double* b_std,
+                          const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0, const void* q_d, void* out_d,
+                          int64_t ldo, int64_t out_bs, std::vector<char>& stage);
 // -x x^T (lower, into neg_inv [n, n] ld = ldo) and alpha = x z from the rows x [n, kcols] (ld = ldx, row i zero left of its
 // 128-column tile) and the vector z [kcols]; *quad_dev = z^T z.  c > 1: z [c, kcols] (ld = ldz) holds c vectors, alpha is
 // [n, c] row-major and quad_dev [c].  cholesky.hip.
 int inverse_from_rows(smn_ctx* ctx, int dtype, const void* x, int64_t ldx, const void* z, int64_t kcols, int64_t n,
                       void* neg_inv, int64_t ldo, void* alpha, double* quad_dev, int64_t c = 1, int64_t ldz = 0);
-// logdet, info and nq device doubles (quadratic forms) through the pinned mailbox: one tiny kernel + ONE synchronisation
-int fetch_results(smn_ctx* ctx, const double* quad_dev, int nq, double* quad_h, double* logdet, int* info);
 
 // small helpers implemented in util.hip
 int fill_identity_pad(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t n_pad, int64_t n_valid);
@@ -243,8 +240,6 @@ int extract_posterior(smn_ctx* ctx, int dtype, const void* a, int64_t lda, int64
 int aug_prep(smn_ctx* ctx, int dtype, void* a, int64_t lda, int64_t row0, int64_t ncols, const void* y, int64_t n,
              int64_t c, int64_t ldy, int64_t n_shift, double jitter_abs, int64_t col0 = 0, hipStream_t st = nullptr,
              double ridge_rel = 0.0, int64_t n_trace = 0);
-// the mailbox after a launch that published into it (extract_posterior(..., publish = true)): synchronise and read
-int fetch_mail(smn_ctx* ctx, int nq, double* quad_h, double* logdet, int* info);
 int solve_rows_padded(smn_ctx* ctx, int dtype, void* a, int64_t n_total, int64_t n_factor, int64_t lda);
 // Schur update of solved appended rows: the lower tiles of a[n_factor:n_total, n_factor:n_total] -= R R^T with R = rows
 // [n_factor, n_total) x columns [0, n_factor) -- the far update of cholesky_padded, one launch per super-panel of columns

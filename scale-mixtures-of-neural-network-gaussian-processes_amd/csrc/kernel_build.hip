@@ -1044,13 +1044,12 @@ int recursion_batch_t(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const dou
 
 }  // namespace
 
-int recursion_lower_batch(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, int nbatch, const double* w_std,
-                          const double* b_std, const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0,
-                          const void* q_d, void* out_d, int64_t ldo, int64_t out_bs, std::vector<char>& stage) {
-  BuildSpec s{dtype, net, act, num_hiddens, 1.0, 0.0, 1.0};
-  if (dtype == SMN_F64)
-    return recursion_batch_t<double>(ctx, s, nbatch, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, out_d, ldo, out_bs, stage);
-  return recursion_batch_t<float>(ctx, s, nbatch, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, out_d, ldo, out_bs, stage);
+int recursion_lower_batch(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const double* w_std, const double* b_std,
+                          const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0, const void* q_d, void* out_d,
+                          int64_t ldo, int64_t out_bs, std::vector<char>& stage) {
+  return by_dtype(spec.dtype, [&](auto e) {
+    return recursion_batch_t<decltype(e)>(ctx, spec, nbatch, w_std, b_std, last_w_std, k0_d, n, ldk0, q_d, out_d, ldo, out_bs, stage);
+  });
 }
 
 int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, int64_t d,
@@ -1059,25 +1058,21 @@ int pad_rows(smn_ctx* ctx, int dtype, const void* src, int64_t n, int64_t lds, i
   const unsigned blocks = (unsigned)((rows_pad + 3) / 4);
   ProfScope ps(ctx, PROF_PREP, ctx->stream);
   if (changed) {   // compare form (Gram cache)
-    if (dtype == SMN_F64)
-      hipLaunchKernelGGL((pad_rows_kernel<double, true>), dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const double*>(src),
-                         n, lds, d, static_cast<double*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                         static_cast<const double*>(src2), n2, lds2, changed, gen);
-    else
-      hipLaunchKernelGGL((pad_rows_kernel<float, true>), dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const float*>(src),
-                         n, lds, d, static_cast<float*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                         static_cast<const float*>(src2), n2, lds2, changed, gen);
+    by_dtype(dtype, [&](auto e) {
+      using T = decltype(e);
+      hipLaunchKernelGGL((pad_rows_kernel<T, true>), dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const T*>(src),
+                         n, lds, d, static_cast<T*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
+                         static_cast<const T*>(src2), n2, lds2, changed, gen);
+    });
     SMN_CHECK_LAUNCH(ctx);
     return SMN_OK;
   }
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(pad_rows_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const double*>(src),
-                       n, lds, d, static_cast<double*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                       static_cast<const double*>(src2), n2, lds2, static_cast<unsigned*>(nullptr), 0u);
-  else
-    hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const float*>(src),
-                       n, lds, d, static_cast<float*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
-                       static_cast<const float*>(src2), n2, lds2, static_cast<unsigned*>(nullptr), 0u);
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(pad_rows_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<const T*>(src),
+                       n, lds, d, static_cast<T*>(dst), rows_pad, kp, 1.0 / (double)d, q, rows_a,
+                       static_cast<const T*>(src2), n2, lds2, static_cast<unsigned*>(nullptr), 0u);
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -1215,7 +1210,7 @@ void gram_cache_settle(smn_ctx* ctx, const GramPlan& p, int rc) {
 }
 
 int run_build(smn_ctx* ctx, const BuildCall& c, BuildOut* out) {
-  return c.spec.dtype == SMN_F64 ? run_build_t<double>(ctx, c, out) : run_build_t<float>(ctx, c, out);
+  return by_dtype(c.spec.dtype, [&](auto e) { return run_build_t<decltype(e)>(ctx, c, out); });
 }
 
 // Size of the corner of a split build: the corner's tiles take about as long on the bulk stream's CUs as the first
@@ -1494,7 +1489,7 @@ extern "C" int smn_recursion(smn_ctx* ctx, int dtype, int net, int act, int num_
   SMN_CHECK_LD(ctx, "smn_recursion", ldk0, n2);
   SMN_CHECK_LD(ctx, "smn_recursion", ldk, n2);
   BuildSpec s{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
-  if (dtype == SMN_F64)
-    return recursion_t<double>(ctx, s, k0_d, n1, n2, ldk0, q1_d, q2_d, symmetric, get_mask, nngp_d, ntk_d, ldk);
-  return recursion_t<float>(ctx, s, k0_d, n1, n2, ldk0, q1_d, q2_d, symmetric, get_mask, nngp_d, ntk_d, ldk);
+  return by_dtype(dtype, [&](auto e) {
+    return recursion_t<decltype(e)>(ctx, s, k0_d, n1, n2, ldk0, q1_d, q2_d, symmetric, get_mask, nngp_d, ntk_d, ldk);
+  });
 }

@@ -312,7 +312,7 @@ int loo_fill_nan(smn_ctx* ctx, void* a, int64_t count) {
 }
 
 int loo_fill_nan(smn_ctx* ctx, int dtype, void* a, int64_t count) {
-  return dtype == SMN_F64 ? loo_fill_nan<double>(ctx, a, count) : loo_fill_nan<float>(ctx, a, count);
+  return by_dtype(dtype, [&](auto e) { return loo_fill_nan<decltype(e)>(ctx, a, count); });
 }
 
 double loo_digamma(double x) {   // x > 0: recurrence up to 16, then the asymptotic series (first term left out: 0.021 / x^12 < 1e-16)
@@ -410,9 +410,9 @@ int loo_head_t(smn_ctx* ctx, const void* nkinv, int64_t ldk, const void* alpha, 
 
 int loo_head(smn_ctx* ctx, int dtype, const void* nkinv, int64_t ldk, const void* alpha, const void* y, int64_t n, int64_t c,
              double df, double scale, double* lam_h, void* mean, void* scale2, double* dhead_h, void* g, int64_t ldg) {
-  if (dtype == SMN_F64)
-    return loo_head_t<double>(ctx, nkinv, ldk, alpha, y, n, c, df, scale, lam_h, mean, scale2, dhead_h, g, ldg);
-  return loo_head_t<float>(ctx, nkinv, ldk, alpha, y, n, c, df, scale, lam_h, mean, scale2, dhead_h, g, ldg);
+  return by_dtype(dtype, [&](auto e) {
+    return loo_head_t<decltype(e)>(ctx, nkinv, ldk, alpha, y, n, c, df, scale, lam_h, mean, scale2, dhead_h, g, ldg);
+  });
 }
 
 // not positive definite: NaN in every output
@@ -500,8 +500,9 @@ extern "C" int smn_spr_loo_grad(smn_ctx* ctx, int dtype, int net, int act, int n
   SMN_TRY(loo_check(ctx, "smn_spr_loo_grad", dtype, n, c, df, scale));
   if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_spr_loo_grad: bad sizes");
   SMN_CHECK_LD(ctx, "smn_spr_loo_grad", ldx, d);
+  const BuildSpec spec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   Posterior p;
-  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p));
+  SMN_TRY(posterior_from_x(ctx, spec, x_d, n, ldx, d, y_d, c, eps_abs, &p));
   void* zeros = nullptr;
   SMN_TRY(loo_seed(ctx, dtype, p, y_d, n, c, df, scale, loo_logpdf_h, dhead_h, info_h, terms_h, loo_mean_d, loo_scale2_d, &zeros));
   if (!zeros) return SMN_OK;
@@ -522,8 +523,9 @@ extern "C" int smn_spr_cnn_loo_grad(smn_ctx* ctx, int dtype, int act, int num_hi
   if (H * W > SMN_CNN_GRAD_MAX_PIXELS)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_spr_cnn_loo_grad: images of more than %d pixels", SMN_CNN_GRAD_MAX_PIXELS);
   if (!(last_w_std != 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_spr_cnn_loo_grad: bad hyper-parameters");
+  const BuildSpec spec{dtype, SMN_NET_MLP, act, num_hiddens, w_std, b_std, last_w_std};   // (net: not read by the conv build)
   Posterior p;
-  SMN_TRY(posterior_from_images(ctx, dtype, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, H, W, C, y_d, c, eps_abs, &p));
+  SMN_TRY(posterior_from_images(ctx, spec, x_d, n, H, W, C, y_d, c, eps_abs, &p));
   void* zeros = nullptr;
   SMN_TRY(loo_seed(ctx, dtype, p, y_d, n, c, df, scale, loo_logpdf_h, dhead_h, info_h, terms_h, loo_mean_d, loo_scale2_d, &zeros));
   if (!zeros) return SMN_OK;
@@ -547,9 +549,9 @@ extern "C" int smn_spr_kinv(smn_ctx* ctx, int dtype, int net, int act, int num_h
   SMN_CHECK_LD(ctx, "smn_spr_kinv", ldkinv, n);
   if (ldkinv % (16 / (int64_t)es))
     return smn_fail(ctx, SMN_EINVAL, "smn_spr_kinv: ldkinv = %lld is not a multiple of 16 bytes", (long long)ldkinv);
+  const BuildSpec spec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
   Posterior p;
-  SMN_TRY(posterior_from_x(ctx, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, y_d, c, eps_abs, &p,
-                           neg_kinv_d, ldkinv, alpha_d));
+  SMN_TRY(posterior_from_x(ctx, spec, x_d, n, ldx, d, y_d, c, eps_abs, &p, neg_kinv_d, ldkinv, alpha_d));
   if (logdet_h) *logdet_h = p.logdet;
   if (info_h) *info_h = p.info;
   return SMN_OK;

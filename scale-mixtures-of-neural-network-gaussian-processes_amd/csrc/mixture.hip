@@ -121,15 +121,13 @@ extern "C" int smn_mixture_nll(smn_ctx* ctx, int dtype, int nprob, int64_t t, co
   if (skip_h) SMN_HIP(ctx, hipMemcpyAsync(skip_d, skip_h, sizeof(int) * (size_t)nprob, hipMemcpyHostToDevice, st));
   const size_t lds = sizeof(double) * (2 * (size_t)nsamples + 256);
   dim3 grid((unsigned)nmix, (unsigned)nprob);
-  if (dtype == SMN_F64) {
-    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(mixture_nll_kernel<double>), lds));
-    hipLaunchKernelGGL(mixture_nll_kernel<double>, grid, dim3(256), lds, st, static_cast<const double*>(mean_d), static_cast<const double*>(var_d), t,
+  SMN_TRY(by_dtype(dtype, [&](auto e) -> int {
+    using T = decltype(e);
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(mixture_nll_kernel<T>), lds));
+    hipLaunchKernelGGL(mixture_nll_kernel<T>, grid, dim3(256), lds, st, static_cast<const T*>(mean_d), static_cast<const T*>(var_d), t,
                        quad_d, ld_d, skip_h ? skip_d : nullptr, y_d, y_mean, y_std, (double)n, nsamples, q_d, r_d, out_d);
-  } else {
-    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(mixture_nll_kernel<float>), lds));
-    hipLaunchKernelGGL(mixture_nll_kernel<float>, grid, dim3(256), lds, st, static_cast<const float*>(mean_d), static_cast<const float*>(var_d), t,
-                       quad_d, ld_d, skip_h ? skip_d : nullptr, y_d, y_mean, y_std, (double)n, nsamples, q_d, r_d, out_d);
-  }
+    return SMN_OK;
+  }));
   SMN_CHECK_LAUNCH(ctx);
   SMN_HIP(ctx, hipMemcpyAsync(tnll_h, out_d, sizeof(double) * (size_t)nprob * (size_t)nmix, hipMemcpyDeviceToHost, st));
   SMN_HIP(ctx, hipStreamSynchronize(st));

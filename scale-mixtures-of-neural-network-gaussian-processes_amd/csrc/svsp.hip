@@ -379,8 +379,9 @@ extern "C" int smn_svsp_moments(smn_ctx* ctx, int dtype, const void* k_zz_d, con
   const double* kzz = static_cast<const double*>(k_zz_d);
   const double* qm = static_cast<const double*>(q_mu_d);
   const double* qv = static_cast<const double*>(q_var_d);
-  if (dtype == SMN_F64) return moments_t<double>(ctx, kzz, k_zt_d, ktt_diag_d, qm, qv, I, T, (int)C, eps, mean_d, var_d, info_h, nonpos_h);
-  return moments_t<float>(ctx, kzz, k_zt_d, ktt_diag_d, qm, qv, I, T, (int)C, eps, mean_d, var_d, info_h, nonpos_h);
+  return by_dtype(dtype, [&](auto e) {   // (T is the number of test points here)
+    return moments_t<decltype(e)>(ctx, kzz, k_zt_d, ktt_diag_d, qm, qv, I, T, (int)C, eps, mean_d, var_d, info_h, nonpos_h);
+  });
 }
 
 extern "C" int smn_mc_softmax(smn_ctx* ctx, int dtype, const void* mean_d, const void* sigma_d, const int* labels_h, int64_t T,
@@ -398,8 +399,9 @@ extern "C" int smn_mc_softmax(smn_ctx* ctx, int dtype, const void* mean_d, const
   double* ll = static_cast<double*>(ll_d);
   int* pred = static_cast<int*>(pred_d);
   double* score = static_cast<double*>(score_d);
-  if (dtype == SMN_F64) return mc_softmax_t<double>(ctx, mean_d, sigma_d, labels_h, T, (int)C, S, df, seed, point0, noise_d, ll, pred, score);
-  return mc_softmax_t<float>(ctx, mean_d, sigma_d, labels_h, T, (int)C, S, df, seed, point0, noise_d, ll, pred, score);
+  return by_dtype(dtype, [&](auto e) {
+    return mc_softmax_t<decltype(e)>(ctx, mean_d, sigma_d, labels_h, T, (int)C, S, df, seed, point0, noise_d, ll, pred, score);
+  });
 }
 
 extern "C" int smn_rng_variates(smn_ctx* ctx, int dtype, uint64_t seed, double df, int64_t point0, int64_t npoints, int64_t C,
@@ -413,10 +415,10 @@ extern "C" int smn_rng_variates(smn_ctx* ctx, int dtype, uint64_t seed, double d
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   const dim3 grid((unsigned)npoints, (unsigned)((C + 3) / 4));
   const double dfe = df > 0.0 ? df : 0.0;
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL(rng_variates_kernel<double>, grid, dim3(256), 0, ctx->stream, k0, k1, dfe, (uint32_t)point0, (int)C, S, static_cast<double*>(out_d));
-  else
-    hipLaunchKernelGGL(rng_variates_kernel<float>, grid, dim3(256), 0, ctx->stream, k0, k1, (float)dfe, (uint32_t)point0, (int)C, S, static_cast<float*>(out_d));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(rng_variates_kernel<T>, grid, dim3(256), 0, ctx->stream, k0, k1, (T)dfe, (uint32_t)point0, (int)C, S, static_cast<T*>(out_d));
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }

@@ -686,12 +686,11 @@ extern "C" int smn_rng_variates_ddf(smn_ctx* ctx, int dtype, uint64_t seed, doub
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   const dim3 grid((unsigned)npoints, (unsigned)((C + 3) / 4));
   const double dfe = df > 0.0 ? df : 0.0;
-  if (dtype == SMN_F64)
-    hipLaunchKernelGGL((variates_kernel<double, double>), grid, dim3(256), 0, ctx->stream, k0, k1, dfe, (uint32_t)point0, (int)C, S,
-                       C * S, S, static_cast<double*>(out_d), static_cast<double*>(dout_d));
-  else
-    hipLaunchKernelGGL((variates_kernel<float, float>), grid, dim3(256), 0, ctx->stream, k0, k1, (float)dfe, (uint32_t)point0, (int)C,
-                       S, C * S, S, static_cast<float*>(out_d), static_cast<float*>(dout_d));
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL((variates_kernel<T, T>), grid, dim3(256), 0, ctx->stream, k0, k1, (T)dfe, (uint32_t)point0, (int)C, S,
+                       C * S, S, static_cast<T*>(out_d), static_cast<T*>(dout_d));
+  });
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -709,10 +708,9 @@ extern "C" int smn_svsp_head_grad(smn_ctx* ctx, int dtype, const void* mean_d, c
   double* gmean = static_cast<double*>(gmean_d);
   double* gcov = static_cast<double*>(gcov_d);
   HeadOut ho{};
-  if (dtype == SMN_F64)
-    SMN_TRY((head_run<double>(ctx, mean, cov, labels_h, B, (int)C, S, df, scale, seed, point0, noise_d, dnoise_d, gmean, gcov, &ho)));
-  else
-    SMN_TRY((head_run<float>(ctx, mean, cov, labels_h, B, (int)C, S, df, scale, seed, point0, noise_d, dnoise_d, gmean, gcov, &ho)));
+  SMN_TRY(by_dtype(dtype, [&](auto e) {
+    return head_run<decltype(e)>(ctx, mean, cov, labels_h, B, (int)C, S, df, scale, seed, point0, noise_d, dnoise_d, gmean, gcov, &ho);
+  }));
   double s[3];
   int info = 0;
   SMN_HIP(ctx, hipMemcpyAsync(s, ho.scal, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
@@ -751,12 +749,10 @@ extern "C" int smn_svsp_elbo_grad(smn_ctx* ctx, int dtype, const void* k_d, int6
   double* gqm = static_cast<double*>(g_q_mu_d);
   double* gqv = static_cast<double*>(g_q_var_d);
   double* gbar = static_cast<double*>(gbar_d);
-  if (dtype == SMN_F64)
-    SMN_TRY((elbo_t<double>(ctx, k, ldk, I, B, (int)C, qm, qv, eps, s, num_train, labels_h, S, df, scale, seed, point0, noise_d,
-                            dnoise_d, gqm, gqv, gbar, ldg, res)));
-  else
-    SMN_TRY((elbo_t<float>(ctx, k, ldk, I, B, (int)C, qm, qv, eps, s, num_train, labels_h, S, df, scale, seed, point0, noise_d,
-                           dnoise_d, gqm, gqv, gbar, ldg, res)));
+  SMN_TRY(by_dtype(dtype, [&](auto e) {
+    return elbo_t<decltype(e)>(ctx, k, ldk, I, B, (int)C, qm, qv, eps, s, num_train, labels_h, S, df, scale, seed, point0, noise_d,
+                               dnoise_d, gqm, gqv, gbar, ldg, res);
+  }));
   if (nll_h) *nll_h = res[0];
   if (kl_n_h) *kl_n_h = res[1];
   if (g_eps_h) *g_eps_h = res[2];

@@ -968,9 +968,105 @@ def test_loss_and_test_nll_at_the_smallest_sizes_and_the_tile_edges(n, t):
         assert abs(model.test_nll(xt, yt) - rn) < 1e-6 * max(1.0, abs(rn)), (method, model.test_nll(xt, yt), rn)
 
 
+def _not_pd_through_the_value_entries(L, ctx, dtype):
+    """K - 5 I (not positive definite at the first pivot) through every entry that returns a value or a prediction: SMN_OK,
+    info >= 1, every host scalar of the failed problem NaN; the good neighbours of a batch are the serial call's bits.
+    Nothing is asserted on mean / cov of a failed call."""
+    from smnngp import nt_kernels, sharding as S
+    from _played import play_ranks
+    n, d, t, c, bad_eps = 40, 3, 5, 3, -5.0
+    rng = np.random.default_rng(3)
+    xh, xth = rng.standard_normal((n, d)).astype(dtype), rng.standard_normal((t, d)).astype(dtype)
+    yh = rng.standard_normal((n, c)).astype(dtype)
+    code = L.dtype_code(dtype)
+    net = (L.NET_MLP, L.ACT["relu"], 1, 1.0, 1e-8, 1.0)
+    x, xt, y, y1 = ctx.to_device(xh), ctx.to_device(xth), ctx.to_device(yh), ctx.to_device(np.ascontiguousarray(yh[:, 0]))
+    kfn = nt_kernels.get_mlp_kernel(1, act="relu", w_std=1.0, b_std=1e-8, last_w_std=1.0)
+    kj = np.ascontiguousarray(np.asarray(kfn(np.concatenate([xh, xth]), None, get="nngp")), dtype=dtype)   # joint [n + t]
+    kd = np.ascontiguousarray(kj[:n, :n])
+
+    def arr(vals):
+        return (C.c_double * len(vals))(*vals)
+
+    def all_nan(info, *scalars):
+        assert info >= 1, info
+        flat = [v for s in scalars for v in (list(s) if hasattr(s, "__len__") else [s.value])]
+        assert flat and all(np.isnan(v) for v in flat), flat
+
+    for df, scale in ((0.0, 1.0), (4.2, 0.7)):
+        lp, quad, logdet, info, cols = C.c_double(7.0), C.c_double(7.0), C.c_double(7.0), C.c_int(-7), arr([7.0] * c)
+        tail = (C.byref(lp), C.byref(quad), C.byref(logdet), C.byref(info))
+        tail_multi = (C.byref(lp), C.byref(quad), cols, C.byref(logdet), C.byref(info))
+        k = ctx.to_device(kd)
+        ctx.call("smn_lml", code, k.ptr, n, n, y1.ptr, bad_eps, df, scale, *tail)
+        all_nan(info.value, lp, quad, logdet)
+        k = ctx.to_device(kd)
+        ctx.call("smn_lml_multi", code, k.ptr, n, n, y.ptr, c, bad_eps, df, scale, *tail_multi)
+        all_nan(info.value, lp, quad, logdet, cols)
+        ctx.call("smn_spr_loss_multi", code, *net, x.ptr, n, d, d, y.ptr, c, bad_eps, df, scale, *tail_multi)
+        all_nan(info.value, lp, quad, logdet, cols)
+        # one rank's paired lower blocks, straight from the staging buffer
+        stage = ctx.to_device(np.full(S.paired_chunk_elems(n, 1), np.nan, dtype))
+        ctx.call("smn_kernel_mlp_shard", code, *net, x.ptr, n, d, d, 1, 0, S.block_rows(n, 1), L.GET_NNGP, stage.ptr, None)
+        ctx.call("smn_lml_from_blocks", code, stage.ptr, n, 1, S.block_rows(n, 1), y1.ptr, bad_eps, df, scale, *tail)
+        all_nan(info.value, lp, quad, logdet)
+        # one played rank of the column-first route: the scatter adds the (negative) shift
+        pieces = S.default_col_pieces(n, 1)
+        stage, _ = play_ranks(L, ctx, net, x, n, d, 1, pieces, dtype=dtype, with_ntk=False)
+        ctx.call("smn_shard_begin", code, n, bad_eps)
+        for g in range(len(pieces) - 1):
+            ctx.call("smn_shard_scatter_cols", code, stage.ptr, n, 1, len(pieces) - 1, S.cols_array(pieces), g, None, 0)
+        ctx.call("smn_lml_from_shards", code, n, y1.ptr, df, scale, *tail)
+        all_nan(info.value, lp, quad, logdet)
+
+    mean, cov, quads, logdet, info = ctx.empty((t, c), dtype), ctx.empty((t, t), dtype), arr([7.0] * c), C.c_double(7.0), C.c_int(-7)
+    k = ctx.to_device(kj)
+    ctx.call("smn_predict", code, k.ptr, n, t, n + t, y.ptr, c, 0.0, bad_eps, mean.ptr, cov.ptr, t, quads,
+             C.byref(logdet), C.byref(info))
+    all_nan(info.value, quads, logdet)
+    quads, logdet, info = arr([7.0] * c), C.c_double(7.0), C.c_int(-7)
+    ctx.call("smn_spr_predict", code, *net, x.ptr, n, d, xt.ptr, t, d, d, y.ptr, c, 0.0, bad_eps, mean.ptr, cov.ptr, t, quads,
+             C.byref(logdet), C.byref(info))
+    all_nan(info.value, quads, logdet)
+    logdet, info = C.c_double(7.0), C.c_int(-7)
+    k = ctx.to_device(kd)
+    ctx.call("smn_cholesky", code, k.ptr, n, n, n, n, bad_eps, 0.0, C.byref(info), C.byref(logdet))
+    all_nan(info.value, logdet)
+
+    # batches: the failed problem between two good ones, each with its own hyper-parameters and head
+    w, b, lw, eps = [1.0, 1.0, 1.3], [1e-8, 1e-8, 0.2], [1.0, 1.0, 0.9], [1e-3, bad_eps, 1e-3]
+    dfs, scales = [0.0, 4.2, 4.2], [1.0, 0.7, 0.7]
+    lps, qs, lds, infos = arr([7.0] * 3), arr([7.0] * 3), arr([7.0] * 3), (C.c_int * 3)(-7, -7, -7)
+    ctx.call("smn_spr_loss_batch", code, net[0], net[1], net[2], 3, arr(w), arr(b), arr(lw), x.ptr, n, d, d, y1.ptr, arr(eps),
+             arr(dfs), arr(scales), lps, qs, lds, infos)
+    all_nan(infos[1], [lps[1], qs[1], lds[1]])
+    for g in (0, 2):
+        lp, quad, logdet, info = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        ctx.call("smn_spr_loss", code, net[0], net[1], net[2], w[g], b[g], lw[g], x.ptr, n, d, d, y1.ptr, eps[g], dfs[g], scales[g],
+                 C.byref(lp), C.byref(quad), C.byref(logdet), C.byref(info))
+        assert info.value == 0 and infos[g] == 0
+        assert np.array([lp.value, quad.value, logdet.value]).tobytes() == np.array([lps[g], qs[g], lds[g]]).tobytes()
+    means, covs, vars_ = ctx.empty((3 * t, c), dtype), ctx.empty((3 * t, t), dtype), ctx.empty((3 * t,), dtype)
+    qs, lds, infos = arr([7.0] * (3 * c)), arr([7.0] * 3), (C.c_int * 3)(-7, -7, -7)
+    ctx.call("smn_spr_predict_batch", code, net[0], net[1], net[2], 3, arr(w), arr(b), arr(lw), x.ptr, n, d, xt.ptr, t, d, d, y.ptr,
+             c, arr([0.0] * 3), arr(eps), means.ptr, covs.ptr, t, vars_.ptr, qs, lds, infos)
+    all_nan(infos[1], list(qs[c:2 * c]) + [lds[1]])
+    mh, ch, vh = means.numpy(), covs.numpy(), vars_.numpy()
+    for g in (0, 2):
+        quads, logdet, info = arr([7.0] * c), C.c_double(), C.c_int()
+        ctx.call("smn_spr_predict", code, net[0], net[1], net[2], w[g], b[g], lw[g], x.ptr, n, d, xt.ptr, t, d, d, y.ptr, c, 0.0,
+                 eps[g], mean.ptr, cov.ptr, t, quads, C.byref(logdet), C.byref(info))
+        assert info.value == 0 and infos[g] == 0
+        assert np.array(list(quads) + [logdet.value]).tobytes() == np.array(list(qs[g * c:(g + 1) * c]) + [lds[g]]).tobytes()
+        assert mean.numpy().tobytes() == mh[g * t:(g + 1) * t].tobytes()
+        assert cov.numpy().tobytes() == ch[g * t:(g + 1) * t].tobytes()
+        assert np.diag(cov.numpy()).tobytes() == vh[g * t:(g + 1) * t].tobytes()
+
+
 def test_not_pd_gives_nan_like_the_reference(L, ctx):
     """JAX's Cholesky returns NaN on a non-PD matrix and the driver notices later (train.py:211): no exception, NaN out,
-    through the fused call (info = first bad pivot), the facade's likelihood on a device matrix, and the batched call."""
+    through the fused call (info = first bad pivot), the facade's likelihood on a device matrix, and -- in both precisions --
+    every other entry that returns a value or a prediction, the batched calls with the bad problem between two good ones."""
     from smnngp import nt_kernels
     from smnngp.spax.kernels import NNGPKernel
     from smnngp.spax.likelihoods import GaussianLikelihood, StudentTLikelihood
@@ -987,6 +1083,8 @@ def test_not_pd_gives_nan_like_the_reference(L, ctx):
     ctx.call("smn_spr_loss", L.F32, L.NET_MLP, L.ACT["relu"], 1, 1.0, 1e-8, 1.0, xd.ptr, 40, 3, 3, yd.ptr, -5.0, 0.0, 1.0,
              C.byref(lp), None, None, C.byref(info))         # K - 5 I: not positive definite
     assert info.value >= 1 and np.isnan(lp.value)
+    for dtype in (np.float32, np.float64):
+        _not_pd_through_the_value_entries(L, ctx, dtype)
 
 
 # ----------------------------------------------------------------------------- "next" rows
@@ -1310,7 +1408,7 @@ def test_analytic_gradient_at_sizes_that_skip_identity_tiles(dtype, n):
 
 @pytest.mark.parametrize("n", [4096, 8192])
 def test_gradient_factorisation_launches_only_the_live_tiles_of_the_identity_block(n):
-    """Both routes of the gradient's factorisation (heads.hip factor_with_identity): below 8192 rows the joint matrix
+    """Both routes of the gradient's factorisation (heads.hip factor_built_with_identity): below 8192 rows the joint matrix
     [[K~, .], [I, 0], [y^T, 0, 0]], whose Schur complement is -K~^-1; from 8192 on the rectangle [[K~], [I], [y^T]] factored
     without its Schur block, then -L^-T L^-1 as one launch.  Either way ~N^3 update flops (chol N^3/3 + L^-T N^3/3 +
     L^-T L^-1 N^3/3) when the structural zeros of the identity rows are left out of every launch (a dense 2N x 2N
