@@ -287,6 +287,15 @@ int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
  *   smn_fit_apply               either kind of state, the caller supplies k_td_d [t, n] and ktt_diag_d [t] and / or k_tt_d
  *                               [t, t] (lower): var_d needs one of the two (the diagonal is taken from ktt_diag_d when both are
  *                               given), cov_d needs k_tt_d.
+ *   smn_fit_predict_grad        fused states only (matrix form: SMN_EINVAL as smn_fit_predict): the derivatives of what
+ *                               smn_fit_predict returns with respect to the test inputs, dmean_d [t, c, d] = d mean[r, k] / d x_r
+ *                               and / or dvar_d [t, d] = d var[r] / d x_r (one may be NULL), in chunks of `capacity` rows.  The
+ *                               kernel-side derivative is smn_kernel_mlp_input_grad's; the first call adds L' = J L^T J, alpha =
+ *                               K~^-1 Y and X^T to the state (smn_fit_info's bytes grow); nothing smn_fit_predict or smn_fit_apply
+ *                               reads changes.  A call also takes context workspace (freed with the context, not counted by
+ *                               smn_fit_info): F_1, F_2, their seeded product and U, 4 x round_up(min(capacity, t), 128) x n_pad
+ *                               elements -- 0.54 GB in fp32 at n = 16384, capacity 2048.  Sums in fp64 and in a fixed order: the same arguments give the same bits, and a
+ *                               row's values do not depend on the rows it shares a call with.  info != 0 -> NaN outputs, SMN_OK.
  *   smn_fit_info                sizes and the bytes the state owns (NULL outputs are skipped).
  *   smn_fit_destroy             synchronises the context's stream and frees the state.
  * Not positive definite: *info_h = the failing pivot, the state is still returned (SMN_OK) and every prediction from it is NaN.
@@ -303,6 +312,7 @@ int smn_fit_create_from_kernel(smn_ctx* ctx, int dtype, const void* k_d, int64_t
 int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* mean_d, void* var_d, void* cov_d, int64_t ldcov);
 int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, const void* ktt_diag_d, const void* k_tt_d, int64_t ldtt,
                   void* mean_d, void* var_d, void* cov_d, int64_t ldcov);
+int smn_fit_predict_grad(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* dmean_d, void* dvar_d);
 int smn_fit_info(smn_fit* fit, int64_t* n, int64_t* c, int64_t* capacity, size_t* bytes);
 int smn_fit_destroy(smn_fit* fit);
 
@@ -669,6 +679,20 @@ int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
                               double w_std, double b_std, double last_w_std,
                               const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                               const void* gbar_d, int64_t ldg, int64_t n_grad, void* gx_d);
+
+/* ---- the MLP / dense-ResNet kernels differentiated in their first argument (experiments/nt_kernels.py:21-31, 83-103 under
+ *      jax.grad with respect to x1: sensitivities, acquisition ascent, saliency) ----
+ * smn_kernel_mlp_input_grad: gx_d [n1, ldgx >= d] = sum_j gbar[r, j] dK(x1_r, x2_j)/dx1_r for K = smn_kernel_mlp(x1, x2); net
+ *   may carry SMN_NET_NTK (then K is Theta).  With u = x1_r . x2_j / d and v = |x1_r|^2 / d, dK_rj/dx1_r = (F_1 x2_j + 2 F_2
+ *   x1_r) / d: F_1 = dK/du and F_2 = dK/dv are carried through the layer stack in forward mode in the epilogue of the fused MFMA
+ *   Gram tile (per-element arithmetic in `dtype`), (gbar o F_1) X2 runs on the tile engine, the row sums of gbar o F_2 in fp64
+ *   in a fixed order (no floating-point atomics: two calls give the same bits).  x2_d must be given: the form in which both
+ *   arguments move (x2 == x1) is not implemented -> SMN_EINVAL by name.  gbar_d [n1, ldg >= n2] of `dtype`.  A row of x1 equal
+ *   to a row of x2 (ReLU: D_A = D_1 = 0 there) and an all-zero row with b_std == 0 (no variance-side term) give finite values.
+ *   fp32 / fp64, relu / erf, any num_hiddens up to 16 activation layers (SMN_ENOTSUP above).  No synchronisation. */
+int smn_kernel_mlp_input_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                              const void* x1_d, int64_t n1, int64_t ldx1, const void* x2_d, int64_t n2, int64_t ldx2, int64_t d,
+                              const void* gbar_d, int64_t ldg, void* gx_d, int64_t ldgx);
 
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other

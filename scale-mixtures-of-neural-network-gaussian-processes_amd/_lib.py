@@ -141,6 +141,8 @@ PROTOTYPES = {
     "smn_fit_create_from_kernel": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _d, _d, _i64, _pvp, _pd, _pd, _pi],
     "smn_fit_predict": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64],
     "smn_fit_apply": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64],
+    "smn_fit_predict_grad": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "smn_kernel_mlp_input_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64],
     "smn_fit_info": [_vp, _pi64, _pi64, _pi64, C.POINTER(C.c_size_t)],
     "smn_fit_destroy": [_vp],
 }

@@ -16,7 +16,15 @@
 // The matrix is therefore [n_pad + cap_pad + 128]^2, at most one tile row more than [n_pad + round_up(capacity + c, 128)]^2.
 // The state owns A and (fused form) its padded copy of x with the row norms q; the context's workspace slots are used only
 // inside a call (padded test chunk: slot 0, layer tables: slot 1, factored diagonal blocks: slot 3), so a state survives any
-// other call on its context.  Nothing in it changes after creation.
+// other call on its context.  Nothing an entry reads changes after creation; the first smn_fit_predict_grad call adds what the
+// gradients alone read (below) beside it.
+//
+// Predictive gradients (smn_fit_predict_grad; the kernel-side derivative is input_grad.hip).  With alpha = K~^-1 Y = L^-T beta and
+// U = K_td K~^-1 = V^T L^-1:
+//     dmean[r, k, :] = (F_1 diag(alpha_k) X + 2 (F_2 alpha)[r, k] x_r) / d          (F_1, F_2 formed ONCE per chunk for all c outputs)
+//     dvar[r, :]     = 2 x_r / d * dk_rr/dq0 - 2 gx(seed = U)[r, :]                 (k_rr the closed-form diagonal, K or Theta)
+// Both backward substitutions run as forward sweeps on L' = J L^T J (J reverses the order; smn_trsm's trans = 1 form): the
+// state keeps L' with one chunk of appended rows, alpha^T [c, n_pad] and X^T from the first gradient call on.
 //
 // Why trsm on L and not the explicit -K~^-1 the gradient pipeline leaves behind: k^T K~^-1 k through an explicit inverse loses
 // cond(K~) u in fp32, while k_tt - |L^-1 k|^2 is a difference of two non-negative numbers each good to n u of k_tt.
@@ -40,6 +48,7 @@
 #include <new>
 
 #include "internal.hpp"
+#include "layer_prog.hpp"
 
 struct smn_fit {
   smn_ctx* ctx = nullptr;
@@ -49,12 +58,17 @@ struct smn_fit {
   int64_t n = 0, n_pad = 0, c = 0, capacity = 0, cap_pad = 0, n_total = 0, lda = 0, d = 0, kp = 0;
   void* a = nullptr;    // [n_total, lda]
   void* xs = nullptr;   // fused form: q [n_pad] doubles, then the padded x [n_pad, kp]
+  // made by the first smn_fit_predict_grad call: L' = J L^T J with cap_pad appended rows [n_pad + cap_pad, n_pad], alpha^T
+  // [c, n_pad] and X^T [round_up(d, 128), n_pad]
+  void* lt = nullptr; void* alpha = nullptr; void* xt = nullptr;
+  bool grad_ready = false;
   size_t bytes = 0;
   int info = 0;
   size_t es() const { return dtype_size(dtype); }
   char* at(int64_t r, int64_t col) const { return static_cast<char*>(a) + es() * (size_t)(r * lda + col); }
   double* q() const { return static_cast<double*>(xs); }
   char* xp() const { return reinterpret_cast<char*>(q() + n_pad); }
+  char* lt_at(int64_t r) const { return static_cast<char*>(lt) + es() * (size_t)(r * n_pad); }
   int64_t beta_row() const { return n_pad + cap_pad; }
 };
 
@@ -170,6 +184,9 @@ void fit_free(smn_fit* f) {
   if (!f) return;
   if (f->a) (void)hipFree(f->a);
   if (f->xs) (void)hipFree(f->xs);
+  if (f->lt) (void)hipFree(f->lt);
+  if (f->alpha) (void)hipFree(f->alpha);
+  if (f->xt) (void)hipFree(f->xt);
   delete f;
 }
 
@@ -251,6 +268,49 @@ int finish_chunk(smn_fit* f, int64_t r, const void* ktt, int64_t ktt_stride, voi
     SMN_TRY(schur_rows_padded(ctx, f->dtype, f->a, f->n_pad + rp, f->n_pad, f->lda));
     SMN_TRY(extract_posterior(ctx, f->dtype, f->a, f->lda, f->n_pad, r, 0, nullptr, cov, ldcov, nullptr, false));
   }
+  return SMN_OK;
+}
+
+// The build of one padded chunk of test rows (xp, q: pad_rows) against whatever second operand the caller fills in.
+BuildCall chunk_build_call(const smn_fit* f, const void* xp, const double* q, int64_t rp) {
+  BuildCall b{};
+  b.spec = BuildSpec{f->dtype, f->net, f->act, f->num_hiddens, f->w_std, f->b_std, f->last_w_std};
+  b.kp = (int)f->kp; b.d = f->d;
+  b.get_mask = f->ntk ? SMN_GET_NTK : SMN_GET_NNGP;
+  b.store_mode = STORE_BOUNDS;
+  b.ldo = f->lda;
+  b.x1p = xp; b.ld1 = f->kp; b.rows1 = rp; b.q1 = q;
+  return b;
+}
+
+// the cross kernel K(x_chunk, X) straight into the appended rows
+int build_cross(smn_fit* f, BuildCall b, int64_t r, BuildOut* built) {
+  b.x2p = f->xp(); b.ld2 = f->kp; b.rows2 = f->n_pad; b.q2 = f->q();
+  b.symmetric = 0; b.exact_diag = 0;
+  b.out_rows = r; b.out_cols = f->n;
+  void* dst = f->at(f->n_pad, 0);
+  b.out_k = f->ntk ? nullptr : dst; b.out_t = f->ntk ? dst : nullptr;
+  return run_build(f->ctx, b, built);
+}
+
+// What the gradients read beside the factor, made once: L' = J L^T J (rows below it cleared), alpha^T = (L^-T beta)^T by the
+// forward sweep on L' of the reversed beta rows, and X^T.
+int ensure_grad_state(smn_fit* f) {
+  if (f->grad_ready) return SMN_OK;
+  smn_ctx* ctx = f->ctx;
+  const size_t es = f->es();
+  const size_t lt_bytes = es * (size_t)(f->n_pad + f->cap_pad) * (size_t)f->n_pad, al_bytes = es * (size_t)f->c * (size_t)f->n_pad,
+               xt_bytes = es * (size_t)round_up(f->d, kTile) * (size_t)f->n_pad;
+  if (!f->lt) { SMN_HIP(ctx, hipMalloc(&f->lt, lt_bytes)); f->bytes += lt_bytes; }
+  if (!f->alpha) { SMN_HIP(ctx, hipMalloc(&f->alpha, al_bytes)); f->bytes += al_bytes; }
+  if (!f->xt) { SMN_HIP(ctx, hipMalloc(&f->xt, xt_bytes)); f->bytes += xt_bytes; }
+  SMN_HIP(ctx, hipMemsetAsync(f->lt, 0, lt_bytes, ctx->stream));
+  SMN_TRY(flip_transpose_lower(ctx, f->dtype, f->lt, f->n_pad, f->a, f->lda, f->n_pad));
+  SMN_TRY(flip_rows(ctx, f->dtype, f->lt_at(f->n_pad), f->n_pad, f->at(f->beta_row(), 0), f->lda, f->c, f->n_pad));
+  SMN_TRY(solve_rows_padded(ctx, f->dtype, f->lt, f->n_pad + kTile, f->n_pad, f->n_pad));
+  SMN_TRY(flip_rows(ctx, f->dtype, f->alpha, f->n_pad, f->lt_at(f->n_pad), f->n_pad, f->c, f->n_pad));
+  SMN_TRY(input_grad_transpose(ctx, f->dtype, f->xp(), f->n_pad, f->kp, f->d, f->xt));
+  f->grad_ready = true;
   return SMN_OK;
 }
 
@@ -343,7 +403,6 @@ extern "C" int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_
   SMN_CHECK_LD(ctx, "smn_fit_predict", ldxt, fit->d);
   if (fit->info != 0) return nan_outputs(fit, t, mean_d, var_d, cov_d, ldcov);
   const size_t es = fit->es();
-  const BuildSpec spec{fit->dtype, fit->net, fit->act, fit->num_hiddens, fit->w_std, fit->b_std, fit->last_w_std};
   {
     // Workspace of the largest chunk, taken before anything is launched: the padded chunk (slot 0) and the cross build's
     // per-row tables (slot 1: 2 (activation layers) + 2 rows of rows1 + rows2 elements, run_build; larger than the K_tt
@@ -361,13 +420,7 @@ extern "C" int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_
     char* xp = reinterpret_cast<char*>(q + rp);
     SMN_TRY(pad_rows(ctx, fit->dtype, static_cast<const char*>(xt_d) + es * (size_t)(start * ldxt), r, ldxt, fit->d, xp, rp, fit->kp, q));
     SMN_TRY(clear_tail_rows(fit, r));
-    BuildCall b{};
-    b.spec = spec;
-    b.kp = (int)fit->kp; b.d = fit->d;
-    b.get_mask = fit->ntk ? SMN_GET_NTK : SMN_GET_NNGP;
-    b.store_mode = STORE_BOUNDS;
-    b.ldo = fit->lda;
-    b.x1p = xp; b.ld1 = fit->kp; b.rows1 = rp; b.q1 = q;
+    const BuildCall b = chunk_build_call(fit, xp, q, rp);
     if (cov_d) {   // K_tt (lower tiles, exact diagonal) into the trailing block; the cross build after it leaves the same table
       BuildCall s = b;
       s.x2p = xp; s.ld2 = fit->kp; s.rows2 = rp; s.q2 = q;
@@ -377,18 +430,77 @@ extern "C" int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_
       s.out_k = fit->ntk ? nullptr : dst; s.out_t = fit->ntk ? dst : nullptr;
       SMN_TRY(run_build(ctx, s));
     }
-    // the cross kernel K(x_chunk, X) straight into the appended rows
-    b.x2p = fit->xp(); b.ld2 = fit->kp; b.rows2 = fit->n_pad; b.q2 = fit->q();
-    b.symmetric = 0; b.exact_diag = 0;
-    b.out_rows = r; b.out_cols = fit->n;
-    void* dst = fit->at(fit->n_pad, 0);
-    b.out_k = fit->ntk ? nullptr : dst; b.out_t = fit->ntk ? dst : nullptr;
     BuildOut built;
-    SMN_TRY(run_build(ctx, b, &built));
+    SMN_TRY(build_cross(fit, b, r, &built));
     // k_tt: the closed-form diagonal of the chunk's rows from the build's own table (what exact_diag writes)
     const void* ktt = fit->ntk ? built.diag_t : built.diag_k;
     SMN_TRY(finish_chunk(fit, r, ktt, 1, static_cast<char*>(mean_d) + es * (size_t)(start * fit->c),
                          var_d ? static_cast<char*>(var_d) + es * (size_t)start : nullptr, cov_d, ldcov));
+  }
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_predict_grad(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* dmean_d, void* dvar_d) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  const char* who = "smn_fit_predict_grad";
+  if (!fit->fused) return smn_fail(ctx, SMN_EINVAL, "%s: the state was made from a kernel matrix (no kernel to differentiate)", who);
+  if (!xt_d) return smn_fail(ctx, SMN_EINVAL, "%s: xt_d is NULL", who);
+  if (!dmean_d && !dvar_d) return smn_fail(ctx, SMN_EINVAL, "%s: dmean_d and dvar_d are both NULL", who);
+  if (t <= 0) return smn_fail(ctx, SMN_EINVAL, "%s: t = %lld must be at least 1", who, (long long)t);
+  SMN_CHECK_LD(ctx, who, ldxt, fit->d);
+  const int64_t c = fit->c, d = fit->d, n_pad = fit->n_pad;
+  if (fit->info != 0) {
+    SMN_TRY(fill_nan(fit, dmean_d, t, c * d, c * d));
+    return fill_nan(fit, dvar_d, t, d, d);
+  }
+  InputGradOps o{};
+  o.spec = BuildSpec{fit->dtype, fit->net, fit->act, fit->num_hiddens, fit->w_std, fit->b_std, fit->last_w_std};
+  o.ntk = fit->ntk;
+  const int nsets = input_grad_nsets(o.spec);
+  if (nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "%s: num_hiddens too large (max %d activation layers)", who, kMaxSets);
+  const size_t es = fit->es();
+  // Workspace of the largest chunk before the first launch, as in smn_fit_predict: the padded chunk (slot 0), the cross build's
+  // tables (slot 1), and in slot 4 the gradient's own scratch with U [rp, n_pad] behind it.
+  const int64_t rp_max = round_up(std::min(fit->capacity, t), kTile);
+  const size_t ig_bytes = input_grad_ws_bytes(fit->dtype, nsets, rp_max, n_pad, false);
+  void *w0 = nullptr, *w4 = nullptr;
+  SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp_max + es * (size_t)rp_max * (size_t)fit->kp, &w0));
+  SMN_TRY(smn_workspace(ctx, 1, es * (size_t)(2 * (fit->num_hiddens + 1) + 2) * (size_t)(rp_max + n_pad), &w0));
+  SMN_TRY(smn_workspace(ctx, 4, ig_bytes + es * (size_t)rp_max * (size_t)n_pad, &w4));
+  SMN_TRY(ensure_grad_state(fit));
+  o.x2p = fit->xp(); o.q2 = fit->q(); o.n2 = fit->n; o.rows2 = n_pad; o.x2t = fit->xt;
+  o.kp = fit->kp; o.d = d;
+  const double inv_d = 1.0 / (double)d;
+  for (int64_t start = 0; start < t; start += fit->capacity) {
+    const int64_t r = std::min(fit->capacity, t - start), rp = round_up(r, kTile);
+    void* xs = nullptr;
+    SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp + es * (size_t)rp * (size_t)fit->kp, &xs));
+    double* q = static_cast<double*>(xs);
+    char* xp = reinterpret_cast<char*>(q + rp);
+    SMN_TRY(pad_rows(ctx, fit->dtype, static_cast<const char*>(xt_d) + es * (size_t)(start * ldxt), r, ldxt, d, xp, rp, fit->kp, q));
+    o.x1p = xp; o.q1 = q; o.n1 = r; o.rows1 = rp;
+    const InputGradWs w = input_grad_ws_carve(w4, fit->dtype, nsets, rp, n_pad, false);
+    void* u = static_cast<char*>(w4) + ig_bytes;
+    if (dvar_d) {   // V^T = K_td L^-T as smn_fit_predict forms it, then U = V^T L^-1 by the forward sweep on L'
+      SMN_TRY(clear_tail_rows(fit, r));
+      SMN_TRY(build_cross(fit, chunk_build_call(fit, xp, q, rp), r, nullptr));
+      SMN_TRY(solve_rows_padded(ctx, fit->dtype, fit->a, n_pad + rp, n_pad, fit->lda));
+      SMN_TRY(flip_rows(ctx, fit->dtype, fit->lt_at(n_pad), n_pad, fit->at(n_pad, 0), fit->lda, rp, n_pad));
+      SMN_TRY(solve_rows_padded(ctx, fit->dtype, fit->lt, n_pad + rp, n_pad, n_pad));
+      SMN_TRY(flip_rows(ctx, fit->dtype, u, n_pad, fit->lt_at(n_pad), n_pad, rp, n_pad));
+    }
+    SMN_TRY(input_grad_factors(ctx, o, w, nullptr, 0));
+    for (int64_t k = 0; k < c && dmean_d; ++k) {
+      SMN_TRY(input_grad_seed(ctx, o, w, static_cast<const char*>(fit->alpha) + es * (size_t)(k * n_pad), 0));
+      SMN_TRY(input_grad_contract(ctx, o, w, inv_d, 2.0 * inv_d, 0.0, static_cast<char*>(dmean_d) + es * (size_t)((start * c + k) * d),
+                                  c * d));
+    }
+    if (dvar_d) {
+      SMN_TRY(input_grad_seed(ctx, o, w, u, n_pad));
+      SMN_TRY(input_grad_contract(ctx, o, w, -2.0 * inv_d, -4.0 * inv_d, 2.0 * inv_d, static_cast<char*>(dvar_d) + es * (size_t)(start * d), d));
+    }
   }
   return SMN_OK;
 }

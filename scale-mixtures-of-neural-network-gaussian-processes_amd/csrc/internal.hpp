@@ -256,6 +256,37 @@ int allgather_piece_on(smn_ctx* ctx, hipStream_t st, int dtype, const void* mine
 int scatter_piece_on(smn_ctx* ctx, hipStream_t st, int dtype, const void* stage_d, int64_t n, const ColPieces& cp, int g,
                      void* k_d, int64_t ldk, double diag_add);
 
+// The derivative of an MLP / dense-ResNet kernel entry in its first argument (input_grad.hip).  Operands are padded copies as
+// pad_rows leaves them (rows a multiple of 128, ld = kp); spec.net is the architecture alone, `ntk` says the kernel is Theta.
+struct InputGradOps {
+  BuildSpec spec; bool ntk;
+  const void* x1p; const double* q1; int64_t n1, rows1;
+  const void* x2p; const double* q2; int64_t n2, rows2;
+  const void* x2t;   // [round_up(d, 128), rows2]: the padded x2 transposed (input_grad_transpose)
+  int64_t kp, d;
+};
+// One call's scratch, carved from a single allocation.  Plain form: f1, f2 = F_1, F_2 [rows1, rows2]; seeded form: partial.
+// w [rows1, rows2] = seed o F_1 and s [rows1] = rowsum(seed o F_2) feed the contraction; ddiag [rows1] = d K_rr / d q0_r.
+struct InputGradWs {
+  void* tab1; void* tab2; void* ddiag; double* s; void* w; void* f1; void* f2; double* partial;
+  size_t bytes;   // of the whole layout
+};
+int input_grad_nsets(const BuildSpec& spec);   // activation layers of the stack
+bool input_grad_seeded_fused(int dtype, bool ntk);   // false: no fused seeded kernel for this form (plain form + input_grad_seed)
+size_t input_grad_ws_bytes(int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded);
+InputGradWs input_grad_ws_carve(void* base, int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded);
+// tables + the hot kernel.  gbar_d == nullptr: F_1, F_2 into ws.f1 / ws.f2; else gbar o F_1 into ws.w and the row sums into ws.s
+int input_grad_factors(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* gbar_d, int64_t ldg);
+// ws.w = F_1 o seed, ws.s = rowsum(F_2 o seed); seed [rows1, rows2] with row stride lds, or one row for all (lds = 0)
+int input_grad_seed(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* seed_d, int64_t lds);
+// out[r, e] = ca (ws.w X2)[r, e] + (cs ws.s[r] + cd ws.ddiag[r]) x1[r, e]   (r < n1, e < d)
+int input_grad_contract(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, double ca, double cs, double cd, void* out_d,
+                        int64_t ldo);
+// xt_d [round_up(d, 128), rows] = the padded xp [rows, kp] transposed, zero rows behind d
+int input_grad_transpose(smn_ctx* ctx, int dtype, const void* xp, int64_t rows, int64_t kp, int64_t d, void* xt_d);
+// dst[r, cols - 1 - j] = src[r, j]
+int flip_rows(smn_ctx* ctx, int dtype, void* dst, int64_t ldd, const void* src, int64_t lds, int64_t rows, int64_t cols);
+
 // K(x_i, x_i) for i < n: the per-image pass of smn_kernel_cnn / smn_kernel_conv_resnet alone (cnn.hip / cnn_resnet.hip), the
 // same launch that fills the diagonal of their symmetric build, so the values are those bits.  diag_d [n] of `dtype`.
 int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,

@@ -103,6 +103,34 @@ class KernelFn:
             return Kernels(**{n: out[n] for n in names}) if set(names) == {"nngp", "ntk"} else tuple(out[n] for n in names)
         return tuple(out[n] for n in names)
 
+    def input_grad(self, x1, x2, gbar, get=None):
+        """gx [n1, d] = sum_j gbar[r, j] dK(x1_r, x2_j)/dx1_r as a device array (smn_kernel_mlp_input_grad): the kernel
+        differentiated in its first argument, contracted with the seed gbar [n1, n2].  `get` ("nngp" or "ntk") picks K or
+        Theta and defaults to the covariance mode.  x2 must be given: the form in which both arguments move is not there."""
+        get = self.cov if get is None else get
+        if get not in ("nngp", "ntk"):
+            raise ValueError("get must be 'nngp' or 'ntk', got %r" % (get,))
+        if x2 is None:
+            raise NotImplementedError("input_grad needs x2: the symmetric form, in which both arguments move, is not implemented")
+        ctx = self.ctx or (x1.ctx if isinstance(x1, DeviceArray) else default_context())
+        a = as_device(x1, ctx)
+        if len(a.shape) != 2:                      # [N, ...] is flattened, as __call__ does (gx comes back [n1, d])
+            a = ctx.to_device(a.numpy().reshape(a.shape[0], -1))
+        b = as_device(x2, ctx, dtype=a.dtype)
+        if len(b.shape) != 2:
+            b = ctx.to_device(b.numpy().reshape(b.shape[0], -1))
+        g = as_device(gbar, ctx, dtype=a.dtype)
+        if a.shape[1] != b.shape[1]:
+            raise ValueError("x1 and x2 feature dimensions differ: %s vs %s" % (a.shape, b.shape))
+        if tuple(g.shape) != (a.shape[0], b.shape[0]):
+            raise ValueError("gbar must be [n1, n2] = %s, got %s" % ((a.shape[0], b.shape[0]), g.shape))
+        n1, d = a.shape
+        out = ctx.empty((n1, d), a.dtype)
+        net = self.net | _lib.NET_NTK if get == "ntk" else self.net
+        ctx.call("smn_kernel_mlp_input_grad", a.dcode, net, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std,
+                 a.ptr, n1, d, b.ptr, b.shape[0], d, d, g.ptr, b.shape[0], out.ptr, d)
+        return out
+
 
 def get_mlp_kernel(num_hiddens, num_class=1, act="relu", w_std=1., b_std=0., last_w_std=1.):
     """experiments/nt_kernels.py:21-31.  `num_class` and the hidden width (512) do not enter the kernel."""

@@ -202,6 +202,36 @@ class FittedPosterior:
             return mean
         return mean, (var if cov == "diag" else full)
 
+    def predict_grad(self, x, mean=True, var=True):
+        """(dmean [T,C,d], dvar [T,d]): the derivatives of `predict(x, cov="diag")` with respect to the test inputs, as device
+        arrays (None for the one not asked for); any T.  Units are those of `predict`: normalised targets, per unit of the
+        input features as they are handed in, so in target units d mean is y_std * dmean and d var is y_std^2 * dvar.  Under
+        the Student-t likelihood the predictive scale^2 is shape * var with predictive_params()'s shape, so its gradient is
+        shape * dvar.  Fused posteriors only (MLP / dense-ResNet kernel functions); the first call adds the transposed factor,
+        alpha and X^T to the device state (`nbytes` grows)."""
+        if not self.fused:
+            raise NotImplementedError("predict_grad needs an MLP / dense-ResNet kernel function: the conv kernels and foreign "
+                                      "callables (matrix-form posteriors) have no input derivative here")
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        if not (mean or var):
+            raise ValueError("predict_grad: ask for mean, var or both")
+        ctx, c = self.ctx, self.num_outputs
+        xt = _as2d(as_device(x, ctx, dtype=self.dtype))
+        t, d = int(xt.shape[0]), self.num_features
+        if t < 1:
+            raise ValueError("predict_grad needs at least one test point")
+        if xt.shape[1] != d:
+            raise ValueError("x has %d features, the training data %d" % (xt.shape[1], d))
+        dmean = ctx.empty((t, c, d), self.dtype) if mean else None
+        dvar = ctx.empty((t, d), self.dtype) if var else None
+        ctx.call_on("smn_fit_predict_grad", self._handle, xt.ptr, t, d, None if dmean is None else dmean.ptr,
+                    None if dvar is None else dvar.ptr)
+        nbytes = C.c_size_t()
+        ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
+        self.nbytes = int(nbytes.value)
+        return dmean, dvar
+
     def _marginals(self, x):
         mean, var = self.predict(x, cov="diag")
         return (np.asarray(mean.raw_numpy(), dtype=np.float64) * self.y_std + self.y_mean,
