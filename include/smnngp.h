@@ -316,6 +316,41 @@ int smn_fit_predict_grad(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt
 int smn_fit_info(smn_fit* fit, int64_t* n, int64_t* c, int64_t* capacity, size_t* bytes);
 int smn_fit_destroy(smn_fit* fit);
 
+/* ---- appending training points to a fitted state: O(n^2 k + n k^2 + k^3) instead of a refit ----
+ * THE FROZEN RIDGE.  A state is made with K~ = K_dd + lambda I, lambda = ridge_abs + ridge_rel tr(K_dd) / n, and lambda is
+ * fixed at creation (smn_fit_stats reads it).  Every appended point gets that lambda as an ABSOLUTE ridge: after any sequence of
+ * appends the state is the posterior of all N = n0 + sum k points under K(X, X) + lambda I -- what smn_fit_create on all the
+ * points with ridge_rel = 0, ridge_abs = lambda gives, NOT the fit whose relative ridge is recomputed at the new N (the two
+ * coincide when the kernel's diagonal is constant).  For new points x+ [k, d], y+ [k, c] and the factor L (n x n):
+ *     V = K(x+, X) L^-T,  S = K(x+, x+) + lambda I - V V^T,  L22 = chol(S),  z = L22^-1 (y+ - V beta)
+ *     L <- [[L, 0], [V, L22]],  beta <- [beta; z],  logdet += 2 sum log diag L22,  quad_c += |z_c|^2
+ * The new rows take the place of the identity padding behind row n; V is solved and S formed where a cov = full prediction
+ * forms them, one splice pass streams each V_i once (into row n + i of L, and into the residual y+ - V beta with the read-out's
+ * own fp64 sums), and S is factored in place by the creation path on that window.
+ *   smn_fit_reserve             room for max_points training rows: n_pad becomes round_up(max_points, 128); the matrix, the
+ *                               padded x copy are reallocated and the factor, the beta rows and x copied (O(n^2); peak memory
+ *                               = old + new state), identity on the new rows' diagonal.  What smn_fit_predict_grad added is
+ *                               dropped and made again by its next call.  max_points within the current room: nothing happens,
+ *                               no bit of the state moves; max_points < n: SMN_EINVAL.  A reserved state predicts at once, at
+ *                               the per-call cost of the new n_pad; the read-out's sums run over n_pad columns, so their order
+ *                               and with it the last bits may differ from the unreserved state's.
+ *   smn_fit_append              fused states: x_new_d [k, ldx], y_new_d [k, c].  quad_h [c], logdet_h: the updated totals;
+ *                               any of the three outputs may be NULL.
+ *   smn_fit_append_from_kernel  matrix-form states (a fused state keeps its own x: SMN_ENOTSUP): k_nd_d [k, n] = K(x+, X)
+ *                               against the state's n rows (n != the state's: SMN_EINVAL), k_nn_d [k, k] = K(x+, x+), lower.
+ * Both: a state without room for n + k rows grows itself as smn_fit_reserve(max(n + k, n + n / 2)) would.  k > capacity goes
+ * through in chunks of `capacity` rows, in order, each seeing the earlier ones as training rows.  A chunk whose S is not
+ * positive definite leaves the state exactly as it was before that chunk -- the earlier chunks stay in --, *info_h is the
+ * 1-based index among all training rows of the failing pivot and the entry returns SMN_OK (smn_fit_info tells how many rows the
+ * state holds).  A state whose own info != 0 takes no rows (SMN_EINVAL).  One host synchronisation per chunk (info).
+ *   smn_fit_stats               max_points (the room, n_pad), lambda, quad [c] and logdet as they stand (NULLs are skipped). */
+int smn_fit_reserve(smn_fit* fit, int64_t max_points);
+int smn_fit_append(smn_fit* fit, const void* x_new_d, int64_t k, int64_t ldx, const void* y_new_d,
+                   double* quad_h, double* logdet_h, int* info_h);
+int smn_fit_append_from_kernel(smn_fit* fit, const void* k_nd_d, int64_t k, int64_t n, int64_t ldk, const void* k_nn_d, int64_t ldnn,
+                               const void* y_new_d, double* quad_h, double* logdet_h, int* info_h);
+int smn_fit_stats(smn_fit* fit, int64_t* max_points, double* ridge, double* quad_h, double* logdet_h);
+
 /* ---- batched small problems: G evaluations on ONE data set in one sequence of launches (grid.y = G) ----
  * The reference's real workloads are small and many: experiments/regression/find.py:134-199 factors the kernel of one data
  * set 2 x 99 times under a grid of (w_std, b_std, eps), train.py:178-212 takes thousands of steps at N = 245, where one

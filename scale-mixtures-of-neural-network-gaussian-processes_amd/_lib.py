@@ -145,6 +145,10 @@ PROTOTYPES = {
     "smn_kernel_mlp_input_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64],
     "smn_fit_info": [_vp, _pi64, _pi64, _pi64, C.POINTER(C.c_size_t)],
     "smn_fit_destroy": [_vp],
+    "smn_fit_reserve": [_vp, _i64],
+    "smn_fit_append": [_vp, _vp, _i64, _i64, _vp, _pd, _pd, _pi],
+    "smn_fit_append_from_kernel": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _pd, _pd, _pi],
+    "smn_fit_stats": [_vp, _pi64, _pd, _pd, _pd],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing

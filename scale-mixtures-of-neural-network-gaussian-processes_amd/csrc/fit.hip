@@ -16,8 +16,20 @@
 // The matrix is therefore [n_pad + cap_pad + 128]^2, at most one tile row more than [n_pad + round_up(capacity + c, 128)]^2.
 // The state owns A and (fused form) its padded copy of x with the row norms q; the context's workspace slots are used only
 // inside a call (padded test chunk: slot 0, layer tables: slot 1, factored diagonal blocks: slot 3), so a state survives any
-// other call on its context.  Nothing an entry reads changes after creation; the first smn_fit_predict_grad call adds what the
+// other call on its context.  No prediction entry changes what another reads; the first smn_fit_predict_grad call adds what the
 // gradients alone read (below) beside it.
+//
+// Appending training points (smn_fit_append, smn_fit_append_from_kernel, smn_fit_reserve; include/smnngp.h has the algebra and
+// the frozen-ridge rule).  The k new rows take the place of the identity padding behind row n -- a state has room for n_pad
+// rows and grows by reallocation when that is not enough.  A chunk of r <= capacity rows is a cov = full prediction of those
+// rows (cross build, K(x+, x+) into the trailing block, solve_rows_padded, schur_rows_padded), then one splice pass over the
+// solved rows (V_i into row n + i of L, the residuals y+ - V beta transposed into the tile row behind the window: the test rows'
+// next tile row, or the beta rows' columns behind n_pad when r fills the capacity), then cholesky_padded on the trailing window
+// [n_pad, n_pad + round_up(r, 128)) with those residual rows as its appended rows -- which leaves L22 in the window, z^T in the
+// residual rows, |z_c|^2 on the Schur diagonal and log det S in the scalars, as at creation.  Only when S was positive definite
+// are L22 and z copied next to L and beta and n moved; otherwise rows [n, n + r) of L are made identity padding again (they
+// held zeros and a one: the state is bit for bit what it was).  Either way the window, its residual rows and the beta rows'
+// tail are cleared.
 //
 // Predictive gradients (smn_fit_predict_grad; the kernel-side derivative is input_grad.hip).  With alpha = K~^-1 Y = L^-T beta and
 // U = K_td K~^-1 = V^T L^-1:
@@ -64,6 +76,9 @@ struct smn_fit {
   bool grad_ready = false;
   size_t bytes = 0;
   int info = 0;
+  // what smn_fit_append carries forward: the absolute ridge lambda the factor was made with (frozen at creation) and the
+  // running totals y_k^T K~^-1 y_k, log det K~
+  double ridge = 0.0, quad[48] = {}, logdet = 0.0;
   size_t es() const { return dtype_size(dtype); }
   char* at(int64_t r, int64_t col) const { return static_cast<char*>(a) + es() * (size_t)(r * lda + col); }
   double* q() const { return static_cast<double*>(xs); }
@@ -241,6 +256,14 @@ int fit_factor(smn_fit* f, const void* y_d, bool prepped, double ridge_rel, doub
   SMN_TRY(fetch_mail(ctx, (int)f->c, &h));
   f->info = h.info;
   publish_head(h, f->c, true, f->n, 0.0, 1.0, nullptr, nullptr, quad_h, logdet_h, info_h);   // (the per-column forms only)
+  for (int64_t k = 0; k < f->c; ++k) f->quad[k] = h.quad[k];
+  f->logdet = h.logdet;
+  f->ridge = ridge_abs;
+  if (ridge_rel != 0.0) {   // the shift the device applied, from the trace it read (diag_shift_kernel's expression)
+    double trace = 0.0;
+    SMN_HIP(ctx, hipMemcpy(&trace, ctx->d_scal + 1, sizeof(double), hipMemcpyDeviceToHost));
+    f->ridge = ridge_abs + ridge_rel * trace / (double)f->n;
+  }
   // (columns [0, n_pad) only: what lies behind them is the creation-time Schur block -beta beta^T, which stays out of the beta rows)
   const size_t pitch = f->es() * (size_t)f->lda;
   SMN_HIP(ctx, hipMemcpy2DAsync(f->at(f->beta_row(), 0), pitch, f->at(f->n_pad, 0), pitch, f->es() * (size_t)f->n_pad, (size_t)kTile,
@@ -331,6 +354,206 @@ int nan_outputs(smn_fit* f, int64_t t, void* mean_d, void* var_d, void* cov_d, i
   SMN_TRY(fill_nan(f, mean_d, t, f->c, f->c));
   SMN_TRY(fill_nan(f, var_d, 1, t, t));
   return fill_nan(f, cov_d, t, t, ldcov);
+}
+
+// ---- appending training points (smn_fit_append / smn_fit_append_from_kernel) ----
+// The splice pass of an append, one workgroup (four waves) per solved new row i -- the read-out's scheme: 16-byte loads of
+// V_i = row i of the test block, fp64 sums per lane in column order, the xor tree, the four waves in wave order.  The pass that
+// forms the first group of columns also stores the row, 16 bytes at a time, into row n + i of the factor (columns [0, n); the
+// last piece may reach into [n, n + VN), where V is zero and the block L_22 is written afterwards).  res[k, i] = y[i, k] - V_i .
+// beta_k: the sum is the read-out's mean of row i, bit for bit, before its rounding to T; the difference is rounded once.
+template <typename T, int CB>
+__global__ void __launch_bounds__(256) fit_splice_kernel(const T* __restrict__ v, int64_t lda, int64_t n_pad, int64_t n,
+                                                         const T* __restrict__ beta, int c, const T* __restrict__ y,
+                                                         T* __restrict__ lrow, T* __restrict__ res) {
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  __shared__ double red[4][CB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = blockIdx.x;
+  const T* vr = v + row * lda;
+  T* lr = lrow + row * lda;
+  for (int c0 = 0; c0 < c; c0 += CB) {
+    double s[CB];
+#pragma unroll
+    for (int e = 0; e < CB; ++e) s[e] = 0.0;
+#pragma unroll 2
+    for (int64_t k = (int64_t)threadIdx.x * VN; k < n_pad; k += 256 * VN) {
+      const V xv = *reinterpret_cast<const V*>(vr + k);
+      const T* xe = reinterpret_cast<const T*>(&xv);
+      if (c0 == 0 && k < n) *reinterpret_cast<V*>(lr + k) = xv;
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        const int ce = c0 + e < c ? c0 + e : c - 1;
+        const V bv = *reinterpret_cast<const V*>(beta + (int64_t)ce * lda + k);
+        const T* be = reinterpret_cast<const T*>(&bv);
+#pragma unroll
+        for (int u = 0; u < VN; ++u) s[e] += (double)xe[u] * (double)be[u];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < CB; ++e) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[e] += __shfl_xor(s[e], o);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int e = 0; e < CB; ++e) red[wave][e] = s[e];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int e = 0; e < CB && c0 + e < c; ++e)
+        res[(int64_t)(c0 + e) * lda + row] = (T)((double)y[row * c + c0 + e] - (((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]));
+    }
+    __syncthreads();   // (the next group of columns rewrites red)
+  }
+}
+
+// the splice pass over the r solved rows of the test block; y_chunk [r, c] their targets, rp = round_up(r, 128)
+template <typename T>
+int splice_t(smn_fit* f, int64_t r, int64_t rp, const void* y_chunk) {
+  smn_ctx* ctx = f->ctx;
+  const T* v = reinterpret_cast<const T*>(f->at(f->n_pad, 0));
+  const T* beta = reinterpret_cast<const T*>(f->at(f->beta_row(), 0));
+  T* lrow = reinterpret_cast<T*>(f->at(f->n, 0));
+  T* res = reinterpret_cast<T*>(f->at(f->n_pad + rp, f->n_pad));
+  const dim3 g((unsigned)r), b(256);
+  ProfScope ps(ctx, PROF_MISC, ctx->stream);
+#define SMN_FIT_SPLICE(CB)                                                                                                   \
+  hipLaunchKernelGGL((fit_splice_kernel<T, CB>), g, b, 0, ctx->stream, v, f->lda, f->n_pad, f->n, beta, (int)f->c,            \
+                     static_cast<const T*>(y_chunk), lrow, res)
+  if (f->c == 1) SMN_FIT_SPLICE(1);
+  else if (f->c <= 4) SMN_FIT_SPLICE(4);
+  else SMN_FIT_SPLICE(8);
+#undef SMN_FIT_SPLICE
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
+// Room for new_pad (a multiple of 128, > n_pad) training rows: a new matrix and padded x copy, the factor's lower triangle,
+// the beta rows and x copied over, identity on the new rows' diagonal, zeros elsewhere.  The old state is released only once
+// the new one is complete; what the gradients read is dropped (ensure_grad_state makes it again at the new size).
+int fit_grow(smn_fit* f, const char* who, int64_t new_pad) {
+  smn_ctx* ctx = f->ctx;
+  const size_t es = f->es();
+  const int64_t nt = new_pad + f->cap_pad + kTile;
+  const size_t abytes = es * (size_t)nt * (size_t)nt;
+  const size_t xbytes_new = f->fused ? sizeof(double) * (size_t)new_pad + es * (size_t)new_pad * (size_t)f->kp : 0;
+  const size_t xbytes_old = f->fused ? sizeof(double) * (size_t)f->n_pad + es * (size_t)f->n_pad * (size_t)f->kp : 0;
+  void *na = nullptr, *nx = nullptr;
+  if (hipMalloc(&na, abytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return smn_fail(ctx, SMN_ENOMEM, "%s: no device memory for %lld training rows (%zu bytes beside the state's %zu)", who,
+                    (long long)new_pad, abytes, f->bytes);
+  }
+  if (f->fused && hipMalloc(&nx, xbytes_new) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(na);
+    return smn_fail(ctx, SMN_ENOMEM, "%s: no device memory for %lld training rows", who, (long long)new_pad);
+  }
+  smn_fit g = *f;   // the new layout, for the addressing helpers
+  g.a = na; g.xs = nx; g.n_pad = new_pad; g.n_total = nt; g.lda = nt;
+  auto fill = [&]() -> int {
+    SMN_HIP(ctx, hipMemsetAsync(na, 0, abytes, ctx->stream));
+    SMN_TRY(copy_matrix(ctx, f->dtype, na, nt, f->a, f->lda, f->n_pad, f->n_pad, 1));
+    SMN_TRY(fill_identity_pad(ctx, f->dtype, na, nt, new_pad, f->n_pad));
+    SMN_TRY(copy_matrix(ctx, f->dtype, g.at(g.beta_row(), 0), nt, f->at(f->beta_row(), 0), f->lda, f->c, f->n_pad, 0));
+    if (f->fused) {
+      SMN_HIP(ctx, hipMemsetAsync(nx, 0, xbytes_new, ctx->stream));
+      SMN_HIP(ctx, hipMemcpyAsync(g.q(), f->q(), sizeof(double) * (size_t)f->n_pad, hipMemcpyDeviceToDevice, ctx->stream));
+      SMN_HIP(ctx, hipMemcpyAsync(g.xp(), f->xp(), es * (size_t)f->n_pad * (size_t)f->kp, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SMN_OK;
+  };
+  const int rc = fill();
+  if (rc != SMN_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(na);
+    if (nx) (void)hipFree(nx);
+    return rc;
+  }
+  (void)hipFree(f->a);
+  if (f->xs) (void)hipFree(f->xs);
+  size_t gone = es * (size_t)f->n_total * (size_t)f->lda + xbytes_old;
+  if (f->lt) { (void)hipFree(f->lt); gone += es * (size_t)(f->n_pad + f->cap_pad) * (size_t)f->n_pad; }
+  if (f->alpha) { (void)hipFree(f->alpha); gone += es * (size_t)f->c * (size_t)f->n_pad; }
+  if (f->xt) { (void)hipFree(f->xt); gone += es * (size_t)round_up(f->d, kTile) * (size_t)f->n_pad; }
+  f->lt = f->alpha = f->xt = nullptr;
+  f->grad_ready = false;
+  f->a = na; f->xs = nx; f->n_pad = new_pad; f->n_total = nt; f->lda = nt;
+  f->bytes = f->bytes - gone + abytes + xbytes_new;
+  return SMN_OK;
+}
+
+// the test rows an append chunk of rp padded rows works in (its appended right-hand-side rows included), cleared
+int clear_append_rows(smn_fit* f, int64_t rp) {
+  const int64_t rows = std::min(rp + (int64_t)kTile, f->cap_pad);
+  SMN_HIP(f->ctx, hipMemsetAsync(f->at(f->n_pad, 0), 0, f->es() * (size_t)rows * (size_t)f->lda, f->ctx->stream));
+  return SMN_OK;
+}
+
+// what an append chunk left in the beta rows behind column n_pad (its right-hand sides when rp == cap_pad, their Schur block)
+int clear_beta_tail(smn_fit* f) {
+  const size_t pitch = f->es() * (size_t)f->lda;
+  SMN_HIP(f->ctx, hipMemset2DAsync(f->at(f->beta_row(), f->n_pad), pitch, 0, f->es() * (size_t)(f->lda - f->n_pad), (size_t)kTile,
+                                   f->ctx->stream));
+  return SMN_OK;
+}
+
+// One chunk of r <= capacity new rows whose cross kernel K(x+, X) sits in the test rows (columns [0, n)) and whose K(x+, x+)
+// (lower) sits in the trailing block: V, S, the splice pass, the factorisation of the trailing window with the residual rows
+// as its appended rows, and -- only when S is positive definite -- L_22, z and the totals.  *info = 0 or the failing pivot's
+// 1-based index among all training rows; the state is then as it was before the chunk.
+int append_chunk(smn_fit* f, int64_t r, const void* y_chunk, int* info) {
+  smn_ctx* ctx = f->ctx;
+  const int64_t rp = round_up(r, kTile), n = f->n, n_pad = f->n_pad;
+  const size_t pitch = f->es() * (size_t)f->lda;
+  SMN_TRY(solve_rows_padded(ctx, f->dtype, f->a, n_pad + rp, n_pad, f->lda));
+  SMN_TRY(schur_rows_padded(ctx, f->dtype, f->a, n_pad + rp, n_pad, f->lda));
+  SMN_TRY(fill_identity_pad(ctx, f->dtype, f->at(n_pad, n_pad), f->lda, rp, r));
+  SMN_TRY(by_dtype(f->dtype, [&](auto e) { return splice_t<decltype(e)>(f, r, rp, y_chunk); }));
+  FactorCall fc{f->dtype, f->at(n_pad, n_pad), rp + kTile, rp, f->lda, r, f->ridge, 0.0, true};
+  SMN_TRY(cholesky_padded(ctx, fc));
+  SMN_TRY(extract_posterior(ctx, f->dtype, f->at(n_pad, n_pad), f->lda, rp, 0, f->c, nullptr, nullptr, 0, ctx->d_scal + 8, true));
+  HeadScalars h;
+  SMN_TRY(fetch_mail(ctx, (int)f->c, &h));
+  if (h.info != 0) {   // rows [n, n + r) of the factor back to identity padding, bit for bit
+    SMN_HIP(ctx, hipMemset2DAsync(f->at(n, 0), pitch, 0, f->es() * (size_t)n_pad, (size_t)r, ctx->stream));
+    SMN_TRY(fill_identity_pad(ctx, f->dtype, f->a, f->lda, n + r, n));
+    SMN_TRY(clear_append_rows(f, rp));
+    SMN_TRY(clear_beta_tail(f));
+    *info = (int)(n + h.info);
+    return SMN_OK;
+  }
+  SMN_TRY(copy_matrix(ctx, f->dtype, f->at(n, n), f->lda, f->at(n_pad, n_pad), f->lda, r, r, 1));
+  SMN_TRY(copy_matrix(ctx, f->dtype, f->at(f->beta_row(), n), f->lda, f->at(n_pad + rp, n_pad), f->lda, f->c, r, 0));
+  SMN_TRY(clear_append_rows(f, rp));
+  SMN_TRY(clear_beta_tail(f));
+  f->n = n + r;
+  for (int64_t k = 0; k < f->c; ++k) f->quad[k] += h.quad[k];
+  f->logdet += h.logdet;
+  f->grad_ready = false;
+  *info = 0;
+  return SMN_OK;
+}
+
+// the checks both append entries share, and the growth of a state that has no room for n + k rows: to
+// round_up(max(n + k, n + n / 2), 128) rows, so that a run of small appends copies the factor O(log) times
+int append_enter(smn_fit* f, const char* who, int64_t k, const void* y_new_d) {
+  smn_ctx* ctx = f->ctx;
+  if (k < 1) return smn_fail(ctx, SMN_EINVAL, "%s: k = %lld must be at least 1", who, (long long)k);
+  if (!y_new_d) return smn_fail(ctx, SMN_EINVAL, "%s: y_new_d is NULL", who);
+  if (f->info != 0)
+    return smn_fail(ctx, SMN_EINVAL, "%s: the state's matrix was not positive definite (info = %d): nothing to append to", who, f->info);
+  if (f->n + k > f->n_pad) SMN_TRY(fit_grow(f, who, round_up(std::max(f->n + k, f->n + f->n / 2), kTile)));
+  return SMN_OK;
+}
+
+void append_publish(const smn_fit* f, int info, double* quad_h, double* logdet_h, int* info_h) {
+  for (int64_t k = 0; k < f->c && quad_h; ++k) quad_h[k] = f->quad[k];
+  if (logdet_h) *logdet_h = f->logdet;
+  if (info_h) *info_h = info;
 }
 
 }  // namespace
@@ -531,6 +754,106 @@ extern "C" int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_
     SMN_TRY(finish_chunk(fit, r, ktt, stride, static_cast<char*>(mean_d) + es * (size_t)(start * fit->c),
                          (var_d && ktt) ? static_cast<char*>(var_d) + es * (size_t)start : nullptr, cov_d, ldcov));
   }
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_reserve(smn_fit* fit, int64_t max_points) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  if (max_points < fit->n)
+    return smn_fail(ctx, SMN_EINVAL, "smn_fit_reserve: max_points = %lld is below the state's n = %lld training rows",
+                    (long long)max_points, (long long)fit->n);
+  const int64_t new_pad = round_up(max_points, kTile);
+  if (new_pad <= fit->n_pad) return SMN_OK;
+  return fit_grow(fit, "smn_fit_reserve", new_pad);
+}
+
+extern "C" int smn_fit_append(smn_fit* fit, const void* x_new_d, int64_t k, int64_t ldx, const void* y_new_d, double* quad_h,
+                              double* logdet_h, int* info_h) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  const char* who = "smn_fit_append";
+  if (!fit->fused) return smn_fail(ctx, SMN_EINVAL, "%s: the state was made from a kernel matrix (use smn_fit_append_from_kernel)", who);
+  if (!x_new_d) return smn_fail(ctx, SMN_EINVAL, "%s: x_new_d is NULL", who);
+  SMN_CHECK_LD(ctx, who, ldx, fit->d);
+  SMN_TRY(append_enter(fit, who, k, y_new_d));
+  const size_t es = fit->es();
+  {   // workspace of the largest chunk before the first launch, as in smn_fit_predict (at the grown n_pad)
+    const int64_t rp_max = round_up(std::min(fit->capacity, k), kTile);
+    void* w = nullptr;
+    SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp_max + es * (size_t)rp_max * (size_t)fit->kp, &w));
+    SMN_TRY(smn_workspace(ctx, 1, es * (size_t)(2 * (fit->num_hiddens + 1) + 2) * (size_t)(rp_max + fit->n_pad), &w));
+  }
+  int info = 0;
+  for (int64_t start = 0; start < k && info == 0; start += fit->capacity) {
+    const int64_t r = std::min(fit->capacity, k - start), rp = round_up(r, kTile), n0 = fit->n;
+    void* xs = nullptr;
+    SMN_TRY(smn_workspace(ctx, 0, sizeof(double) * (size_t)rp + es * (size_t)rp * (size_t)fit->kp, &xs));
+    double* q = static_cast<double*>(xs);
+    char* xp = reinterpret_cast<char*>(q + rp);
+    SMN_TRY(pad_rows(ctx, fit->dtype, static_cast<const char*>(x_new_d) + es * (size_t)(start * ldx), r, ldx, fit->d, xp, rp, fit->kp, q));
+    SMN_TRY(clear_append_rows(fit, rp));
+    const BuildCall b = chunk_build_call(fit, xp, q, rp);
+    BuildCall s = b;   // K(x+, x+): lower tiles, exact diagonal, into the trailing block (smn_fit_predict's cov build)
+    s.x2p = xp; s.ld2 = fit->kp; s.rows2 = rp; s.q2 = q;
+    s.symmetric = 1; s.exact_diag = 1;
+    s.out_rows = r; s.out_cols = r;
+    void* dst = fit->at(fit->n_pad, fit->n_pad);
+    s.out_k = fit->ntk ? nullptr : dst; s.out_t = fit->ntk ? dst : nullptr;
+    SMN_TRY(run_build(ctx, s));
+    SMN_TRY(build_cross(fit, b, r, nullptr));
+    SMN_TRY(append_chunk(fit, r, static_cast<const char*>(y_new_d) + es * (size_t)(start * fit->c), &info));
+    if (info == 0) {   // the chunk's padded rows and their q join the state's copy: the bits pad_rows gives a fresh state
+      SMN_HIP(ctx, hipMemcpyAsync(fit->q() + n0, q, sizeof(double) * (size_t)r, hipMemcpyDeviceToDevice, ctx->stream));
+      SMN_HIP(ctx, hipMemcpyAsync(fit->xp() + es * (size_t)(n0 * fit->kp), xp, es * (size_t)r * (size_t)fit->kp, hipMemcpyDeviceToDevice,
+                                  ctx->stream));
+    }
+  }
+  append_publish(fit, info, quad_h, logdet_h, info_h);
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_append_from_kernel(smn_fit* fit, const void* k_nd_d, int64_t k, int64_t n, int64_t ldk, const void* k_nn_d,
+                                          int64_t ldnn, const void* y_new_d, double* quad_h, double* logdet_h, int* info_h) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  const char* who = "smn_fit_append_from_kernel";
+  if (fit->fused)
+    return smn_fail(ctx, SMN_ENOTSUP, "%s: the state was made from inputs and keeps its own copy of x (use smn_fit_append)", who);
+  if (!k_nd_d) return smn_fail(ctx, SMN_EINVAL, "%s: k_nd_d is NULL", who);
+  if (!k_nn_d) return smn_fail(ctx, SMN_EINVAL, "%s: k_nn_d is NULL", who);
+  if (k < 1) return smn_fail(ctx, SMN_EINVAL, "%s: k = %lld must be at least 1", who, (long long)k);
+  if (n != fit->n)
+    return smn_fail(ctx, SMN_EINVAL, "%s: n = %lld, the state holds %lld training rows", who, (long long)n, (long long)fit->n);
+  SMN_CHECK_LD(ctx, who, ldk, n);
+  SMN_CHECK_LD(ctx, who, ldnn, k);
+  SMN_TRY(append_enter(fit, who, k, y_new_d));
+  const size_t es = fit->es();
+  int info = 0;
+  for (int64_t start = 0; start < k && info == 0; start += fit->capacity) {
+    const int64_t r = std::min(fit->capacity, k - start), rp = round_up(r, kTile);
+    const char* nn_row = static_cast<const char*>(k_nn_d) + es * (size_t)(start * ldnn);
+    SMN_TRY(clear_append_rows(fit, rp));
+    // K(chunk, all rows so far) = [k_nd rows | the chunk's rows of k_nn left of its own block]
+    SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(fit->n_pad, 0), fit->lda, static_cast<const char*>(k_nd_d) + es * (size_t)(start * ldk),
+                        ldk, r, n, 0));
+    SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(fit->n_pad, n), fit->lda, nn_row, ldnn, r, start, 0));
+    SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(fit->n_pad, fit->n_pad), fit->lda, nn_row + es * (size_t)start, ldnn, r, r, 1));
+    SMN_TRY(append_chunk(fit, r, static_cast<const char*>(y_new_d) + es * (size_t)(start * fit->c), &info));
+  }
+  append_publish(fit, info, quad_h, logdet_h, info_h);
+  return SMN_OK;
+}
+
+extern "C" int smn_fit_stats(smn_fit* fit, int64_t* max_points, double* ridge, double* quad_h, double* logdet_h) {
+  if (!fit) return SMN_EINVAL;
+  if (max_points) *max_points = fit->n_pad;
+  if (ridge) *ridge = fit->ridge;
+  for (int64_t k = 0; k < fit->c && quad_h; ++k) quad_h[k] = fit->quad[k];
+  if (logdet_h) *logdet_h = fit->logdet;
   return SMN_OK;
 }
 

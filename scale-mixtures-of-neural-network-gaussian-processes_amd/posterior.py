@@ -10,6 +10,11 @@ MLP / dense-ResNet kernel functions (under NNGPKernel or NTKKernel) take the fus
 built straight into the state.  The conv kernels and any other callable take the matrix form: K_dd once at creation, then per
 chunk of test points kernel_fn(x_chunk, x_train), the prior variances (smn_kernel_conv_diag for the conv kernels) and, for
 cov="full", kernel_fn(x_chunk, None).
+
+The training set can grow: `post.append(x, y)` adds observations at O(N^2 k) without refitting, under the ridge the state
+froze when it was made (`post.ridge`, absolute for every later point), and `post.reserve(max_points)` makes room up front.
+The fused form hands the new inputs to smn_fit_append; the matrix form builds kernel_fn(x_chunk, x_train) and the lower
+kernel_fn(x_chunk, None) per chunk of `capacity` points for smn_fit_append_from_kernel and keeps x_train as the concatenation.
 """
 from __future__ import annotations
 
@@ -60,18 +65,25 @@ def _at(arr, elems):
 class FittedPosterior:
     """See the module docstring.  Attributes: quad [C] (y_k^T K~^-1 y_k), logdet (log det K~), info (0, or the failing pivot
     of a matrix that is not positive definite: every prediction is then NaN), num_data, num_outputs, capacity, nbytes (device
-    memory the state owns), hyper (the snapshot: w_std, b_std, last_w_std, eps, df, scale)."""
+    memory the state owns), hyper (the snapshot: w_std, b_std, last_w_std, eps, df, scale), ridge (lambda = ridge_abs +
+    ridge_rel tr(K_dd) / n as the device applied it at creation: the absolute ridge of every point appended later), max_points
+    (training points the state has room for; a multiple of 128)."""
 
-    def __init__(self, kernel_fn, x, y, *, ridge_rel=0.0, ridge_abs=0.0, capacity=2048, mode="nngp", ctx=None):
+    def __init__(self, kernel_fn, x, y, *, ridge_rel=0.0, ridge_abs=0.0, capacity=2048, mode="nngp", ctx=None, reserve=None):
         capacity = int(capacity)
         if capacity < 1:
             raise ValueError("capacity must be at least 1, got %d" % capacity)
         if mode not in ("nngp", "ntk"):
             raise ValueError("mode must be 'nngp' or 'ntk', got %r" % (mode,))
+        if reserve is not None and int(reserve) < int(x.shape[0]):
+            raise ValueError("reserve = %d is below the %d training points" % (int(reserve), int(x.shape[0])))
         self.ctx = ctx or getattr(kernel_fn, "ctx", None) or getattr(x, "ctx", None) or _lib.default_context()
         self._handle = None
         self.kernel_fn, self.mode, self.capacity = kernel_fn, mode, capacity
-        self.x_train = x
+        self._x_train, self._x_pending = x, []
+        self._y_first, self._y_parts = y, None
+        self._quad_model, self._student_quad, self._student_stale = None, None, False
+        self.label_targets = None
         self.dtype = np.dtype(x.dtype)
         self.num_data = int(x.shape[0])
         self.num_outputs = int(y.shape[1]) if len(y.shape) > 1 else 1
@@ -102,9 +114,14 @@ class FittedPosterior:
         nbytes = C.c_size_t()
         self.ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
         self.nbytes = int(nbytes.value)
+        max_points, ridge = C.c_int64(), C.c_double()
+        self.ctx.call_on("smn_fit_stats", self._handle, C.byref(max_points), C.byref(ridge), None, None)
+        self.ridge, self.max_points = float(ridge.value), int(max_points.value)
+        if reserve is not None:
+            self.reserve(reserve)
 
     @classmethod
-    def from_model(cls, model, capacity=2048):
+    def from_model(cls, model, capacity=2048, reserve=None):
         """The posterior of `model.predict` at the model's current hyper-parameters (SPR or MultiSPR)."""
         from .spax.kernels import NTKKernel
         if not hasattr(model.likelihood, "lml_params"):
@@ -114,12 +131,166 @@ class FittedPosterior:
         df, scale = model.likelihood.lml_params()
         student_quad = model._draws_quad(kernel_fn, scale) if df > 0.0 else None
         post = cls(kernel_fn, model.x_data, model.y_data, ridge_rel=model.eps.safe_value, capacity=capacity, mode=mode,
-                   ctx=model.x_data.ctx)
+                   ctx=model.x_data.ctx, reserve=reserve)
         post.multi = hasattr(model, "num_outputs")
         post.y_mean, post.y_std = float(model.y_mean), float(model.y_std)
         post.df, post.scale, post.student_quad = float(df), float(scale), student_quad
         post.hyper.update(df=float(df), scale=float(scale))
+        post._quad_model = model
+        post._y_parts = [np.asarray(model.y_host, dtype=np.float64).reshape(post.num_data, post.num_outputs)]
+        if getattr(model, "_from_labels", False):
+            post.label_targets = model.label_targets   # the model's own onehot(labels) - 1/C rule
         return post
+
+    # ---- the training inputs: what was handed in at creation, then every appended chunk; joined when someone reads them
+    @property
+    def x_train(self):
+        if self._x_pending:
+            host = lambda a: a.raw_numpy() if isinstance(a, DeviceArray) else np.asarray(a)   # noqa: E731
+            parts = [host(self._x_train)] + [host(p) for p in self._x_pending]
+            joined = np.concatenate([p.reshape((p.shape[0],) + parts[0].shape[1:]) for p in parts], axis=0)
+            self._x_train = as_device(joined, self.ctx, dtype=self.dtype) if isinstance(self._x_train, DeviceArray) else joined
+            self._x_pending = []
+        return self._x_train
+
+    @x_train.setter
+    def x_train(self, x):
+        self._x_train, self._x_pending = x, []
+
+    # ---- the Student-t head's quadratic form y^T ((b/a) K + 1e-6 I)^-1 y: another matrix than K~, so an append cannot carry
+    # it forward from L; it goes stale there and is recomputed over all the points by the model's own fp64 route when read
+    @property
+    def student_quad(self):
+        if self._student_stale:
+            m = self._quad_model
+            y = np.concatenate(self._y_parts, axis=0)
+            shadow = type(m)(m.kernel, m.likelihood, self.x_train, y if self.multi else y.reshape(-1), m.y_mean, m.y_std,
+                             eps=m.eps.safe_value)
+            self._student_quad = shadow._draws_quad(self.kernel_fn, self.scale)
+            self._student_stale = False
+        return self._student_quad
+
+    @student_quad.setter
+    def student_quad(self, value):
+        self._student_quad, self._student_stale = value, False
+
+    def _sync_stats(self):
+        """num_data, nbytes, max_points, quad, logdet from the device state."""
+        n, nbytes, max_points = C.c_int64(), C.c_size_t(), C.c_int64()
+        quad, logdet = (C.c_double * self.num_outputs)(), C.c_double()
+        self.ctx.call_on("smn_fit_info", self._handle, C.byref(n), None, None, C.byref(nbytes))
+        self.ctx.call_on("smn_fit_stats", self._handle, C.byref(max_points), None, quad, C.byref(logdet))
+        self.num_data, self.nbytes, self.max_points = int(n.value), int(nbytes.value), int(max_points.value)
+        self.quad, self.logdet = np.array(list(quad), dtype=np.float64), float(logdet.value)
+
+    # ---- growing the training set
+    def reserve(self, max_points):
+        """Room for up to `max_points` training points (smn_fit_reserve): one O(N^2) copy of the factor into a larger
+        allocation -- old and new state are both alive while it runs --, after which appends up to that size neither copy
+        nor allocate (`nbytes` stays put).  Within the current room (`max_points`, a multiple of 128) nothing happens.  The
+        state predicts as before at once; per-call cost follows the reserved size, and since the read-out's sums run over
+        the padded row the last bits of a prediction may differ from the unreserved state's."""
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        max_points = int(max_points)
+        if max_points < self.num_data:
+            raise ValueError("reserve: max_points = %d is below the %d training points" % (max_points, self.num_data))
+        self.ctx.call_on("smn_fit_reserve", self._handle, max_points)
+        self._sync_stats()
+        return self
+
+    def _check_append(self, x, y):
+        """Everything about append's arguments that needs no device; returns (k, y as a host [k, C] float64 array or None
+        when y is a device array of the right shape)."""
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        xs = tuple(int(s) for s in getattr(x, "shape", np.shape(x)))
+        if len(xs) < 1 or xs[0] < 1:
+            raise ValueError("append needs at least one new point, got x of shape %s" % (xs,))
+        k, c = xs[0], self.num_outputs
+        if self.fused:
+            feats = int(np.prod(xs[1:])) if len(xs) > 1 else 1
+            if feats != self.num_features:
+                raise ValueError("x has %d features, the training data %d" % (feats, self.num_features))
+        else:
+            tail = tuple(int(s) for s in self._x_train.shape[1:])
+            if xs[1:] != tail:
+                raise ValueError("x has rows of shape %s, the training data %s" % (xs[1:], tail))
+        if isinstance(y, DeviceArray):
+            ys = tuple(y.shape)
+            if ys != (k, c) and not (c == 1 and ys == (k,)):
+                raise ValueError("y must be [%d] or [%d, %d], got %s" % (k, k, c, ys))
+            return k, None
+        y = np.asarray(y)
+        if self.label_targets is not None and y.ndim == 1 and np.issubdtype(y.dtype, np.integer):
+            y = self.label_targets(y, c)
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim == 1 and c == 1:
+            y = y[:, None]
+        if y.shape != (k, c):
+            raise ValueError("y must be [%d] or [%d, %d] (C = %d outputs), got %s" % (k, k, c, c, y.shape))
+        return k, y
+
+    def append(self, x, y):
+        """Add k observations (x [k, ...] in the training inputs' layout, y [k] or [k, C] in the units of the training
+        targets; host or device arrays; integer labels for a posterior of MultiSPR.from_labels) without refitting:
+        O(N^2 k + N k^2 + k^3) (smn_fit_append / smn_fit_append_from_kernel).  Returns self.
+
+        THE RIDGE IS FROZEN: `ridge` = ridge_abs + ridge_rel tr(K_dd)/n0 is fixed when the state is made and every appended
+        point gets it as an absolute ridge.  After any appends the state is the posterior of all N points under
+        K(X, X) + ridge I -- what FittedPosterior(..., ridge_rel=0, ridge_abs=post.ridge) on all the points gives --, not the
+        fit whose relative ridge is recomputed at the new N; the two coincide when the kernel's diagonal is constant.
+
+        A state without room (`max_points`) grows itself to max(N + k, 1.5 N) points rounded up to 128 -- an O(N^2) copy
+        with both states alive; `reserve` first to avoid it.  k > capacity goes in chunks of `capacity` points, each seeing
+        the earlier ones as training points.  A chunk whose Schur complement is not positive definite is not taken:
+        numpy.linalg.LinAlgError names the pivot and how many points did go in, and the state stays usable at that size.
+        Updates num_data, quad, logdet, nbytes, max_points; the next predict_grad rebuilds what it keeps beside the factor.
+        Student-t likelihood: the quadratic form of predictive_params / test_nll / sample belongs to another matrix,
+        (b/a) K + 1e-6 I, and is recomputed over all N points by the model's fp64 route at the first call that reads it --
+        one fp64 O(N^3) factorisation --; predict, predict_grad and classify never read it and stay O(N^2 k).  The degrees
+        of freedom use the new N."""
+        k, y_host = self._check_append(x, y)
+        ctx, c, n_before = self.ctx, self.num_outputs, self.num_data
+        xd = as_device(x, ctx, dtype=self.dtype)
+        yd = as_device(y, ctx, dtype=self.dtype) if y_host is None else ctx.to_device(np.ascontiguousarray(y_host, dtype=self.dtype))
+        if y_host is None:
+            y_host = np.asarray(yd.raw_numpy(), dtype=np.float64).reshape(k, c)
+        quad, logdet, info = (C.c_double * c)(), C.c_double(), C.c_int()
+        if self.fused:
+            x2 = _as2d(xd)
+            ctx.call_on("smn_fit_append", self._handle, x2.ptr, k, self.num_features, yd.ptr, quad, C.byref(logdet), C.byref(info))
+            self._sync_stats()
+            went = self.num_data - n_before
+            if went:   # (a host array is copied: the caller may reuse it; a device array is kept as a view)
+                self._x_pending.append(_rows(xd, 0, went) if isinstance(x, DeviceArray) else np.array(np.asarray(x)[:went]))
+        else:
+            went = 0
+            for start, rows in chunks(k, self.capacity):
+                xc = _rows(xd, start, rows)
+                k_nd = self._kernel(xc, self.x_train)
+                k_nn = self._kernel(xc, None, fill="lower")
+                n = self.num_data
+                ctx.call_on("smn_fit_append_from_kernel", self._handle, k_nd.ptr, rows, n, n, k_nn.ptr, rows, _at(yd, start * c), quad,
+                            C.byref(logdet), C.byref(info))
+                self._sync_stats()
+                if info.value != 0:
+                    break
+                went += rows
+                self._x_pending.append(xc)
+                self.x_train   # (joined now: the next chunk's cross kernel is against all of them)
+        if went:
+            if self._y_parts is None:
+                self._y_parts = [np.asarray(self._y_first.raw_numpy(), dtype=np.float64).reshape(n_before, c)]
+            self._y_parts.append(y_host[:went])
+            self._y_first = None
+            if self.df > 0.0:
+                self._student_stale = True
+        if info.value != 0:
+            raise np.linalg.LinAlgError("append: the Schur complement of the new points is not positive definite at pivot %d "
+                                        "(1-based, among all training points); %d of the %d new points went in and the state "
+                                        "holds %d" % (info.value, went, k, self.num_data))
+        return self
 
     # ---- lifetime
     def close(self):

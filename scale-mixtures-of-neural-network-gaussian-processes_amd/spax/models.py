@@ -153,13 +153,15 @@ class _DrawsMixin:
     def _draws_quad(self, kernel_fn, scale):
         return self._student_quad_f64(kernel_fn, scale)
 
-    def posterior(self, capacity=2048):
+    def posterior(self, capacity=2048, reserve=None):
         """Fit once, predict many: a FittedPosterior (posterior.py) of this model at its current hyper-parameters -- the
         factor of K~ = K_dd + eps tr(K_dd)/N I stays on the device and predict / test_nll / sample / classify on it cost
         O(N^2 T) per call, for test sets of any size (chunks of `capacity` points; a full covariance needs T <= capacity).
-        A snapshot: later changes to the model's variables do not reach it.  The model's own methods are unaffected."""
+        A snapshot: later changes to the model's variables do not reach it.  The model's own methods are unaffected.
+        The state can grow: `post.append(x, y)` adds observations at O(N^2 k) under the ridge frozen at this moment
+        (`post.ridge`; FittedPosterior.append), and `reserve` = the number of training points to make room for up front."""
         from ..posterior import FittedPosterior
-        return FittedPosterior.from_model(self, capacity=capacity)
+        return FittedPosterior.from_model(self, capacity=capacity, reserve=reserve)
 
     def predictive_params(self):
         """(df_post, shape) of the predictive law in normalised units.  Gaussian likelihood: (None, 1.0), no device work.
@@ -426,7 +428,9 @@ class MultiSPR(_ExactGP):
     @classmethod
     def from_labels(cls, kernel, likelihood, x_data, labels, num_classes, y_mean=0., y_std=1., *, eps: float = 1e-6):
         """The classifier: targets onehot(labels) - 1/num_classes (every row sums to zero, its arg-max is the label)."""
-        return cls(kernel, likelihood, x_data, cls.label_targets(labels, num_classes), y_mean, y_std, eps=eps)
+        model = cls(kernel, likelihood, x_data, cls.label_targets(labels, num_classes), y_mean, y_std, eps=eps)
+        model._from_labels = True   # (its posteriors take labels in append, through label_targets)
+        return model
 
     @staticmethod
     def label_targets(labels, num_classes):
