@@ -351,6 +351,34 @@ int smn_fit_append_from_kernel(smn_fit* fit, const void* k_nd_d, int64_t k, int6
                                const void* y_new_d, double* quad_h, double* logdet_h, int* info_h);
 int smn_fit_stats(smn_fit* fit, int64_t* max_points, double* ridge, double* quad_h, double* logdet_h);
 
+/* ---- removing training points from a fitted state: O(n^2 k) instead of a refit (csrc/fit_remove.hip) ----
+ * No hyperbolic downdate: an orthogonal triangularisation, backward stable, which cannot fail for lack of positive definiteness.
+ * With L (n x n, lower), L L^T = K~ = K(X, X) + lambda I, beta^T = Y^T L^-T, J the k removed rows, R the kept ones in their order
+ * and H = L[R, :] ((n - k) x n): H H^T = K~_RR and Y_R = H beta.  For any orthogonal Q with H Q = [L' 0], L' lower triangular
+ * with a positive diagonal,
+ *     [ H      ]       [ L'       0     ]      L' L'^T = K(X_R, X_R) + lambda I,   beta' = L'^-1 Y_R,   rho is discarded.
+ *     [ beta^T ] Q  =  [ beta'^T  rho^T ]
+ * THE FROZEN RIDGE holds as for an append: lambda is unchanged and absolute, so after a removal the state is the posterior of the
+ * kept points under K + lambda I -- what smn_fit_create on the kept points with ridge_rel = 0, ridge_abs = lambda gives.
+ * Only the tail moves: columns left of j1 = min J and rows above it are untouched; behind it new row i ends at column i + r(i)
+ * (r(i) <= k removed rows above it), and the band is reduced in steps of b = 64 rows: the LQ factorisation of a b x (b + KMAX)
+ * block in fp64 (both dtypes; sign flips folded in so that diag L' > 0, exact zeros where the block becomes zero), then the rows
+ * below -- the beta rows among them -- times Q_s on the MFMA tile engine in the state's dtype; two launches per step, no host
+ * synchronisation inside the sweep.  KMAX = 32 rows per pass; more rows go in passes of KMAX from the highest indices down, each
+ * a complete removal.  J = exactly the last k rows (any k) touches no entry of L: the rows become identity padding, the beta
+ * columns are cleared -- the exact undo of smn_fit_append.  quad [c] = sum beta'^2 and logdet = 2 sum log diag L' are recomputed
+ * over the new state in fp64 in a fixed order (one host synchronisation, at the end); the same removal on the same state gives
+ * the same bits.  Workspace: the sweep runs in context workspace (freed with the context, not counted by smn_fit_info):
+ * (MB + 192) x (MB + 64) elements, MB = round_up(n - k - floor(j1 / 64) 64, 64) -- at most about the factor's own size, 1.07 GB
+ * in fp32 at n = 16384 when row 0 goes.  The state's n_pad, capacity and allocation stay as they are; the freed rows are
+ * identity padding again, and (fused states) the padded x copy is compacted.  What smn_fit_predict_grad keeps beside the factor
+ * is made again by its next call.
+ *   smn_fit_remove              idx_h: k distinct 0-based row indices on the HOST, any order; fused and matrix-form states.  Rows
+ *                               behind a removed one move down by one index each.  SMN_EINVAL, naming the value, with nothing
+ *                               moved and nothing launched: k < 1, k >= n (a state keeps at least one point), an index outside
+ *                               [0, n), an index given twice, a state whose own info != 0.  quad_h, logdet_h may be NULL. */
+int smn_fit_remove(smn_fit* fit, const int64_t* idx_h, int64_t k, double* quad_h, double* logdet_h);
+
 /* ---- batched small problems: G evaluations on ONE data set in one sequence of launches (grid.y = G) ----
  * The reference's real workloads are small and many: experiments/regression/find.py:134-199 factors the kernel of one data
  * set 2 x 99 times under a grid of (w_std, b_std, eps), train.py:178-212 takes thousands of steps at N = 245, where one

@@ -31,6 +31,10 @@
 // held zeros and a one: the state is bit for bit what it was).  Either way the window, its residual rows and the beta rows'
 // tail are cleared.
 //
+// Removing training points (smn_fit_remove) is fit_remove.hip; the state's layout is fit_state.hpp.  A removal restores what the
+// entries here rely on: identity padding behind row n, and zeros in columns [n, n_pad) of the beta rows and of the test rows (a
+// chunk's cross kernel is written in columns [0, n) only, while the solve and the read-out run over the whole padded row).
+//
 // Predictive gradients (smn_fit_predict_grad; the kernel-side derivative is input_grad.hip).  With alpha = K~^-1 Y = L^-T beta and
 // U = K_td K~^-1 = V^T L^-1:
 //     dmean[r, k, :] = (F_1 diag(alpha_k) X + 2 (F_2 alpha)[r, k] x_r) / d          (F_1, F_2 formed ONCE per chunk for all c outputs)
@@ -59,33 +63,9 @@
 #include <cmath>
 #include <new>
 
+#include "fit_state.hpp"
 #include "internal.hpp"
 #include "layer_prog.hpp"
-
-struct smn_fit {
-  smn_ctx* ctx = nullptr;
-  int dtype = 0, net = 0, act = 0, num_hiddens = 0;
-  bool ntk = false, fused = false;
-  double w_std = 0.0, b_std = 0.0, last_w_std = 0.0;
-  int64_t n = 0, n_pad = 0, c = 0, capacity = 0, cap_pad = 0, n_total = 0, lda = 0, d = 0, kp = 0;
-  void* a = nullptr;    // [n_total, lda]
-  void* xs = nullptr;   // fused form: q [n_pad] doubles, then the padded x [n_pad, kp]
-  // made by the first smn_fit_predict_grad call: L' = J L^T J with cap_pad appended rows [n_pad + cap_pad, n_pad], alpha^T
-  // [c, n_pad] and X^T [round_up(d, 128), n_pad]
-  void* lt = nullptr; void* alpha = nullptr; void* xt = nullptr;
-  bool grad_ready = false;
-  size_t bytes = 0;
-  int info = 0;
-  // what smn_fit_append carries forward: the absolute ridge lambda the factor was made with (frozen at creation) and the
-  // running totals y_k^T K~^-1 y_k, log det K~
-  double ridge = 0.0, quad[48] = {}, logdet = 0.0;
-  size_t es() const { return dtype_size(dtype); }
-  char* at(int64_t r, int64_t col) const { return static_cast<char*>(a) + es() * (size_t)(r * lda + col); }
-  double* q() const { return static_cast<double*>(xs); }
-  char* xp() const { return reinterpret_cast<char*>(q() + n_pad); }
-  char* lt_at(int64_t r) const { return static_cast<char*>(lt) + es() * (size_t)(r * n_pad); }
-  int64_t beta_row() const { return n_pad + cap_pad; }
-};
 
 namespace {
 

@@ -15,6 +15,10 @@ The training set can grow: `post.append(x, y)` adds observations at O(N^2 k) wit
 froze when it was made (`post.ridge`, absolute for every later point), and `post.reserve(max_points)` makes room up front.
 The fused form hands the new inputs to smn_fit_append; the matrix form builds kernel_fn(x_chunk, x_train) and the lower
 kernel_fn(x_chunk, None) per chunk of `capacity` points for smn_fit_append_from_kernel and keeps x_train as the concatenation.
+
+And it can shrink: `post.remove(indices)` takes observations out at O(N^2 k), again without refitting and under the same frozen
+ridge (smn_fit_remove: an orthogonal re-triangularisation of the kept rows of L, no kernel is evaluated) -- a sliding window
+over a stream is `remove(range(k))` + `append`, and removing the points just appended undoes the append bit for bit.
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ from . import _lib
 from ._lib import DeviceArray, as_device
 from .nt_kernels import CnnKernelFn, KernelFn
 
-__all__ = ["FittedPosterior", "chunks"]
+__all__ = ["FittedPosterior", "chunks", "normalise_indices"]
 
 
 def chunks(T, capacity):
@@ -56,6 +60,34 @@ def _as2d(arr):
                        owner=False)
     view._base = arr if arr._base is None else arr._base
     return view
+
+
+def normalise_indices(indices, n):
+    """`indices` (an int, a sequence / array of ints, or a boolean mask of length n; negative values count from the end) as a
+    sorted int64 array of distinct values in [0, n).  ValueError: empty, out of range, duplicates after normalisation, a mask
+    of another length, anything that is not integral."""
+    n = int(n)
+    arr = np.asarray(indices)
+    if arr.dtype == np.bool_:
+        if arr.shape != (n,):
+            raise ValueError("a boolean mask must have shape (%d,), the training points; got %s" % (n, arr.shape))
+        arr = np.flatnonzero(arr)
+    else:
+        arr = np.atleast_1d(arr)
+        if arr.ndim != 1 or not (arr.size == 0 or np.issubdtype(arr.dtype, np.integer)):
+            raise ValueError("indices must be an int, a 1-d sequence of ints or a boolean mask, got dtype %s, shape %s"
+                             % (arr.dtype, arr.shape))
+    if arr.size == 0:
+        raise ValueError("remove needs at least one point: the selection is empty")
+    arr = arr.astype(np.int64)
+    bad = arr[(arr < -n) | (arr >= n)]
+    if bad.size:
+        raise ValueError("index %d is out of range for %d training points" % (int(bad[0]), n))
+    arr = np.sort(np.where(arr < 0, arr + n, arr))
+    dup = arr[1:][arr[1:] == arr[:-1]]
+    if dup.size:
+        raise ValueError("index %d is given more than once" % int(dup[0]))
+    return arr
 
 
 def _at(arr, elems):
@@ -290,6 +322,51 @@ class FittedPosterior:
             raise np.linalg.LinAlgError("append: the Schur complement of the new points is not positive definite at pivot %d "
                                         "(1-based, among all training points); %d of the %d new points went in and the state "
                                         "holds %d" % (info.value, went, k, self.num_data))
+        return self
+
+    # ---- shrinking the training set
+    def remove(self, indices):
+        """Take k observations out without refitting (smn_fit_remove): O(N^2 k) -- about m^2 (64 + 32)^2 / 64 flops per pass
+        of at most 32 points for the m points behind the first removed one -- instead of O(N^3); removing exactly the last k
+        points costs O(N k) and undoes an `append` of them bit for bit.  Returns self.
+
+        `indices`: an int, a sequence or array of ints, or a boolean mask of length num_data; negative values count from the
+        end; a value given twice (after that normalisation) is a ValueError, as are an empty selection, one that takes every
+        point (a posterior keeps at least one) and a value out of range -- all before any device call.  A REMOVED POINT'S INDEX
+        SHIFTS THE LATER ONES DOWN: after remove([3]) the old point 4 is point 3, as with numpy.delete; all the indices of one
+        call refer to the numbering before it.
+
+        THE RIDGE IS FROZEN, as for `append`: `ridge` stays what it was when the state was made, so afterwards the state is
+        the posterior of the kept points under K(X_R, X_R) + ridge I -- what FittedPosterior(..., ridge_rel=0,
+        ridge_abs=post.ridge) on the kept points gives --, not the fit whose relative ridge is recomputed on them.
+
+        No kernel is evaluated (fused and matrix-form posteriors go through the same entry); the kept rows of the factor are
+        re-triangularised by orthogonal transformations, which is backward stable and cannot fail.  `max_points` and `nbytes`
+        stay as they are (the room is kept for later appends).  Updates num_data, quad, logdet, x_train; the next predict_grad
+        rebuilds what it keeps beside the factor; under a Student-t likelihood the quadratic form is recomputed over the kept
+        points at the first call that reads it, as after an append."""
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        n, c = self.num_data, self.num_outputs
+        idx = normalise_indices(indices, n)
+        if idx.size >= n:
+            raise ValueError("remove: the selection takes all %d training points; a posterior keeps at least one" % n)
+        quad, logdet = (C.c_double * c)(), C.c_double()
+        self.ctx.call_on("smn_fit_remove", self._handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), quad, C.byref(logdet))
+        keep = np.ones(n, dtype=bool)
+        keep[idx] = False
+        x = self.x_train                                       # (joined)
+        if isinstance(x, DeviceArray):
+            self._x_train = as_device(np.ascontiguousarray(x.raw_numpy()[keep]), self.ctx, dtype=self.dtype)
+        else:
+            self._x_train = np.asarray(x)[keep]
+        if self._y_parts is None:
+            self._y_parts = [np.asarray(self._y_first.raw_numpy(), dtype=np.float64).reshape(n, c)]
+        self._y_parts = [np.concatenate(self._y_parts, axis=0)[keep]]
+        self._y_first = None
+        if self.df > 0.0:
+            self._student_stale = True
+        self._sync_stats()
         return self
 
     # ---- lifetime
