@@ -900,6 +900,13 @@ __global__ void __launch_bounds__(256, BN == 64 ? 4 : (BM == 64 ? (sizeof(T) == 
       }
   // trailing updates (TAG 1) run K = 256 ... 1024: the pipelined K loop; strips (K = 128) the plain one
   t.template mainloop<TAG == 1 ? 1 : 0>(u.a + row0 * u.lda + u.k0, u.lda, u.a + col0 * u.lda + u.k0, u.lda, u.K, smem);
+  // The store addresses are computed again, from copies of the (workgroup-uniform) origin that the compiler cannot tell
+  // are the prologue's: left to itself it keeps the C read's per-row addresses (32 VGPRs in the 128x128 tile) alive across
+  // the K loop for the stores, and at the tile's register limit that is a spill to scratch in front of the loop and a
+  // reload behind it in every TAG 1 form.
+  T* sa = u.a;
+  int64_t srow = row0, scol = col0, slda = u.lda;
+  asm volatile("" : "+s"(sa), "+s"(srow), "+s"(scol), "+s"(slda));
   if (clip) {   // (its own copy of the loop: the stores of every other tile stay unconditional)
 #pragma unroll
     for (int m = 0; m < Tile::MT; ++m)
@@ -907,9 +914,9 @@ __global__ void __launch_bounds__(256, BN == 64 ? 4 : (BM == 64 ? (sizeof(T) == 
       for (int n = 0; n < Tile::NT; ++n)
 #pragma unroll
         for (int i = 0; i < M::ACC; ++i) {
-          const int64_t gr = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
-          const int64_t gc = col0 + wc * Tile::WN + n * M::TN + M::acc_col(lane);
-          if (gc <= gr) u.a[gr * u.lda + gc] = -t.acc[m][n][i];
+          const int64_t gr = srow + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
+          const int64_t gc = scol + wc * Tile::WN + n * M::TN + M::acc_col(lane);
+          if (gc <= gr) sa[gr * slda + gc] = -t.acc[m][n][i];
         }
     return;
   }
@@ -919,9 +926,9 @@ __global__ void __launch_bounds__(256, BN == 64 ? 4 : (BM == 64 ? (sizeof(T) == 
     for (int n = 0; n < Tile::NT; ++n)
 #pragma unroll
       for (int i = 0; i < M::ACC; ++i) {
-        const int64_t gr = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
-        const int64_t gc = col0 + wc * Tile::WN + n * M::TN + M::acc_col(lane);
-        u.a[gr * u.lda + gc] = -t.acc[m][n][i];
+        const int64_t gr = srow + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
+        const int64_t gc = scol + wc * Tile::WN + n * M::TN + M::acc_col(lane);
+        sa[gr * slda + gc] = -t.acc[m][n][i];
       }
 }
 
