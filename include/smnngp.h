@@ -168,6 +168,35 @@ int smn_kernel_conv_resnet(smn_ctx* ctx, int dtype, int act, int block_size,
                            const void* x1_d, int64_t n1, const void* x2_d, int64_t n2,
                            int64_t H, int64_t W, int64_t C, int fill, void* nngp_d, int64_t ldk);
 
+/* conv-NNGP with global average pooling in front of the read-out:
+ *   num_hiddens x [stax.Conv(1, (3,3), padding SAME, W_std=w_std, b_std=b_std); act];  stax.GlobalAvgPool();
+ *   stax.Dense(num_class, W_std=last_w_std, b_std=0)
+ * -- get_cnn_kernel with stax.Flatten replaced by stax.GlobalAvgPool (the stax.AvgPool left commented out at
+ * experiments/nt_kernels.py:75).  The read-out averages the covariance of every pixel p of x1[n] with every pixel q of x2[m]:
+ *   K0[p,q] = sum_c x1[n,p,c] x2[m,q,c] / C;   per layer K~[p,q] = w_std^2/9 sum_{d in 3x3} K[p+d,q+d] + b_std^2 (terms outside
+ *   either image are 0), K[p,q] = act(K~[p,q]; K~_nn[p,p], K~_mm[q,q]);   nngp[n,m] = last_w_std^2 sum_{p,q} K[p,q] / (H W)^2
+ * -- (H W)^2 entries per pair and layer where smn_kernel_cnn has H W.  num_hiddens == 0: last_w_std^2 (mean_p x1[n,p]) .
+ * (mean_q x2[m,q]) / C.
+ * smn_kernel_cnn_pool: same argument meaning and validation as smn_kernel_cnn (x2_d == NULL: the symmetric build, pairs m <= n,
+ *   mirrored under SMN_FILL_FULL; SMN_FILL_LOWER leaves the strict upper triangle and everything past the row's n2 entries
+ *   untouched).  Null ctx / x1_d / nngp_d, n < 1, ldk < n2 and a bad act, dtype or fill: SMN_EINVAL, by name.
+ *   Limit: H*W <= SMN_CNN_POOL_MAX_PIXELS whatever the aspect ratio (1 x 1024 included); larger images return SMN_ENOTSUP with a
+ *   message naming the limit.  b_std == 0 and all-zero neighbourhoods give finite values (a zero-variance pixel contributes 0
+ *   under ReLU).  Per-entry arithmetic in `dtype`; every sum over pixels and offsets in fp64, in an order fixed by (H, W): no
+ *   floating-point atomics, and the bits of nngp[n,m] depend on the two images, the hyper-parameters and (H, W, C) alone -- not
+ *   on n1, n2, fill, ldk, the pair's position, or the number of passes the pair list is cut into when its partial sums exceed the
+ *   workspace budget (256 MB, or smn_debug_batch_bytes if smaller).  The diagonal pair (n, n) of a symmetric build takes its
+ *   same-pixel entries K[p,p] from the per-image variance recursion, as smn_kernel_cnn takes its diagonal.  No synchronisation.
+ * smn_kernel_cnn_pool_diag: diag_d[i] = nngp[i,i] of the symmetric build, i < n, bit for bit, without the other pairs. */
+#define SMN_CNN_POOL_MAX_PIXELS 1024
+int smn_kernel_cnn_pool(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                        double w_std, double b_std, double last_w_std,
+                        const void* x1_d, int64_t n1, const void* x2_d, int64_t n2,
+                        int64_t H, int64_t W, int64_t C, int fill, void* nngp_d, int64_t ldk);
+int smn_kernel_cnn_pool_diag(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                             double w_std, double b_std, double last_w_std,
+                             const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C, void* diag_d);
+
 /* ---- factorisation and solves ----
  * smn_cholesky: in-place lower Cholesky of the leading n_factor x n_factor block of the symmetric
  * matrix a_d [n_total,n_total] (lower triangle read/written), carried through the remaining

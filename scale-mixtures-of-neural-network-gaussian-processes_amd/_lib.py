@@ -72,6 +72,8 @@ PROTOTYPES = {
     "smn_recursion": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _vp, _vp, _i64],
     "smn_kernel_cnn": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i, _vp, _i64],
     "smn_kernel_conv_resnet": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i, _vp, _i64],
+    "smn_kernel_cnn_pool": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i, _vp, _i64],
+    "smn_kernel_cnn_pool_diag": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp],
     "smn_cholesky": [_vp, _i, _vp, _i64, _i64, _i64, _i64, _d, _d, _pi, _pd],
     "smn_trsm": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _i64, _i],
     "smn_transpose": [_vp, _i, _vp, _i64, _vp, _i64, _i64, _i64],

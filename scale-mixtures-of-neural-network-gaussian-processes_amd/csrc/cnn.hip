@@ -405,6 +405,16 @@ int launch_pairs(smn_ctx* ctx, const PairArgs<T>& a, int64_t blocks, size_t lds,
   return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn: H*W > %d", 64 * kMaxPix);
 }
 
+// THE launch of the per-image pass.  No profiling scope and no launch check of its own: the callers bracket one or two of them.
+template <typename T>
+int launch_conv_q(smn_ctx* ctx, const ConvProg& p, const void* x, int64_t n, T* R, T* diag, bool patch44, T* xperm) {
+  const size_t lds_q = conv_q_lds_bytes(p.H, p.W);
+  SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(conv_q_kernel<T>), lds_q));
+  hipLaunchKernelGGL(conv_q_kernel<T>, dim3((unsigned)n), dim3(256), lds_q, ctx->stream, static_cast<const T*>(x), n, p, R, diag,
+                     patch44 ? 1 : 0, patch44 ? xperm : static_cast<T*>(nullptr));
+  return SMN_OK;
+}
+
 template <typename T>
 int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, const void* x1, int64_t n1,
           const void* x2, int64_t n2, int64_t H, int64_t W, int64_t C, int fill, void* out, int64_t ldk) {
@@ -412,10 +422,8 @@ int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, cons
   if (sym) n2 = n1;
   const ConvProg p = make_prog(act, layers, H, W, C, w, b, lw);
   const int64_t HW = H * W;
-  const size_t psz = (size_t)(H + 2) * (W + 2);
-  const size_t lds_q = (2 * psz + 256) * sizeof(double);
   const size_t lds_p = wave_map_lds_bytes<T>(H, W);
-  if (lds_q > 160 * 1024 || lds_p > 160 * 1024)
+  if (conv_q_lds_bytes(H, W) > 160 * 1024 || lds_p > 160 * 1024)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_cnn: image %lldx%lld too large for the on-chip pair map", (long long)H, (long long)W);
   // tables: R1 [n1][L][HW], diag1 [n1] (+ R2, diag2); patch order + patch-order copies of the inputs for conv_pair44_kernel
   const bool patch44 = H == 32 && W == 32 && (C == 1 || C == 3) && sizeof(T) == 8;
@@ -431,12 +439,8 @@ int cnn_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, cons
   T* xp2 = sym ? xp1 : xp1 + xn1;
   {
     ProfScope ps(ctx, PROF_PREP, ctx->stream);
-    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(conv_q_kernel<T>), lds_q));
-    hipLaunchKernelGGL(conv_q_kernel<T>, dim3((unsigned)n1), dim3(256), lds_q, ctx->stream,
-                       static_cast<const T*>(x1), n1, p, R1, d1, patch44 ? 1 : 0, patch44 ? xp1 : nullptr);
-    if (!sym)
-      hipLaunchKernelGGL(conv_q_kernel<T>, dim3((unsigned)n2), dim3(256), lds_q, ctx->stream,
-                         static_cast<const T*>(x2), n2, p, R2, d2, patch44 ? 1 : 0, patch44 ? xp2 : nullptr);
+    SMN_TRY(launch_conv_q<T>(ctx, p, x1, n1, R1, d1, patch44, xp1));
+    if (!sym) SMN_TRY(launch_conv_q<T>(ctx, p, x2, n2, R2, d2, patch44, xp2));
   }
   SMN_CHECK_LAUNCH(ctx);
   PairArgs<T> a;
@@ -458,22 +462,26 @@ template <typename T>
 int cnn_diag_t(smn_ctx* ctx, int act, int layers, double w, double b, double lw, const void* x, int64_t n, int64_t H, int64_t W,
                int64_t C, void* diag) {
   const ConvProg p = make_prog(act, layers, H, W, C, w, b, lw);
-  const size_t lds_q = (2 * (size_t)(H + 2) * (W + 2) + 256) * sizeof(double);
-  if (lds_q > 160 * 1024)
+  if (conv_q_lds_bytes(H, W) > 160 * 1024)
     return smn_fail(ctx, SMN_ENOTSUP, "smn_kernel_conv_diag: image %lldx%lld too large for the on-chip map", (long long)H, (long long)W);
   void* tv = nullptr;   // the factor tables the pass writes beside the diagonal: scratch here
   SMN_TRY(smn_workspace(ctx, 1, sizeof(T) * (size_t)n * (size_t)(layers > 0 ? layers : 1) * (size_t)(H * W) + 64, &tv));
-  {
-    ProfScope ps(ctx, PROF_PREP, ctx->stream);
-    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(conv_q_kernel<T>), lds_q));
-    hipLaunchKernelGGL(conv_q_kernel<T>, dim3((unsigned)n), dim3(256), lds_q, ctx->stream, static_cast<const T*>(x), n, p,
-                       static_cast<T*>(tv), static_cast<T*>(diag), 0, static_cast<T*>(nullptr));
-  }
-  SMN_CHECK_LAUNCH(ctx);
-  return SMN_OK;
+  return cnn_tables(ctx, sizeof(T) == 8 ? SMN_F64 : SMN_F32, p, x, n, tv, diag);
 }
 
 }  // namespace
+
+int cnn_tables(smn_ctx* ctx, int dtype, const smn_cnn::ConvProg& p, const void* x_d, int64_t n, void* r_d, void* diag_d) {
+  return by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    {
+      ProfScope ps(ctx, PROF_PREP, ctx->stream);
+      SMN_TRY(launch_conv_q<T>(ctx, p, x_d, n, static_cast<T*>(r_d), static_cast<T*>(diag_d), false, static_cast<T*>(nullptr)));
+    }
+    SMN_CHECK_LAUNCH(ctx);
+    return (int)SMN_OK;
+  });
+}
 
 int cnn_diag(smn_ctx* ctx, int dtype, int act, int layers, double w, double b, double lw, const void* x_d, int64_t n,
              int64_t H, int64_t W, int64_t C, void* diag_d) {

@@ -344,3 +344,10 @@ inline void tiled_pair_grid(int64_t resident, int64_t npairs, int64_t max_blocks
 }
 
 }  // namespace smn_cnn
+
+// Dynamic LDS of the per-image pass (cnn.hip conv_q_kernel): two padded fp64 maps and the 256 doubles of its reduction.
+inline size_t conv_q_lds_bytes(int64_t H, int64_t W) { return (2 * (size_t)(H + 2) * (size_t)(W + 2) + 256) * sizeof(double); }
+// The per-image pass of smn_kernel_cnn alone (cnn.hip conv_q_kernel, plain pixel order): r_d [n][layers][H W] = the factor
+// tables the pair kernels multiply, diag_d [n] = K(x_i, x_i) of the Flatten kernel; both of `dtype`.  The caller has checked
+// that conv_q_lds_bytes(H, W) fits the LDS.  smn_kernel_conv_diag (kind 0) is this call; cnn_pool.hip reads the same tables.
+int cnn_tables(smn_ctx* ctx, int dtype, const smn_cnn::ConvProg& p, const void* x_d, int64_t n, void* r_d, void* diag_d);

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import DeviceArray, as_device, default_context
 
-__all__ = ["get_mlp_kernel", "get_cnn_kernel", "get_conv_resnet_kernel", "get_dense_resnet_kernel"]
+__all__ = ["get_mlp_kernel", "get_cnn_kernel", "get_cnn_pool_kernel", "get_conv_resnet_kernel", "get_dense_resnet_kernel"]
 
 Kernels = collections.namedtuple("Kernels", ["nngp", "ntk"])
 
@@ -144,7 +144,8 @@ def get_dense_resnet_kernel(num_hiddens, num_class=1, act="relu", w_std=1., b_st
 
 class CnnKernelFn:
     """kernel_fn of get_cnn_kernel (experiments/nt_kernels.py:34-45) or, with entry="smn_kernel_conv_resnet", of
-    get_conv_resnet_kernel (:48-80, num_hiddens = block size); x is [N,H,W,C]; NNGP only."""
+    get_conv_resnet_kernel (:48-80, num_hiddens = block size), or, with entry="smn_kernel_cnn_pool", of get_cnn_pool_kernel
+    (GlobalAvgPool in place of Flatten); x is [N,H,W,C]; NNGP only."""
 
     def __init__(self, num_hiddens, act, w_std, b_std, last_w_std, ctx=None, entry="smn_kernel_cnn"):
         self.num_hiddens, self.act_name, self.act = int(num_hiddens), act, get_act_class(act)
@@ -159,6 +160,8 @@ class CnnKernelFn:
     def __call__(self, x1, x2=None, get="nngp", fill="full"):
         if get != "nngp":
             raise NotImplementedError("conv kernel: only get='nngp' is on the hot path")
+        if not isinstance(x1, DeviceArray) and np.ndim(x1) != 4:   # a host array: refused before a context is made
+            raise ValueError("conv kernel expects x of shape [N,H,W,C]")
         ctx = self.ctx or (x1.ctx if isinstance(x1, DeviceArray) else default_context())
         a = as_device(x1, ctx)
         if len(a.shape) != 4:
@@ -175,6 +178,34 @@ class CnnKernelFn:
                  a.ptr, n1, None if b is None else b.ptr, n2, h, w, c,
                  _lib.FILL_FULL if fill == "full" else _lib.FILL_LOWER, k.ptr, n2)
         return k
+
+    def diag(self, x):
+        """K(x_i, x_i) [N] as a device array without the other pairs: the bits of the diagonal of kernel_fn(x, None).  The
+        Flatten kernels run their per-image pass (smn_kernel_conv_diag, kind 0 / 1); the pooled kernel has no per-image closed
+        form -- every pixel of an image meets every other -- and runs its N diagonal pairs (smn_kernel_cnn_pool_diag)."""
+        if not isinstance(x, DeviceArray) and np.ndim(x) != 4:
+            raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+        ctx = self.ctx or (x.ctx if isinstance(x, DeviceArray) else default_context())   # __call__'s precedence
+        a = as_device(x, ctx)
+        if len(a.shape) != 4:
+            raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+        n, h, w, c = a.shape
+        out = ctx.empty((n,), a.dtype)
+        if self.entry == "smn_kernel_cnn_pool":
+            ctx.call("smn_kernel_cnn_pool_diag", a.dcode, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std,
+                     a.ptr, n, h, w, c, out.ptr)
+        else:
+            ctx.call("smn_kernel_conv_diag", a.dcode, 0 if self.entry == "smn_kernel_cnn" else 1, self.act, self.num_hiddens,
+                     self.w_std, self.b_std, self.last_w_std, a.ptr, n, h, w, c, out.ptr)
+        return out
+
+
+def get_cnn_pool_kernel(num_hiddens, num_class=1, act="relu", w_std=1., b_std=0., last_w_std=1.):
+    """get_cnn_kernel with stax.GlobalAvgPool() in place of stax.Flatten() (the pooling experiments/nt_kernels.py:75 leaves
+    commented out): num_hiddens x [Conv(3x3, SAME); act]; GlobalAvgPool; Dense.  Translation-aware: the read-out averages the
+    covariance of every pixel of one image with every pixel of the other, (H W)^2 entries per pair and layer
+    (csrc/cnn_pool.hip); H W <= 1024.  `num_class` does not enter the kernel.  NNGP only, no analytic gradients."""
+    return CnnKernelFn(num_hiddens, act, w_std, b_std, last_w_std, entry="smn_kernel_cnn_pool")
 
 
 def get_cnn_kernel(num_hiddens, num_class=1, act="relu", w_std=1., b_std=0., last_w_std=1.):

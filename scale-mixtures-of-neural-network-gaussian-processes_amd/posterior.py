@@ -403,12 +403,7 @@ class FittedPosterior:
         diagonal); for any other callable the diagonal of kernel_fn(x, None)."""
         fn = self.kernel_fn
         if isinstance(fn, CnnKernelFn):
-            xd = as_device(xc, self.ctx, dtype=self.dtype)
-            out = self.ctx.empty((xd.shape[0],), self.dtype)
-            act, depth, w, b, lw = fn.params
-            self.ctx.call("smn_kernel_conv_diag", xd.dcode, 0 if fn.entry == "smn_kernel_cnn" else 1, act, depth, w, b, lw,
-                          xd.ptr, xd.shape[0], xd.shape[1], xd.shape[2], xd.shape[3], out.ptr)
-            return out
+            return fn.diag(as_device(xc, self.ctx, dtype=self.dtype))
         return self.ctx.to_device(np.ascontiguousarray(self._kernel(xc, None).diagonal(), dtype=self.dtype))
 
     # ---- predictions

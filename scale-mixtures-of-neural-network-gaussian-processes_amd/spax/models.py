@@ -50,7 +50,7 @@ def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
 
 def grad_route(kernel_fn, likelihood):
     """The fused C-ABI entry SPR.loss_and_grad uses for this kernel function and likelihood: "smn_spr_loss_grad" (MLP /
-    dense ResNet) or "smn_spr_cnn_loss_grad" (get_cnn_kernel).  Anything else, the conv ResNet included, has no analytic
+    dense ResNet) or "smn_spr_cnn_loss_grad" (get_cnn_kernel).  Anything else, the conv ResNet and get_cnn_pool_kernel included, has no analytic
     gradient: NotImplementedError, which train.build_train_step(method="auto") answers with central differences."""
     if hasattr(likelihood, "lml_params"):
         if isinstance(kernel_fn, KernelFn):
@@ -703,10 +703,7 @@ class SVSP(Module):
         if q_mu.shape != (c, n_i) or q_var.shape != (c, n_i):
             raise ValueError("q_mu / q_sqrt must be [num_latent_gps, num_inducing] = %s" % ((c, n_i),))
         k_zt = kernel_fn(z, x, get="nngp")                        # [I,T]
-        ktt = ctx.empty((t,), self.dtype)
-        act, depth, w, b, lw = kernel_fn.params
-        ctx.call("smn_kernel_conv_diag", x.dcode, 0 if kernel_fn.entry == "smn_kernel_cnn" else 1, act, depth, w, b, lw,
-                 x.ptr, t, x.shape[1], x.shape[2], x.shape[3], ktt.ptr)
+        ktt = kernel_fn.diag(x)                                   # [T] prior variances, the bits of the symmetric diagonal
         mean, var = ctx.empty((t, c), self.dtype), ctx.empty((t, c), self.dtype)
         info, nonpos = C.c_int(), C.c_int64()
         q_mu_d, q_var_d = ctx.to_device(q_mu), ctx.to_device(q_var)                        # fp64 whatever the model's dtype
