@@ -786,6 +786,45 @@ int smn_kernel_mlp_input_grad(smn_ctx* ctx, int dtype, int net, int act, int num
                               const void* x1_d, int64_t n1, int64_t ldx1, const void* x2_d, int64_t n2, int64_t ldx2, int64_t d,
                               const void* gbar_d, int64_t ldg, void* gx_d, int64_t ldgx);
 
+/* ---- the log-marginal likelihood differentiated in the INPUTS: per-feature input scales (automatic relevance determination) and
+ *      d loss / d X (experiments/regression/train.py:61-67 under objax.GradValues with the inputs, or a per-feature scale in front
+ *      of experiments/nt_kernels.py:21-31, 83-103, among the variables; spax/models.py:93-98 is the loss) ----
+ * Notation: x~ = the inputs as the kernel sees them, G = coef A A^T - c K~^-1 the seed of smn_lml_grad_terms_multi (A = K~^-1 Y
+ * [n, c]), u_nm = x~_n . x~_m / d, v_n = |x~_n|^2 / d, F_1 = dK_nm/du, F_2[n, m] = dK_nm/dv_n, ddiag_n = dK_nn/dv_n (closed-form
+ * diagonal).  Then with W = G o F_1 (zero diagonal) and r_n = sum_{m != n} G_nm F_2[n, m]
+ *     gx_n   = d log p / d x~_n = (sum_m W_nm x~_m + (2 r_n + G_nn ddiag_n) x~_n) / d
+ *     feat_j = sum_n gx[n, j] x~[n, j]        (x~ = s o x:  d log p / d s_j = feat_j / s_j,  d log p / d x_n = s o gx_n)
+ * smn_scale_columns: out_d [n, ldo >= d] = x_d [n, ldx >= d] with column j multiplied by s_h[j] (a host vector, rounded to `dtype`
+ *   first; the product in `dtype`: the bits of NumPy's x * s.astype(dtype)).  out_d may be x_d.  16-byte accesses when ldx and ldo
+ *   are multiples of 16 bytes and both bases are aligned.  One synchronisation (the upload of s).
+ * smn_kernel_mlp_input_grad_sym: gx_d [n, ldgx >= d] and / or feat_h [d] (host, fp64; one may be NULL, each leaves the other's bits
+ *   as they are) for a generic symmetric seed, the way smn_kernel_cnn_grad_terms takes one: neg_kinv_d [n, ldkinv >= n] (its lower
+ *   triangle is read), alpha_d [n, c] row-major and coef; with coef = 0, a zero alpha and c = 1 the seed is the matrix passed as
+ *   neg_kinv_d.  net may carry SMN_NET_NTK (Theta in place of K).  One elementwise pass over the lower triangle of the Gram matrix
+ *   x~ x~^T / d (built here as the gradient entries build it) carries (K, K_u, K_v, K_v') -- the row-side and the column-side variance
+ *   tangent -- through the layer stack in `dtype` and writes W; the sums of G o F_2 are fp64, one slot per (tile, row), added in
+ *   tile order (no floating-point atomics: two calls give the same bits, and a row's values do not depend on ldx, ldgx or an earlier
+ *   call); W X~ runs on the MFMA tile engine, its epilogue adding the row term and, for feat_h, the fp64 column sums of gx o x~.
+ *   Two exactly equal rows (ReLU: D_A = D_1 = 0 there) and an all-zero row with b_std == 0 give finite values.  Workspace, beside
+ *   the Gram matrix: one n_pad x n_pad matrix (W), the transposed padded inputs and (n_pad / 64 + 1) x n_pad doubles, n_pad =
+ *   round_up(n, 128) -- 1.1 GB in fp32 at n = 16384 --, all acquired before the first launch.  c <= 48; at most 16 activation layers
+ *   (SMN_ENOTSUP above).  feat_h != NULL: one synchronisation at the end; else none.
+ * smn_spr_loss_grad_inputs: smn_spr_loss_grad_multi followed by that pass on the posterior it leaves on the device: quad_h,
+ *   quad_cols_h, logdet_h, info_h and terms_h[0..3] are smn_spr_loss_grad_multi's bits on the same arguments, gx_d / feat_h those of
+ *   smn_kernel_mlp_input_grad_sym fed smn_spr_kinv's outputs and coef = the head's (1: Gaussian; (df + n c) / ((df + Q / scale)
+ *   scale): Student-t).  These are derivatives of log p, not of the loss (the loss is -log p / n).  Not positive definite: *info_h
+ *   != 0, NaN in the scalar outputs, gx_d and feat_h untouched, SMN_OK. */
+int smn_scale_columns(smn_ctx* ctx, int dtype, const void* x_d, int64_t n, int64_t ldx, int64_t d, const double* s_h, void* out_d,
+                      int64_t ldo);
+int smn_kernel_mlp_input_grad_sym(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                                  double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* neg_kinv_d,
+                                  int64_t ldkinv, const void* alpha_d, int64_t c, double coef, void* gx_d, int64_t ldgx,
+                                  double* feat_h);
+int smn_spr_loss_grad_inputs(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                             double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const void* y_d, int64_t c,
+                             double eps_abs, double df, double scale, double* quad_h, double* quad_cols_h, double* logdet_h,
+                             int* info_h, double terms_h[4], void* gx_d, int64_t ldgx, double* feat_h);
+
 /* ---- multi-GPU (nothing in the reference to mirror) ----
  * One process per GPU.  Rank 0 calls smn_comm_unique_id and ships the 128 bytes to the other
  * ranks by any host channel; every rank then calls smn_comm_init.  smn_allgather is an RCCL

@@ -145,6 +145,10 @@ PROTOTYPES = {
     "smn_fit_apply": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64],
     "smn_fit_predict_grad": [_vp, _vp, _i64, _i64, _vp, _vp],
     "smn_kernel_mlp_input_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64],
+    "smn_scale_columns": [_vp, _i, _vp, _i64, _i64, _i64, _pd, _vp, _i64],
+    "smn_kernel_mlp_input_grad_sym": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _d, _vp, _i64, _pd],
+    "smn_spr_loss_grad_inputs": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pi, _pd,
+                                 _vp, _i64, _pd],
     "smn_fit_info": [_vp, _pi64, _pi64, _pi64, C.POINTER(C.c_size_t)],
     "smn_fit_destroy": [_vp],
     "smn_fit_reserve": [_vp, _i64],

@@ -131,7 +131,8 @@ def read_run(ckpt_dir, ckpt_index=None):
 def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtype=np.float32):
     """experiments/regression/test.py:89-130: rebuild SPR from a run directory and assign the stored raw values.  The
     run's arguments may carry ``kernel``: "nngp" (the default when absent) or "ntk" for a model built on NTKKernel, whose
-    trainables and names are the same."""
+    trainables and names are the same.  A collection that carries the vector variable ``input_scales`` (a kernel built with
+    per-feature input scales) gets them back; one without reads exactly as before."""
     from . import nt_kernels
     from .spax.kernels import NNGPKernel, NTKKernel
     from .spax.likelihoods import GaussianLikelihood, StudentTLikelihood
@@ -152,7 +153,13 @@ def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtyp
     covariance = context.get("kernel") or "nngp"
     if covariance not in ("nngp", "ntk"):
         raise ValueError("Unsupported kernel '%s'" % covariance)
-    kernel = (NTKKernel if covariance == "ntk" else NNGPKernel)(get_kernel_fn, 1.0, 1.0, 1.0)
+    index = latest_index(ckpt_dir) if ckpt_index is None else ckpt_index
+    scales_raw = get_from_vars(load_var_collection(os.path.join(ckpt_dir, FILE_FORMAT.format(index))), "input_scales")
+    kernel_cls = NTKKernel if covariance == "ntk" else NNGPKernel
+    if scales_raw is None:
+        kernel = kernel_cls(get_kernel_fn, 1.0, 1.0, 1.0)
+    else:
+        kernel = kernel_cls(get_kernel_fn, 1.0, 1.0, 1.0, input_scales=np.ones(np.size(scales_raw)))
     method = context["method"]
     if method == "gp":
         likelihood = GaussianLikelihood()
@@ -166,6 +173,8 @@ def restore_spr(ckpt_dir, x_train, y_train, y_mean, y_std, ckpt_index=None, dtyp
     model.kernel.w_std.assign(raw["w_std"])
     model.kernel.b_std.assign(raw["b_std"])
     model.kernel.last_w_std.assign(raw["last_w_std"])
+    if scales_raw is not None:
+        model.kernel.input_scales.assign(np.asarray(scales_raw, dtype=np.float64).reshape(-1))
     if method == "tp":                       # the Gaussian likelihood has no a / b (test.py assigns them blindly)
         if raw["a"] is not None:
             model.likelihood.a.assign(raw["a"])

@@ -432,6 +432,22 @@ int input_grad_factors(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w
   return by_dtype(o.spec.dtype, [&](auto e) { return ig_factors_t<decltype(e)>(ctx, o, w, gbar_d, ldg); });
 }
 
+int input_grad_tables(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const double* q64, int64_t rows, void* tab_d, void* ddiag_d) {
+  const int nsets = input_grad_nsets(spec);
+  const double w2 = spec.w_std * spec.w_std, b2 = spec.b_std * spec.b_std, lw2 = spec.last_w_std * spec.last_w_std;
+  by_dtype(spec.dtype, [&](auto e) {
+    using T = decltype(e);
+    ig_with_form(spec.net, spec.act, ntk, [&](auto NET, auto ACT, auto) -> int {
+      hipLaunchKernelGGL((ig_tables_kernel<decltype(NET)::value, decltype(ACT)::value, T>), dim3((unsigned)((rows + 255) / 256)),
+                         dim3(256), 0, ctx->stream, q64, rows, nsets, w2, b2, lw2, ntk ? 1 : 0, static_cast<T*>(tab_d),
+                         static_cast<T*>(ddiag_d));
+      return SMN_OK;
+    });
+  });
+  SMN_CHECK_LAUNCH(ctx);
+  return SMN_OK;
+}
+
 int input_grad_seed(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* seed_d, int64_t lds) {
   by_dtype(o.spec.dtype, [&](auto e) {
     using T = decltype(e);

@@ -277,6 +277,9 @@ size_t input_grad_ws_bytes(int dtype, int nsets, int64_t rows1, int64_t rows2, b
 InputGradWs input_grad_ws_carve(void* base, int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded);
 // tables + the hot kernel.  gbar_d == nullptr: F_1, F_2 into ws.f1 / ws.f2; else gbar o F_1 into ws.w and the row sums into ws.s
 int input_grad_factors(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* gbar_d, int64_t ldg);
+// the table kernel alone: tab_d [nsets][4][rows] = (q, p = dq/dq0, ra, rb) per activation layer and row of q64 [rows], and
+// ddiag_d [rows] = dK_rr/dq0 (ntk: dTheta_rr/dq0), both of spec.dtype (input_grad_sym.hip)
+int input_grad_tables(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const double* q64, int64_t rows, void* tab_d, void* ddiag_d);
 // ws.w = F_1 o seed, ws.s = rowsum(F_2 o seed); seed [rows1, rows2] with row stride lds, or one row for all (lds = 0)
 int input_grad_seed(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* seed_d, int64_t lds);
 // out[r, e] = ca (ws.w X2)[r, e] + (cs ws.s[r] + cd ws.ddiag[r]) x1[r, e]   (r < n1, e < d)

@@ -7,6 +7,7 @@ arrays.  ``get`` accepts "nngp", "ntk" or a tuple of both (a namedtuple-like Ker
 from __future__ import annotations
 
 import collections
+import ctypes as C
 
 import numpy as np
 
@@ -44,10 +45,31 @@ def _parse_get(get):
     return names, mask
 
 
+def _check_scales(s):
+    """input_scales as a positive float64 vector (None stays None)."""
+    if s is None:
+        return None
+    s = np.array(s, dtype=np.float64).reshape(-1)
+    if s.size == 0 or not np.all(np.isfinite(s)) or not np.all(s > 0.0):
+        raise ValueError("input_scales must be a non-empty vector of positive finite numbers")
+    return s
+
+
+def _scale_columns(ctx, a, s, out=None):
+    """a [n, d] with column j multiplied by s[j], in a's dtype (smn_scale_columns); `out` may be a itself."""
+    n, d = a.shape
+    if s.shape[0] != d:
+        raise ValueError("input_scales has %d entries for inputs with %d features" % (s.shape[0], d))
+    out = ctx.empty((n, d), a.dtype) if out is None else out
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    ctx.call("smn_scale_columns", a.dcode, a.ptr, n, d, d, s.ctypes.data_as(C.POINTER(C.c_double)), out.ptr, d)
+    return out
+
+
 class KernelFn:
     """kernel_fn of an MLP-family architecture (net = MLP or dense ResNet)."""
 
-    def __init__(self, net, num_hiddens, act, w_std, b_std, last_w_std, ctx=None, cov="nngp"):
+    def __init__(self, net, num_hiddens, act, w_std, b_std, last_w_std, ctx=None, cov="nngp", input_scales=None):
         self.net, self.num_hiddens = int(net), int(num_hiddens)
         self.act_name, self.act = act, get_act_class(act)
         self.w_std, self.b_std, self.last_w_std = float(w_std), float(b_std), float(last_w_std)
@@ -55,6 +77,7 @@ class KernelFn:
         if cov not in ("nngp", "ntk"):
             raise ValueError("cov must be 'nngp' or 'ntk', got %r" % (cov,))
         self.cov = cov
+        self.input_scales = _check_scales(input_scales)
 
     @property
     def params(self):
@@ -66,7 +89,25 @@ class KernelFn:
     def with_cov(self, cov):
         """The same kernel function in covariance mode `cov` ("nngp" or "ntk"): which of its two kernels a model built on
         it (spax.kernels.NNGPKernel / NTKKernel) takes as the covariance function of its GP.  `__call__` is unaffected."""
-        return KernelFn(self.net, self.num_hiddens, self.act_name, self.w_std, self.b_std, self.last_w_std, self.ctx, cov)
+        return KernelFn(self.net, self.num_hiddens, self.act_name, self.w_std, self.b_std, self.last_w_std, self.ctx, cov,
+                        self.input_scales)
+
+    def with_input_scales(self, s):
+        """The same kernel function on scaled inputs, k(x, x') = K(s o x, s o x'): s is a positive vector with one entry per
+        input feature (automatic relevance determination; None takes the scales off).  The scaling multiplies in the storage
+        dtype with s rounded to it first, so the results are the bits of this kernel function without scales on
+        x * s.astype(dtype).  `params` is unchanged: the model entries are handed `scaled(x)`."""
+        return KernelFn(self.net, self.num_hiddens, self.act_name, self.w_std, self.b_std, self.last_w_std, self.ctx, self.cov, s)
+
+    def scaled(self, x, ctx=None, dtype=None):
+        """x as the kernel sees it: the device array x * input_scales (smn_scale_columns), or x itself without scales."""
+        ctx = ctx or self.ctx or (x.ctx if isinstance(x, DeviceArray) else default_context())
+        a = as_device(x, ctx, dtype=dtype)
+        if len(a.shape) != 2:
+            a = ctx.to_device(a.numpy().reshape(a.shape[0], -1))
+        if self.input_scales is None:
+            return a
+        return _scale_columns(ctx, a, self.input_scales)
 
     def cov_matrix(self, x1, x2=None, fill="full"):
         """The matrix of the covariance mode: K or Theta of x1 against x2."""
@@ -88,6 +129,9 @@ class KernelFn:
                 raise ValueError("x1 and x2 feature dimensions differ: %s vs %s" % (a.shape, b.shape))
             if b.dtype != a.dtype:
                 raise TypeError("x1 and x2 dtypes differ")
+        if self.input_scales is not None:
+            a = _scale_columns(ctx, a, self.input_scales)
+            b = None if b is None else _scale_columns(ctx, b, self.input_scales)
         n1, d = a.shape
         n2 = n1 if b is None else b.shape[0]
         k = ctx.empty((n1, n2), a.dtype) if mask & _lib.GET_NNGP else None
@@ -106,7 +150,9 @@ class KernelFn:
     def input_grad(self, x1, x2, gbar, get=None):
         """gx [n1, d] = sum_j gbar[r, j] dK(x1_r, x2_j)/dx1_r as a device array (smn_kernel_mlp_input_grad): the kernel
         differentiated in its first argument, contracted with the seed gbar [n1, n2].  `get` ("nngp" or "ntk") picks K or
-        Theta and defaults to the covariance mode.  x2 must be given: the form in which both arguments move is not there."""
+        Theta and defaults to the covariance mode.  x2 must be given: the form in which both arguments move is the seeded
+        one of the exact models (SPR.loss_input_grad).  Under input scales both arguments are scaled first and the result is
+        multiplied by s: the derivative in x1 as handed in."""
         get = self.cov if get is None else get
         if get not in ("nngp", "ntk"):
             raise ValueError("get must be 'nngp' or 'ntk', got %r" % (get,))
@@ -125,10 +171,14 @@ class KernelFn:
         if tuple(g.shape) != (a.shape[0], b.shape[0]):
             raise ValueError("gbar must be [n1, n2] = %s, got %s" % ((a.shape[0], b.shape[0]), g.shape))
         n1, d = a.shape
+        if self.input_scales is not None:
+            a, b = _scale_columns(ctx, a, self.input_scales), _scale_columns(ctx, b, self.input_scales)
         out = ctx.empty((n1, d), a.dtype)
         net = self.net | _lib.NET_NTK if get == "ntk" else self.net
         ctx.call("smn_kernel_mlp_input_grad", a.dcode, net, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std,
                  a.ptr, n1, d, b.ptr, b.shape[0], d, d, g.ptr, b.shape[0], out.ptr, d)
+        if self.input_scales is not None:
+            _scale_columns(ctx, out, self.input_scales, out=out)
         return out
 
 

@@ -132,6 +132,7 @@ class FittedPosterior:
         if self.fused:
             x2 = _as2d(x)
             self.num_features = int(x2.shape[1])
+            x2 = self._scaled(x2)          # input scales: the state is fitted on s o x (x_train stays what was handed in)
             net, act, depth, w, b, lw = kernel_fn.with_cov(mode).params      # "ntk": net carries SMN_NET_NTK
             self.ctx.call("smn_fit_create", code, net, act, depth, w, b, lw, x2.ptr, n, self.num_features, self.num_features,
                           y.ptr, c, float(ridge_rel), float(ridge_abs), capacity, C.byref(handle), quad, C.byref(logdet),
@@ -151,6 +152,16 @@ class FittedPosterior:
         self.ridge, self.max_points = float(ridge.value), int(max_points.value)
         if reserve is not None:
             self.reserve(reserve)
+
+    def _scaled(self, x2):
+        """x2 [rows, d] as the fused state sees it: multiplied by the kernel function's input scales (the snapshot taken with
+        the kernel function), or x2 itself."""
+        s = getattr(self.kernel_fn, "input_scales", None)
+        if s is None:
+            return x2
+        if x2.shape[1] != s.shape[0]:
+            raise ValueError("input_scales has %d entries for inputs with %d features" % (s.shape[0], x2.shape[1]))
+        return self.kernel_fn.scaled(x2, self.ctx)
 
     @classmethod
     def from_model(cls, model, capacity=2048, reserve=None):
@@ -290,7 +301,7 @@ class FittedPosterior:
             y_host = np.asarray(yd.raw_numpy(), dtype=np.float64).reshape(k, c)
         quad, logdet, info = (C.c_double * c)(), C.c_double(), C.c_int()
         if self.fused:
-            x2 = _as2d(xd)
+            x2 = self._scaled(_as2d(xd))
             ctx.call_on("smn_fit_append", self._handle, x2.ptr, k, self.num_features, yd.ptr, quad, C.byref(logdet), C.byref(info))
             self._sync_stats()
             went = self.num_data - n_before
@@ -430,6 +441,7 @@ class FittedPosterior:
             xt = _as2d(xt)
             if xt.shape[1] != self.num_features:
                 raise ValueError("x has %d features, the training data %d" % (xt.shape[1], self.num_features))
+            xt = self._scaled(xt)
             ctx.call_on("smn_fit_predict", self._handle, xt.ptr, t, xt.shape[1], mean.ptr, vptr, cptr, t)
         else:
             n = self.num_data
@@ -468,8 +480,15 @@ class FittedPosterior:
             raise ValueError("x has %d features, the training data %d" % (xt.shape[1], d))
         dmean = ctx.empty((t, c, d), self.dtype) if mean else None
         dvar = ctx.empty((t, d), self.dtype) if var else None
+        xt = self._scaled(xt)
         ctx.call_on("smn_fit_predict_grad", self._handle, xt.ptr, t, d, None if dmean is None else dmean.ptr,
                     None if dvar is None else dvar.ptr)
+        s = getattr(self.kernel_fn, "input_scales", None)
+        if s is not None:              # per unit of the inputs as handed in: d/dx = s o d/d(s o x)
+            sv = np.ascontiguousarray(s, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
+            for g, rows in ((dmean, t * c), (dvar, t)):
+                if g is not None:
+                    ctx.call("smn_scale_columns", g.dcode, g.ptr, rows, d, d, sv, g.ptr, d)
         nbytes = C.c_size_t()
         ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
         self.nbytes = int(nbytes.value)

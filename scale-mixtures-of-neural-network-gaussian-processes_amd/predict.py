@@ -52,6 +52,15 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
                   ctx, dtype=x.dtype)
     n = x.shape[0]
     c = y.shape[1] if len(y.shape) > 1 else 1
+    kept = {}
+
+    def scaled_train():
+        """The training inputs as a KernelFn's fused entries see them (its input scales applied once), or x itself."""
+        if getattr(kernel_fn, "input_scales", None) is None or len(x.shape) != 2:
+            return x
+        if "xs" not in kept:
+            kept["xs"] = kernel_fn.scaled(x, ctx)
+        return kept["xs"]
 
     def predict_fn(t=None, x_test=None, get="nngp", compute_cov=True):
         if t is not None:
@@ -75,7 +84,10 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, diag_reg=0.0, dia
         rel, ab = (0.0, float(diag_reg)) if diag_reg_absolute_scale else (float(diag_reg), 0.0)
         if isinstance(kernel_fn, KernelFn):
             net, act, L, w, b, lw = kernel_fn.with_cov(mode).params       # "ntk": net carries SMN_NET_NTK
-            ctx.call("smn_spr_predict", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], xt.ptr, tt, xt.shape[1],
+            xs = scaled_train()                                            # (input scales: the fused entry sees s o x)
+            if xs is not x:
+                xt = kernel_fn.scaled(xt, ctx)
+            ctx.call("smn_spr_predict", x.dcode, net, act, L, w, b, lw, xs.ptr, n, x.shape[1], xt.ptr, tt, xt.shape[1],
                      x.shape[1], y.ptr, c, rel, ab, mean.ptr, cov.ptr, tt, quad, C.byref(logdet), C.byref(info))
         else:  # any other kernel_fn: build the joint kernel with it, then the same factorisation
             xa = np.concatenate([np.asarray(x), np.asarray(xt)], axis=0)

@@ -7,6 +7,8 @@ Nothing numerical happens here: a kernel function built by `nt_kernels` is a han
 """
 from __future__ import annotations
 
+import numpy as np
+
 from ..nt_kernels import CnnKernelFn, KernelFn
 from ..predict import gradient_descent_mse_ensemble
 from .base import ConstraintTrainVar, Module
@@ -19,15 +21,26 @@ _TRAINABLES = ("w_std", "b_std", "last_w_std")
 
 class NNGPKernel(Module):
     """`get_kernel_fn(w_std, b_std, last_w_std) -> kernel_fn` is any of the `nt_kernels.get_*_kernel` factories with the
-    architecture arguments bound (experiments/regression/train.py:128-134)."""
+    architecture arguments bound (experiments/regression/train.py:128-134).
 
-    def __init__(self, get_kernel_fn, w_std: float = 1.0, b_std: float = 1.0, last_w_std: float = 1.0):
+    input_scales (default None): a sequence of d positive numbers, one per input feature -- automatic relevance
+    determination.  The covariance function becomes that of the scaled inputs, k(x, x') = K(s o x, s o x'), i.e. a per-feature
+    prior variance of the first-layer weights, and s is ONE more trainable, the vector variable `input_scales` (positive(),
+    stored softplus-inverse).  The MLP / dense-ResNet factories only: a conv kernel or a foreign callable raises
+    NotImplementedError in get_kernel_fn, before any device call.  None registers nothing: vars() is what it was."""
+
+    def __init__(self, get_kernel_fn, w_std: float = 1.0, b_std: float = 1.0, last_w_std: float = 1.0, input_scales=None):
         super().__init__()
         if not callable(get_kernel_fn):
             raise TypeError("get_kernel_fn must be callable: (w_std, b_std, last_w_std) -> kernel_fn")
         self._get_kernel_fn = get_kernel_fn
         for name, value in zip(_TRAINABLES, (w_std, b_std, last_w_std)):
             setattr(self, name, ConstraintTrainVar(value, constraint=positive()))   # stored softplus-inverse
+        if input_scales is not None:
+            s = np.array(input_scales, dtype=np.float64).reshape(-1)
+            if s.size == 0 or not np.all(np.isfinite(s)) or not np.all(s > 0.0):
+                raise ValueError("input_scales must be a non-empty sequence of positive finite numbers")
+            self.input_scales = ConstraintTrainVar(s, constraint=positive())
 
     # -- current (constrained) values -------------------------------------------------------------------------
     def get_params(self):
@@ -36,8 +49,20 @@ class NNGPKernel(Module):
 
     def get_kernel_fn(self):
         """A kernel function at the current hyper-parameters; rebuilt on every call because the trainables may have
-        moved since the last one (spax/kernels.py:37-41)."""
-        return self._get_kernel_fn(*self.get_params())
+        moved since the last one (spax/kernels.py:37-41).  With input scales, their current values ride on it."""
+        kernel_fn = self._get_kernel_fn(*self.get_params())
+        s = self.get_input_scales()
+        if s is None:
+            return kernel_fn
+        if not isinstance(kernel_fn, KernelFn):
+            raise NotImplementedError("input_scales need an MLP / dense-ResNet kernel function (get_mlp_kernel, "
+                                      "get_dense_resnet_kernel); got %s" % type(kernel_fn).__name__)
+        return kernel_fn.with_input_scales(s)
+
+    def get_input_scales(self):
+        """The current (constrained) input scales as a float64 vector, or None."""
+        var = getattr(self, "input_scales", None)
+        return None if var is None else np.asarray(var.constraint(var.value), dtype=np.float64).reshape(-1)
 
     # -- the two uses the model makes of a kernel function ----------------------------------------------------
     def K(self, kernel_fn, x, x2=None):

@@ -61,6 +61,28 @@ def grad_route(kernel_fn, likelihood):
                               "a Gaussian or Student-t likelihood; use train.value_and_grad_fd")
 
 
+def _seen(kernel_fn, x):
+    """x as the fused entries must be handed it: multiplied by the kernel function's input scales (KernelFn.scaled), or x
+    itself when there are none."""
+    if getattr(kernel_fn, "input_scales", None) is None:
+        return x
+    return kernel_fn.scaled(x, x.ctx)
+
+
+def _check_scales_length(kernel, x):
+    """ValueError when a kernel's input scales do not have one entry per input feature of x [N, d]."""
+    s = kernel.get_input_scales() if hasattr(kernel, "get_input_scales") else None
+    shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    if s is not None and (len(shape) != 2 or s.shape[0] != shape[1]):
+        raise ValueError("input_scales has %d entries for inputs of shape %s: one per feature of x [N, d] is needed"
+                         % (s.shape[0], shape))
+
+
+def _scales_key(kernel_fn):
+    s = getattr(kernel_fn, "input_scales", None)
+    return None if s is None else tuple(float(v) for v in s)
+
+
 def _raw_grads(model, d_con, divisor=1.0):
     """{variable name: d / d RAW value} from d_con = {key: (variable, d / d constrained value)}: the chain rule through each
     variable's constraint, over `divisor` (-N turns a log-pdf into the exact models' loss)."""
@@ -123,7 +145,11 @@ class _LooMixin:
         (d Lambda = sum_ij G_ij dK~_ij; one N^3 product on the MFMA tile engine) and the tangent pass of loss_and_grad over G
         (smn_spr_loo_grad / smn_spr_cnn_loo_grad).  Follows grad_route: the conv ResNet, a likelihood without lml_params and
         images above 1024 pixels raise NotImplementedError."""
-        grad_route(self.kernel.get_kernel_fn(), self.likelihood)   # what has no analytic gradient raises before anything else
+        kernel_fn = self.kernel.get_kernel_fn()
+        grad_route(kernel_fn, self.likelihood)   # what has no analytic gradient raises before anything else
+        if getattr(kernel_fn, "input_scales", None) is not None:
+            raise NotImplementedError("loo_loss_and_grad under input scales is not implemented (loss_and_grad is; loo_loss and "
+                                      "loo_predict work)")
         n, c = self._loo_shape()
         lam, info = C.c_double(), C.c_int()
         terms, dhead = (C.c_double * 4)(), (C.c_double * 2)()
@@ -226,6 +252,15 @@ class _ExactGP(_DrawsMixin, _LooMixin, Module):
             self._y64 = ctx.to_device(self.y_host)
         return self._x64, self._y64
 
+    def _f64_seen(self, kernel_fn, x64):
+        """The fp64 copy of the training inputs as the kernel sees them.  Under input scales this is the upcast of the inputs
+        scaled in the STORAGE dtype (what every other route is handed), not x64 scaled in fp64: the model stays the model of
+        x * s.astype(dtype)."""
+        if getattr(kernel_fn, "input_scales", None) is None:
+            return x64
+        xs = _seen(kernel_fn, self.x_data)
+        return xs if xs.dtype == np.float64 else xs.ctx.to_device(xs.numpy().astype(np.float64))
+
     def _call_grad_entry(self, kind, c, outs):
         """One fused entry on the training data, "smn_spr_" + kind (MLP / dense ResNet) or "smn_spr_cnn_" + kind
         (get_cnn_kernel) as grad_route decides: (x, y, [c unless None,] eps, df, scale, *outs).  Returns (df, scale)."""
@@ -262,8 +297,69 @@ class _ExactGP(_DrawsMixin, _LooMixin, Module):
             owners.update(a=self.likelihood.a, b=self.likelihood.b)
         return _raw_grads(self, {key: (owners[key], g) for key, g in d_con.items()}, divisor)
 
+    def _inputs_entry(self, want_gx, want_feat):
+        """smn_spr_loss_grad_inputs on the training inputs as the kernel sees them: (kernel_fn, x~, quad, logdet, info, terms,
+        gx [N, d] device array = d log p / d x~ or None, feat [d] = sum_n gx o x~ or None, df, scale)."""
+        kernel_fn = self.kernel.get_kernel_fn()
+        if grad_route(kernel_fn, self.likelihood) != "smn_spr_loss_grad":
+            raise NotImplementedError("gradients in the inputs need an MLP / dense-ResNet KernelFn")
+        n, c = self._loo_shape()
+        x = _seen(kernel_fn, self.x_data)
+        ctx, d = x.ctx, x.shape[1]
+        df, scale = self.likelihood.lml_params()
+        quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
+        terms = (C.c_double * 4)()
+        gx = ctx.empty((n, d), x.dtype) if want_gx else None
+        feat = np.zeros(d) if want_feat else None
+        ctx.call("smn_spr_loss_grad_inputs", x.dcode, *kernel_fn.params, x.ptr, n, d, d, self.y_data.ptr, c, self.eps.safe_value,
+                 df, scale, C.byref(quad), None, C.byref(logdet), C.byref(info), terms, gx.ptr if want_gx else None, d,
+                 feat.ctypes.data_as(C.POINTER(C.c_double)) if want_feat else None)
+        return kernel_fn, x, quad.value, logdet.value, info.value, terms, gx, feat, df, scale
+
+    def _lml_loss_and_grad_scaled(self):
+        """loss_and_grad under input scales: the scalar entries as without them (on s o x), plus `input_scales`, a length-d
+        array of d loss / d RAW value: d log p / d s_j = feat_j / s_j (csrc/input_grad_sym.hip), over -N, through the
+        constraint."""
+        n, c = self._loo_shape()
+        kernel_fn, _, quad, logdet, info, terms, _, feat, df, scale = self._inputs_entry(False, True)
+        var = self.kernel.input_scales
+        name = {id(v): k for k, v in self.vars().items()}[id(var)]
+        if info != 0:
+            loss, grads = self._nan_grads()
+            grads[name] = np.full(var.value.shape, np.nan)
+            return loss, grads
+        student = df > 0.0
+        lp, dlp = lml_value_and_grads(terms, quad, c * logdet, n * c, df, scale,
+                                      self.likelihood.a.safe_value if student else None,
+                                      self.likelihood.b.safe_value if student else None)
+        grads = self._raw_grads(dlp, -n)
+        grads[name] = (feat / kernel_fn.input_scales) / -n * var.constraint.grad(var.value)
+        return -lp / n, grads
+
+    def loss_input_grad(self):
+        """(loss, d loss / d x): the gradient of loss() in the training inputs as an [N, d] device array, per unit of the inputs
+        as handed in (under input scales: s o the gradient in the scaled inputs) -- learned or inducing inputs, dataset
+        distillation.  One smn_spr_loss_grad_inputs call: loss_and_grad's pipeline followed by the two-sided tangent pass and
+        one N^2 d product on the tile engine (csrc/input_grad_sym.hip).  MLP / dense-ResNet kernels, Gaussian or Student-t
+        likelihood; a matrix that is not positive definite gives NaN for both."""
+        n, c = self._loo_shape()
+        kernel_fn, x, quad, logdet, info, terms, gx, _, df, scale = self._inputs_entry(True, False)
+        ctx, d = x.ctx, x.shape[1]
+        if info != 0:
+            return float("nan"), ctx.to_device(np.full((n, d), np.nan, dtype=x.dtype))
+        student = df > 0.0
+        lp, _ = lml_value_and_grads(terms, quad, c * logdet, n * c, df, scale,
+                                    self.likelihood.a.safe_value if student else None,
+                                    self.likelihood.b.safe_value if student else None)
+        s = kernel_fn.input_scales
+        fac = np.ascontiguousarray((np.ones(d) if s is None else s) / -n, dtype=np.float64)   # loss = -log p / N
+        ctx.call("smn_scale_columns", gx.dcode, gx.ptr, n, d, d, fac.ctypes.data_as(C.POINTER(C.c_double)), gx.ptr, d)
+        return -lp / n, gx
+
     def _lml_loss_and_grad(self):
         """loss_and_grad of both models: the head in dimension N C with log-determinant C logdet K~."""
+        if getattr(self.kernel, "input_scales", None) is not None:
+            return self._lml_loss_and_grad_scaled()
         n, c = self._loo_shape()
         quad, logdet, info = C.c_double(), C.c_double(), C.c_int()
         terms = (C.c_double * 4)()
@@ -284,6 +380,7 @@ class _ExactGP(_DrawsMixin, _LooMixin, Module):
 class SPR(_ExactGP):
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, eps: float = 1e-6):
         super().__init__()
+        _check_scales_length(kernel, x_data)         # (before anything touches a device)
         self.kernel = kernel
         self.likelihood = likelihood
         self.x_data = as_device(x_data)              # resident in HBM for the life of the model
@@ -302,11 +399,12 @@ class SPR(_ExactGP):
         second call costs the fp32 posterior alone.  (Measured at N = 16384: this fp64 build + factorisation is 44 ms
         against 29 ms for the posterior, and running the two concurrently on two contexts buys 3 % -- both are bound by the
         matrix pipes, not by latency; profiles/r04_two_context_probe.txt.)"""
-        key = (tuple(kernel_fn.params), float(scale))
+        key = (tuple(kernel_fn.params), float(scale), _scales_key(kernel_fn))
         hit = getattr(self, "_quad64_cache", None)
         if hit is not None and hit[0] == key:
             return hit[1]
         xd, yd = self._f64_data()
+        xd = self._f64_seen(kernel_fn, xd)
         net, act, L, w, b, lw = kernel_fn.params
         quad, info = C.c_double(), C.c_int()
         xd.ctx.call("smn_spr_loss", xd.dcode, net, act, L, w, b, lw, xd.ptr, xd.shape[0], xd.shape[1],
@@ -330,7 +428,7 @@ class SPR(_ExactGP):
         if isinstance(kernel_fn, KernelFn) and hasattr(self.likelihood, "lml_params"):
             # fused: build K(X,X)+eps I in the factorisation workspace, factor, carry y through
             df, scale = self.likelihood.lml_params()
-            x, ctx = self.x_data, self.x_data.ctx
+            x, ctx = _seen(kernel_fn, self.x_data), self.x_data.ctx
             net, act, L, w, b, lw = kernel_fn.params
             lp, info = C.c_double(), C.c_int()
             ctx.call("smn_spr_loss", x.dcode, net, act, L, w, b, lw, x.ptr, x.shape[0], x.shape[1], x.shape[1],
@@ -349,7 +447,10 @@ class SPR(_ExactGP):
         dK/d(w_std, b_std, last_w_std): over X X^T / d for MLP / dense-ResNet kernels (csrc/grad.hip), over the image
         pairs for get_cnn_kernel (csrc/cnn_grad.hip, images of up to 1024 pixels).  The (a, b) derivatives of the
         Student-t head and the softplus chain rule are closed forms on the host (lml_value_and_grads).  Anything else --
-        the conv ResNet, a likelihood without lml_params, larger images -- raises NotImplementedError."""
+        the conv ResNet, a likelihood without lml_params, larger images -- raises NotImplementedError.
+        A kernel with input scales (NNGPKernel(..., input_scales=...)) adds the entry `input_scales`, a length-d array, from one
+        smn_spr_loss_grad_inputs call on the scaled inputs (csrc/input_grad_sym.hip); the scalar entries are computed as without
+        scales."""
         return self._lml_loss_and_grad()
 
     # ---- spax/models.py:100-120
@@ -409,6 +510,7 @@ class MultiSPR(_ExactGP):
 
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean=0., y_std=1., *, eps: float = 1e-6):
         super().__init__()
+        _check_scales_length(kernel, x_data)
         self.kernel = kernel
         self.likelihood = likelihood
         self.x_data = as_device(x_data)
@@ -447,13 +549,15 @@ class MultiSPR(_ExactGP):
             raise NotImplementedError("MultiSPR needs a Gaussian or Student-t likelihood")
         return self.likelihood.lml_params()
 
-    def _joint_lml(self, kernel_fn, x, y, eps, df, scale):
+    def _joint_lml(self, kernel_fn, x, y, eps, df, scale, seen=False):
         """(log-pdf, total quadratic form, info) of y [N,C] under K(x,x) + eps I: the fused build for the MLP family, the
-        conv build followed by smn_lml_multi for the conv kernels."""
+        conv build followed by smn_lml_multi for the conv kernels.  seen: x already carries the kernel function's input
+        scales."""
         ctx, n, c = x.ctx, self.num_data, self.num_outputs
         lp, quad, info = C.c_double(), C.c_double(), C.c_int()
         if isinstance(kernel_fn, KernelFn):
             net, act, L, w, b, lw = kernel_fn.params
+            x = x if seen else _seen(kernel_fn, x)
             ctx.call("smn_spr_loss_multi", x.dcode, net, act, L, w, b, lw, x.ptr, n, x.shape[1], x.shape[1], y.ptr, c,
                      eps, df, scale, C.byref(lp), C.byref(quad), None, None, C.byref(info))
         elif isinstance(kernel_fn, CnnKernelFn):
@@ -483,12 +587,13 @@ class MultiSPR(_ExactGP):
     def _student_quad_f64(self, kernel_fn, scale):
         """tr(Y^T (scale K + 1e-6 I)^-1 Y) with K WITHOUT eps, always in fp64 (SPR._student_quad_f64 for C columns); the
         value of the last parameter setting is kept."""
-        key = (type(kernel_fn).__name__, getattr(kernel_fn, "entry", None), tuple(kernel_fn.params), float(scale))
+        key = (type(kernel_fn).__name__, getattr(kernel_fn, "entry", None), tuple(kernel_fn.params), float(scale),
+               _scales_key(kernel_fn))
         hit = getattr(self, "_quad64_cache", None)
         if hit is not None and hit[0] == key:
             return hit[1]
         xd, yd = self._f64_data()
-        _, quad, info = self._joint_lml(kernel_fn, xd, yd, 1e-6 / scale, 0.0, 1.0)
+        _, quad, info = self._joint_lml(kernel_fn, self._f64_seen(kernel_fn, xd), yd, 1e-6 / scale, 0.0, 1.0, seen=True)
         val = float("nan") if info else quad / scale
         self._quad64_cache = (key, val)
         return val

@@ -34,6 +34,13 @@ def _net_code(network, covariance):
     return _NET[network] | (_lib.NET_NTK if covariance == "ntk" else 0)
 
 
+def _no_scales(input_scales):
+    """The batched entries have no input-scale (ARD) form: refused before any device call."""
+    if input_scales is not None:
+        raise NotImplementedError("the batched sweeps do not take input scales (automatic relevance determination): scale the "
+                                  "inputs yourself, or use SPR / MultiSPR with NNGPKernel(..., input_scales=...)")
+
+
 def _batched(ctx, name, *args):
     try:
         ctx.call(name, *args)
@@ -54,11 +61,13 @@ def _darr(values):
 
 
 def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0, scale=1.0,
-               covariance="nngp"):
+               covariance="nngp", input_scales=None):
     """G x SPR.loss on one data set in one batched pass (smn_spr_loss_batch).  w_std, b_std, last_w_std, eps, df, scale:
     scalars or sequences of one common length G.  x, y: DeviceArrays of ctx (float32 or float64, the compute type).
     covariance="ntk" (here and in the two functions below) raises NotImplementedError: the batched entries are NNGP-only.
+    input_scales (here and in the functions below) must stay None: NotImplementedError otherwise.
     Returns (logpdf[G], quad[G], logdet[G], info[G]) as NumPy arrays; logpdf is NaN where info != 0."""
+    _no_scales(input_scales)
     g = max(np.size(v) for v in (w_std, b_std, last_w_std, eps, df, scale))
     cols = [_darr(np.broadcast_to(np.asarray(v, dtype=np.float64), (g,))) for v in (w_std, b_std, last_w_std, eps, df, scale)]
     n, d = x.shape
@@ -72,12 +81,13 @@ def loss_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_
 
 
 def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0, eps, df=0.0,
-                        scale=1.0, covariance="nngp"):
+                        scale=1.0, covariance="nngp", input_scales=None):
     """G x SPR.loss_and_grad's device call on one data set in one batched pass (smn_spr_loss_grad_batch): multi-start
     training (train.build_multistart_step) and gradient refinement of the cells of a grid search.  Arguments as for
     loss_batch (MLP and dense-ResNet kernels).  Returns (logpdf[G], quad[G], logdet[G], info[G], terms[G, 4]) as NumPy
     arrays: terms[g] = sum G dK~/d(w_std, b_std, last_w_std, eps) exactly as smn_spr_loss_grad returns them for problem g;
     logpdf from quad and logdet by the host arithmetic of SPR.loss_and_grad; NaN where info != 0."""
+    _no_scales(input_scales)
     from .spax.models import lml_value_and_grads
     g = max(np.size(v) for v in (w_std, b_std, last_w_std, eps, df, scale))
     cols = [_darr(np.broadcast_to(np.asarray(v, dtype=np.float64), (g,))) for v in (w_std, b_std, last_w_std, eps, df, scale)]
@@ -98,10 +108,11 @@ def loss_and_grad_batch(ctx, x, y, *, network="mlp", num_hiddens=4, activation="
 
 
 def predict_batch(ctx, x, y, x_test, *, network="mlp", num_hiddens=4, activation="relu", w_std, b_std, last_w_std=1.0,
-                  diag_reg, full_cov=False, on_device=False, covariance="nngp"):
+                  diag_reg, full_cov=False, on_device=False, covariance="nngp", input_scales=None):
     """G x NNGPKernel.predict (relative ridge diag_reg, spax/kernels.py:29-32) on one data set in one batched pass
     (smn_spr_predict_batch).  y: DeviceArray [n, c].  Returns (mean [G,t,c], var [G,t] or cov [G,t,t], info[G]); the first
     two as DeviceArrays when on_device."""
+    _no_scales(input_scales)
     g = max(np.size(v) for v in (w_std, b_std, last_w_std, diag_reg))
     cols = [_darr(np.broadcast_to(np.asarray(v, dtype=np.float64), (g,))) for v in (w_std, b_std, last_w_std, diag_reg)]
     n, d = x.shape
@@ -119,8 +130,9 @@ def predict_batch(ctx, x, y, x_test, *, network="mlp", num_hiddens=4, activation
 def find_grid(x_train, y_train, x_test, y_test, y_mean=0.0, y_std=1.0, *, network="mlp", num_hiddens=4,
               activation="relu", w_std_list=(1.0, 1.4, 2.0), b_std_list=(0.0, 0.3, 1.0),
               eps_list=(1e-6, 1e-4, 1e-2), alpha_list=(1.0, 2.0, 3.0), beta_list=(1.0, 2.0, 3.0),
-              num_samples=1000, ctx=None):
+              num_samples=1000, ctx=None, input_scales=None):
     """Returns dict(gnll[i,j,k], tnll[i,j,k,a,b], best_gaussian, best_student) — the tables find.py logs."""
+    _no_scales(input_scales)
     from scipy import stats as scipy_stats       # the Burr-XII draws, as in the reference's find.py
 
     if network not in _NET:

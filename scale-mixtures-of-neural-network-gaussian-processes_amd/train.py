@@ -37,10 +37,27 @@ def value_and_grad(model, variables=None):
 
 
 def value_and_grad_fd(loss_fn, variables, h=1e-4):
-    """(loss, {name: dloss/draw}) by central differences on the raw (unconstrained) values."""
+    """(loss, {name: dloss/draw}) by central differences on the raw (unconstrained) values; an array-valued variable
+    (input_scales) component by component: 2 loss evaluations each."""
     value = float(loss_fn())
     grads = {}
     for name, var in variables.items():
+        if np.ndim(var.value) > 0:
+            base = np.array(var.value, dtype=np.float64)
+            g = np.empty_like(base)
+            for idx in np.ndindex(base.shape):
+                step = h * max(1.0, abs(base[idx]))
+                moved = base.copy()
+                moved[idx] = base[idx] + step
+                var.assign(moved)
+                up = float(loss_fn())
+                moved[idx] = base[idx] - step
+                var.assign(moved)
+                dn = float(loss_fn())
+                g[idx] = (up - dn) / (2.0 * step)
+            var.assign(base)
+            grads[name] = g
+            continue
         raw = float(var.value)
         step = h * max(1.0, abs(raw))
         var.assign(raw + step)
@@ -65,6 +82,15 @@ class Adam:
         self.t += 1
         lr_t = lr * math.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t)
         for k, g in grads.items():
+            if np.ndim(g) > 0:                    # an array-valued variable: element-wise moments, the arithmetic below
+                g = np.asarray(g, dtype=np.float64)
+                ok = np.isfinite(g)
+                g0 = np.where(ok, g, 0.0)
+                self.m[k] = np.where(ok, self.b1 * self.m[k] + (1 - self.b1) * g0, self.m[k])
+                self.v[k] = np.where(ok, self.b2 * self.v[k] + (1 - self.b2) * g0 * g0, self.v[k])
+                raw = np.asarray(self.vars[k].value, dtype=np.float64)
+                self.vars[k].assign(np.where(ok, raw - lr_t * self.m[k] / (np.sqrt(self.v[k]) + self.eps), raw))
+                continue
             if not np.isfinite(g):
                 continue
             self.m[k] = self.b1 * self.m[k] + (1 - self.b1) * g
@@ -150,6 +176,9 @@ class MultiStartStep:
     def __init__(self, model, starts, optimizer=None):
         from . import _lib
         from .spax.models import grad_route
+        if getattr(model.kernel, "input_scales", None) is not None:
+            raise NotImplementedError("multi-start training under input scales is not implemented: the batched gradient entry "
+                                      "has no input-scale form; use build_train_step per start")
         kernel_fn = model.kernel.get_kernel_fn()
         if grad_route(kernel_fn, model.likelihood) != "smn_spr_loss_grad":
             raise NotImplementedError("multi-start training supports the MLP and dense-ResNet kernels only")
