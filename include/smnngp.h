@@ -325,6 +325,15 @@ int smn_spr_predict(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
  *                               smn_fit_info): F_1, F_2, their seeded product and U, 4 x round_up(min(capacity, t), 128) x n_pad
  *                               elements -- 0.54 GB in fp32 at n = 16384, capacity 2048.  Sums in fp64 and in a fixed order: the same arguments give the same bits, and a
  *                               row's values do not depend on the rows it shares a call with.  info != 0 -> NaN outputs, SMN_OK.
+ *   smn_fit_weights             either kind of state: the solve behind those gradients for a cross kernel of the caller's, u_d
+ *                               [t, ldu >= n] = K_td K~^-1 from k_td_d [t, ldk >= n] (the two forward sweeps, on L and on L' =
+ *                               J L^T J; 1 <= t <= capacity per call) and / or alpha_d [n, c] row-major = K~^-1 Y; either output
+ *                               may be NULL.  With smn_kernel_cnn_input_grad_cross these are jax.grad of the predictive of
+ *                               experiments/nt_kernels.py:34-45 with respect to the test images.  The first call adds L' and
+ *                               alpha to the state (smn_fit_info's bytes grow; a matrix-form state adds no X^T);
+ *                               smn_fit_reserve, the appends and smn_fit_remove drop and rebuild them as for
+ *                               smn_fit_predict_grad; nothing smn_fit_predict or smn_fit_apply reads changes.  info != 0 ->
+ *                               NaN outputs, SMN_OK.  No synchronisation.
  *   smn_fit_info                sizes and the bytes the state owns (NULL outputs are skipped).
  *   smn_fit_destroy             synchronises the context's stream and frees the state.
  * Not positive definite: *info_h = the failing pivot, the state is still returned (SMN_OK) and every prediction from it is NaN.
@@ -342,6 +351,7 @@ int smn_fit_predict(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, voi
 int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, const void* ktt_diag_d, const void* k_tt_d, int64_t ldtt,
                   void* mean_d, void* var_d, void* cov_d, int64_t ldcov);
 int smn_fit_predict_grad(smn_fit* fit, const void* xt_d, int64_t t, int64_t ldxt, void* dmean_d, void* dvar_d);
+int smn_fit_weights(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, void* u_d, int64_t ldu, void* alpha_d);
 int smn_fit_info(smn_fit* fit, int64_t* n, int64_t* c, int64_t* capacity, size_t* bytes);
 int smn_fit_destroy(smn_fit* fit);
 
@@ -771,6 +781,35 @@ int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens,
                               double w_std, double b_std, double last_w_std,
                               const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,
                               const void* gbar_d, int64_t ldg, int64_t n_grad, void* gx_d);
+
+/* ---- the conv-NNGP kernel differentiated in its first argument for many seeds at once: saliency maps of a fitted posterior
+ *      (jax.grad of the predictive of experiments/nt_kernels.py:34-45 with respect to the test images) ----
+ * smn_kernel_cnn_input_grad_cross: for K = smn_kernel_cnn, rows x1_d [n1,H,W,C] and partners x2_d [n2,H,W,C], which do not move,
+ *     gmean_d [n1, c, H, W, C]:  gmean[r, k] = sum_j alpha[j, k] dK(x1_r, x2_j)/dx1_r     (alpha_d [n2, c] row-major: column seeds,
+ *                                                                                          shared by all rows)
+ *     gvar_d  [n1, H, W, C]:     gvar[r] = gdiag[r] dK(x1_r, x1_r)/dx1_r + sum_j gbar[r, j] dK(x1_r, x2_j)/dx1_r
+ *   with K(x, x) the exact per-image diagonal; gbar_d [n1, ldg >= n2], gdiag_d [n1]; gdiag_d == NULL: no diagonal term, gbar_d ==
+ *   NULL: no cross term.  Either output may be NULL (its seeds are then not run); gmean_d needs alpha_d, gvar_d needs gbar_d or
+ *   gdiag_d; 1 <= c <= 48, c is ignored (and may be 0) when alpha_d is NULL.  A fitted posterior's gradients are alpha = K~^-1 Y,
+ *   gbar = -2 K_td K~^-1 (smn_fit_weights) and gdiag = 1.
+ *   The reverse sweep is linear in its seed: a pair runs ONE forward and ONE reverse sweep (from the unit seed, without the
+ *   mirror factor 2 of the symmetric entry) for all c + 1 seeds, and only the n1 x n2 cross pairs are visited -- against
+ *   (n1 + n2)^2 pairs once per seed through smn_kernel_cnn_input_grad on the union.  Per-element arithmetic in `dtype`, the sums
+ *   over partners in fp64 and in a fixed order (no floating-point atomics: two calls give the same bits).  A row's partner list
+ *   is cut into slices by n1, n2, the pixels-per-lane form and the device alone; the sums ([seeds][rows x slices][L + C][64 NP]
+ *   doubles) are capped at min(256 MB, smn_debug_batch_bytes) by running the seeds in groups -- one more pass over the pairs
+ *   each -- and, beyond that, the rows in batches: the bits depend neither on the budget nor on which outputs are asked for
+ *   (a mean-only or variance-only call gives the bits of the joint call).  ROWS COMPUTED ALONE NEED NOT CARRY THE BITS OF THE
+ *   SAME ROWS IN A LARGER CALL: n1 enters the cut.
+ *   fp32 / fp64, relu / erf, num_hiddens >= 0, H*W <= SMN_CNN_GRAD_MAX_PIXELS at any aspect ratio (SMN_ENOTSUP above, naming the
+ *   limit); zero-variance pixels and an x1 image that also occurs in x2 give finite values, as in the symmetric entry.
+ *   SMN_EINVAL by name: x1_d / x2_d NULL, both outputs NULL, gmean_d without alpha_d, gvar_d without gbar_d and gdiag_d, n1 < 1,
+ *   n2 < 1, ldg < n2; SMN_ENOTSUP: c > 48.  A refused call writes nothing.  Synchronises. */
+int smn_kernel_cnn_input_grad_cross(smn_ctx* ctx, int dtype, int act, int num_hiddens,
+                                    double w_std, double b_std, double last_w_std,
+                                    const void* x1_d, int64_t n1, const void* x2_d, int64_t n2, int64_t H, int64_t W, int64_t C,
+                                    const void* alpha_d, int64_t c, const void* gbar_d, int64_t ldg, const void* gdiag_d,
+                                    void* gmean_d, void* gvar_d);
 
 /* ---- the MLP / dense-ResNet kernels differentiated in their first argument (experiments/nt_kernels.py:21-31, 83-103 under
  *      jax.grad with respect to x1: sensitivities, acquisition ascent, saliency) ----

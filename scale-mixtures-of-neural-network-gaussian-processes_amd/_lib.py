@@ -99,6 +99,8 @@ PROTOTYPES = {
     "smn_spr_loss_grad_batch": [_vp, _i, _i, _i, _i, _i, _pd, _pd, _pd, _vp, _i64, _i64, _i64, _vp, _pd, _pd, _pd, _pd, _pd, _pi, _pd],
     "smn_kernel_cnn_grad_terms": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _d, _pd],
     "smn_kernel_cnn_input_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp],
+    "smn_kernel_cnn_input_grad_cross": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
+                                        _vp, _vp],
     "smn_spr_cnn_loss_grad": [_vp, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _vp, _d, _d, _d, _pd, _pd, _pi, _pd],
     "smn_lml_multi": [_vp, _i, _vp, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pd, _pi],
     "smn_spr_loss_multi": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _d, _d, _d, _pd, _pd, _pd, _pd, _pi],
@@ -144,6 +146,7 @@ PROTOTYPES = {
     "smn_fit_predict": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64],
     "smn_fit_apply": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64],
     "smn_fit_predict_grad": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "smn_fit_weights": [_vp, _vp, _i64, _i64, _vp, _i64, _vp],
     "smn_kernel_mlp_input_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64],
     "smn_scale_columns": [_vp, _i, _vp, _i64, _i64, _i64, _pd, _vp, _i64],
     "smn_kernel_mlp_input_grad_sym": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _d, _vp, _i64, _pd],

@@ -26,6 +26,9 @@
 // lane + 64 i from a wave-uniform base (guarded accesses at computed offsets made the 16-pixel forms spill).  Memory beyond
 // inputs and outputs: the per-image tables (n L 64 NP), one forward slab per resident wave, one sum block per slice -- nothing
 // grows with n^2 HW.  DESIGN.md section 6d.
+//
+// The cross, multi-seed form for a fitted posterior's saliency maps (rows x1 against fixed partners x2, all seeds from one
+// reverse sweep per pair) follows the symmetric one below and shares its per-image kernels; DESIGN.md section 6m.
 #include <algorithm>
 #include <cmath>
 
@@ -173,22 +176,19 @@ __global__ void __launch_bounds__(256, cig_occ(NP)) cig_pair_kernel(CigArgs<T> a
   }
 }
 
-// Second stage and the per-image pass, one workgroup per differentiated image: the slices of the pair pass added in slice
-// order (bitwise reproducible), the reverse chain of the exact diagonal through two padded fp64 maps, the result in T.
+// Second stage and the per-image pass of one differentiated image by one workgroup: the slices of the pair pass (`mine`, one
+// block of L + C rows of HWP sums per slice) added in slice order (bitwise reproducible), the reverse chain of the exact
+// diagonal from r0 through two padded fp64 maps, the result in T.  dq_img [L][HW], x_img and gx_img [HW][C].
 template <typename T>
-__global__ void __launch_bounds__(256) cig_finish_kernel(const T* __restrict__ x, ConvProg p, const T* __restrict__ g, int64_t ldg,
-                                                         const double* __restrict__ dq_tab, const double* __restrict__ part,
-                                                         int nsplit, int HWP, T* __restrict__ gx) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void cig_finish_image(const T* __restrict__ x_img, const ConvProg& p, double r0,
+                                                 const double* __restrict__ dq_img, const double* __restrict__ mine, int nsplit,
+                                                 int HWP, T* __restrict__ gx_img, char* smem) {
   const int H = p.H, W = p.W, HW = H * W, PW = W + 2, PSZ = (H + 2) * PW, L = p.layers, C = p.C;
   double* cur = reinterpret_cast<double*>(smem);
   double* nxt = cur + PSZ;
-  const int64_t img = blockIdx.x;
-  const double* mine = part + img * nsplit * (int64_t)(L + C) * HWP;
   const int64_t sstride = (int64_t)(L + C) * HWP;
   for (int i = threadIdx.x; i < 2 * PSZ; i += blockDim.x) cur[i] = 0.0;
   __syncthreads();
-  const double r0 = (double)g[img * ldg + img] * p.lw2 / HW;
   for (int px = threadIdx.x; px < HW; px += blockDim.x) cur[(px / W + 1) * PW + px % W + 1] = r0;
   __syncthreads();
   for (int l = L - 1; l >= 0; --l) {
@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(256) cig_finish_kernel(const T* __restrict__ x
       double qs = 0.0;
       for (int s = 0; s < nsplit; ++s) qs += mine[s * sstride + (int64_t)l * HWP + px];
       const int o = (px / W + 1) * PW + px % W + 1;
-      cur[o] = dq_tab[(img * L + l) * HW + px] * cur[o] + qs;
+      cur[o] = dq_img[l * HW + px] * cur[o] + qs;
     }
     __syncthreads();
     for (int px = threadIdx.x; px < HW; px += blockDim.x) {
@@ -211,8 +211,20 @@ __global__ void __launch_bounds__(256) cig_finish_kernel(const T* __restrict__ x
     double s = 0.0;
     for (int k = 0; k < nsplit; ++k) s += mine[k * sstride + (int64_t)(L + c) * HWP + px];
     const double r = cur[(px / W + 1) * PW + px % W + 1];
-    gx[img * HW * C + e] = (T)(s + 2.0 * (double)x[img * HW * C + e] * r / C);
+    gx_img[e] = (T)(s + 2.0 * (double)x_img[e] * r / C);
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) cig_finish_kernel(const T* __restrict__ x, ConvProg p, const T* __restrict__ g, int64_t ldg,
+                                                         const double* __restrict__ dq_tab, const double* __restrict__ part,
+                                                         int nsplit, int HWP, T* __restrict__ gx) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int HW = p.H * p.W, L = p.layers, C = p.C;
+  const int64_t img = blockIdx.x;
+  const double r0 = (double)g[img * ldg + img] * p.lw2 / HW;
+  cig_finish_image<T>(x + img * HW * C, p, r0, dq_tab + img * L * HW, part + img * nsplit * (int64_t)(L + C) * HWP, nsplit, HWP,
+                      gx + img * HW * C, smem);
 }
 
 template <typename T>
@@ -286,7 +298,261 @@ int cig_run(smn_ctx* ctx, int act, int layers, double w_std, double b_std, doubl
   return SMN_OK;
 }
 
+// ---------------------------------------------------------------- the cross, multi-seed form (smn_kernel_cnn_input_grad_cross)
+// Rows x1 [n1] against partners x2 [n2], which do not move, and S seeds at once: the c columns of alpha (mean seeds, g_s(r, j) =
+// alpha[j, s], shared by all rows) and gbar (the variance seed, g(r, j) = gbar[r, j]).  The reverse sweep is linear in its seed, so
+// a pair runs its forward sweep and ONE reverse sweep from the unit seed lw^2 / HW -- no mirror factor 2: a cross entry occurs
+// once -- which yields khat_0[p] and, per layer, qhat_l[p] = pair factor ra_r^2 khat_l[p]; every seed then takes
+//     qtbar_s^l += g_s qhat_l,      gx_s[p, ch] += g_s khat_0[p] x2_j[p, ch] / C
+// in its own fp64 block of the slice (the product in T, the sum in fp64, in the order of the partner list).  The seed loop is
+// the innermost one, inside groups of four pixels: the four values wait in registers while the seeds' blocks are read, added
+// to and written back, so nothing of size S or NP x S lives in registers.  A seed's value is one wave-uniform load.
+// Only the owner's variance-side term exists.  The per-image pass (cig_finish_image) runs once per row and seed; its r0 =
+// gdiag[r] lw^2 / HW belongs to the variance seed alone.
+// The cut of a row's partner list (nsplit, per) follows n1, n2, the form and the device, nothing else.  The sums are
+// [seeds of the group][rows of the batch x nsplit][L + C][HWP] doubles, capped at min(256 MB, smn_debug_batch_bytes): above
+// that the seeds go in groups -- one more pass over the pairs each, same cut, and a seed's sums never meet another seed's, so
+// the bits do not depend on the budget or on which seeds share a call -- and, when one seed alone is too much, the rows in
+// batches.  Rows computed alone need NOT carry the bits of the same rows in a larger call: n1 enters the cut.
+template <typename T>
+struct CigxArgs {
+  const T* x1; const T* x2;       // [n1][HW][C], [n2][HW][C]
+  const T* ra1; const T* ra2;     // [n1][L][HWP], [n2][L][HWP]
+  const T* alpha; int c;          // mean seeds [n2][c]; c = 0 without them
+  const T* gbar; int64_t ldg;     // variance seed [n1][ldg], or null: zero
+  int64_t row0, n2, items;        // rows [row0, row0 + items / nsplit) of x1; items = rows * nsplit
+  int nsplit; int64_t per;
+  int s0, ns;                     // seeds s0 .. s0 + ns - 1 of the list: s < c the mean seed of output s, s == c the variance seed
+  ConvProg prog;
+  T* fwd;                         // [gridDim.x * 4 waves][L][2][HWP]
+  double* part;                   // [ns][items][L + C][HWP]
+};
+
+template <typename T, int ACT, int NP>
+__global__ void __launch_bounds__(256, cig_occ(NP)) cigx_pair_kernel(CigxArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const ConvProg& p = a.prog;
+  const int HW = p.H * p.W, L = p.layers, C = p.C;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  constexpr int HWP = 64 * NP;
+  WaveMap<T, NP, false> wm(smem, p.H, p.W, lane, wave);
+  auto own = [&](int i) { return wm.own(i); };
+  auto pix = [&](int i) { return wm.pix(i); };
+  const T w2_9 = (T)(p.w2 / 9.0), b2 = (T)p.b2;
+  const T inv_c = (T)(1.0 / C), lw2_hw = (T)(p.lw2 / HW);
+  constexpr int KB = NP < 4 ? NP : 4;
+  const int64_t gw = (int64_t)blockIdx.x * 4 + wave, nw = (int64_t)gridDim.x * 4;
+  const int64_t sstride = a.items * (int64_t)(L + C) * HWP;   // from one seed's blocks to the next seed's
+  T* fwd = a.fwd + gw * (int64_t)(2 * L) * HWP + lane;
+  for (int64_t item = gw; item < a.items; item += nw) {
+    const int64_t r = a.row0 + item / a.nsplit;
+    const int64_t j0 = (item % a.nsplit) * a.per, j1 = min(j0 + a.per, a.n2);
+    double* part = a.part + item * (int64_t)(L + C) * HWP + lane;
+    for (int s = 0; s < a.ns; ++s)
+      for (int f = 0; f < L + C; ++f)
+#pragma unroll
+        for (int i = 0; i < NP; ++i) part[s * sstride + f * HWP + 64 * i] = 0.0;   // by the lane that adds to it below
+    const T* xa = a.x1 + r * HW * C;
+    for (int64_t j = j0; j < j1; ++j) {
+      const T* xb = a.x2 + j * HW * C;
+      auto seed = [&](int s) -> T {
+        const int sid = a.s0 + s;
+        return sid < a.c ? a.alpha[j * a.c + sid] : (a.gbar ? a.gbar[r * a.ldg + j] : T(0));
+      };
+      T k[NP];
+      load_k0<KB, false>(xa, xb, C, inv_c, pix, k);
+#pragma unroll
+      for (int i = 0; i < NP; ++i) k[i] = own(i) ? k[i] : T(0);
+      // forward sweep, as in cig_pair_kernel
+      for (int l = 0; l < L; ++l) {
+        const T* t1 = a.ra1 + (r * L + l) * HWP + lane;
+        const T* t2 = a.ra2 + (j * L + l) * HWP + lane;
+        T* fl = fwd + l * 2 * HWP;
+        wm.box(k);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          const T rr = t1[64 * i] * t2[64 * i];
+          T dA, tq;
+          act_factors<T, ACT>(fma(w2_9, k[i], b2), rr, k[i], dA, tq);
+          fl[64 * i] = dA;
+          fl[HWP + 64 * i] = tq;
+          if (NP > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // one reverse sweep from the unit seed; every seed of the group takes its share of each group of four pixels
+#pragma unroll
+      for (int i = 0; i < NP; ++i) k[i] = own(i) ? lw2_hw : T(0);
+      for (int l = L - 1; l >= 0; --l) {
+        const T* t1 = a.ra1 + (r * L + l) * HWP + lane;
+        const T* fl = fwd + l * 2 * HWP;
+        double* qb = part + l * HWP;
+#pragma unroll
+        for (int i0 = 0; i0 < NP; i0 += KB) {
+          T qh[KB];
+#pragma unroll
+          for (int u = 0; u < KB; ++u) {
+            const int i = i0 + u;
+            const T ra = t1[64 * i];
+            qh[u] = fl[HWP + 64 * i] * (ra * ra) * k[i];
+            k[i] *= fl[64 * i];
+          }
+          for (int s = 0; s < a.ns; ++s) {
+            const T gv = seed(s);
+            double* qs = qb + s * sstride;
+#pragma unroll
+            for (int u = 0; u < KB; ++u) qs[64 * (i0 + u)] += (double)(gv * qh[u]);
+          }
+          if (NP > 4) __builtin_amdgcn_sched_barrier(0);
+        }
+        wm.box(k);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) k[i] = own(i) ? k[i] * w2_9 : T(0);
+      }
+      for (int c = 0; c < C; ++c) {
+        double* gp = part + (L + c) * HWP;
+#pragma unroll
+        for (int i0 = 0; i0 < NP; i0 += KB) {
+          T v[KB];
+#pragma unroll
+          for (int u = 0; u < KB; ++u) v[u] = k[i0 + u] * xb[pix(i0 + u) * C + c] * inv_c;   // k is zero past the image
+          for (int s = 0; s < a.ns; ++s) {
+            const T gv = seed(s);
+            double* gs = gp + s * sstride;
+#pragma unroll
+            for (int u = 0; u < KB; ++u) gs[64 * (i0 + u)] += (double)(gv * v[u]);
+          }
+          if (NP > 4) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+  }
+}
+
+// The per-image pass of row row0 + blockIdx.x and seed s0 + blockIdx.y of the group: mean seeds (sid < c) into gmean [n1][c],
+// the variance seed into gvar [n1], which alone starts its chain from gdiag.
+template <typename T>
+__global__ void __launch_bounds__(256) cigx_finish_kernel(const T* __restrict__ x1, ConvProg p, const T* __restrict__ gdiag,
+                                                          const double* __restrict__ dq_tab, const double* __restrict__ part,
+                                                          int nsplit, int HWP, int64_t row0, int64_t items, int s0, int c,
+                                                          T* __restrict__ gmean, T* __restrict__ gvar) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int HW = p.H * p.W, L = p.layers, C = p.C;
+  const int64_t img = row0 + blockIdx.x;
+  const int sid = s0 + (int)blockIdx.y;
+  const double r0 = (sid >= c && gdiag) ? (double)gdiag[img] * p.lw2 / HW : 0.0;
+  T* out = sid < c ? gmean + (img * c + sid) * HW * C : gvar + img * HW * C;
+  const double* mine = part + ((int64_t)blockIdx.y * items + (int64_t)blockIdx.x * nsplit) * (int64_t)(L + C) * HWP;
+  cig_finish_image<T>(x1 + img * HW * C, p, r0, dq_tab + img * L * HW, mine, nsplit, HWP, out, smem);
+}
+
+template <typename T>
+using CigxKernel = void (*)(CigxArgs<T>);
+
+template <typename T>
+CigxKernel<T> cigx_form(int act, int64_t hw) {
+  if (act == SMN_ACT_RELU) return hw <= 64 ? cigx_pair_kernel<T, 0, 1> : hw <= 256 ? cigx_pair_kernel<T, 0, 4> : cigx_pair_kernel<T, 0, 16>;
+  return hw <= 64 ? cigx_pair_kernel<T, 1, 1> : hw <= 256 ? cigx_pair_kernel<T, 1, 4> : cigx_pair_kernel<T, 1, 16>;
+}
+
+constexpr size_t kCigxPartBytes = (size_t)256 << 20;   // the sums of one pass (or smn_debug_batch_bytes, if smaller)
+constexpr int64_t kCigxMinPer = 8;                      // partners per slice, at least (fewer only when n2 is)
+
+template <typename T>
+int cigx_run(smn_ctx* ctx, int act, int layers, double w_std, double b_std, double last_w_std, const void* x1_d, int64_t n1,
+             const void* x2_d, int64_t n2, int64_t H, int64_t W, int64_t C, const void* alpha_d, int64_t c, const void* gbar_d,
+             int64_t ldg, const void* gdiag_d, void* gmean_d, void* gvar_d) {
+  const ConvProg p = make_prog(act, layers, H, W, C, w_std, b_std, last_w_std);
+  const int64_t HW = H * W;
+  const int64_t HWP = HW <= 64 ? 64 : HW <= 256 ? 256 : 1024;
+  const size_t lds_q = 2 * (size_t)(H + 2) * (W + 2) * sizeof(double);
+  const size_t lds_p = wave_map_lds_bytes<T>(H, W);
+  const CigxKernel<T> kern = cigx_form<T>(act, HW);
+  SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_p));
+  const int64_t resident = std::max<int64_t>(resident_blocks(ctx, kern, lds_p), ctx->num_cu) * 4;
+  // rows x slices fills the resident waves once, with slices of at least kCigxMinPer partners: every slice costs a block of
+  // sums per seed that is cleared, added to and read back by the per-image pass, and at four partners per slice (16 rows of
+  // 32 x 32 images against 1000 partners) that traffic, not the sweeps, was the call
+  int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(resident / n1, (n2 + kCigxMinPer - 1) / kCigxMinPer));
+  const int64_t per = (n2 + nsplit - 1) / nsplit;
+  nsplit = (n2 + per - 1) / per;   // no empty slice
+  // the seed list: mean seeds 0 .. cc - 1, the variance seed cc
+  const int cc = alpha_d ? (int)c : 0;
+  const int s_begin = gmean_d ? 0 : cc, s_end = gvar_d ? cc + 1 : cc;
+  const size_t block = sizeof(double) * (size_t)(layers + C) * HWP;   // one seed's sums of one slice
+  const size_t budget = std::max<size_t>(std::min(ctx->batch_bytes, kCigxPartBytes), block);
+  const int64_t rows_b = std::max<int64_t>(1, std::min<int64_t>(n1, (int64_t)(budget / (block * (size_t)nsplit))));
+  const int sg = (int)std::max<size_t>(1, std::min<size_t>((size_t)(s_end - s_begin), budget / (block * (size_t)(rows_b * nsplit))));
+  const int64_t waves_max = std::min(resident, round_up(rows_b * nsplit, 4));
+  // doubles first: dq [n1][L][HW], part [sg][rows_b nsplit][L + C][HWP]; then in T: ra1 [n1][L][HWP], ra2 [n2][L][HWP], fwd
+  const size_t lay = (size_t)(layers > 0 ? layers : 1);
+  const size_t n_part = (size_t)sg * (size_t)(rows_b * nsplit) * (size_t)(layers + C) * HWP;
+  const size_t nd = (size_t)n1 * lay * HW + n_part;
+  const size_t nt = (size_t)(n1 + n2) * lay * HWP + (size_t)waves_max * 2 * lay * HWP;
+  void* wsv = nullptr;
+  SMN_TRY(smn_workspace(ctx, 4, sizeof(double) * nd + sizeof(T) * nt, &wsv));
+  double* dq = static_cast<double*>(wsv);
+  double* part = dq + (size_t)n1 * lay * HW;
+  T* ra1 = reinterpret_cast<T*>(part + n_part);
+  T* ra2 = ra1 + (size_t)n1 * lay * HWP;
+  CigxArgs<T> a;
+  a.x1 = static_cast<const T*>(x1_d); a.x2 = static_cast<const T*>(x2_d);
+  a.ra1 = ra1; a.ra2 = ra2;
+  a.alpha = static_cast<const T*>(alpha_d); a.c = cc;
+  a.gbar = static_cast<const T*>(gbar_d); a.ldg = ldg;
+  a.n2 = n2; a.nsplit = (int)nsplit; a.per = per;
+  a.prog = p;
+  a.fwd = ra2 + (size_t)n2 * lay * HWP;
+  a.part = part;
+  {
+    ProfScope ps(ctx, PROF_PREP, ctx->stream);
+    SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(cig_q_kernel<T>), lds_q));
+    hipLaunchKernelGGL(cig_q_kernel<T>, dim3((unsigned)n1), dim3(256), lds_q, ctx->stream, a.x1, p, n1, (int)HWP, ra1, dq);
+    hipLaunchKernelGGL(cig_q_kernel<T>, dim3((unsigned)n2), dim3(256), lds_q, ctx->stream, a.x2, p, (int64_t)0, (int)HWP, ra2,
+                       static_cast<double*>(nullptr));
+  }
+  SMN_CHECK_LAUNCH(ctx);
+  SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(cigx_finish_kernel<T>), lds_q));
+  for (int64_t row0 = 0; row0 < n1; row0 += rows_b) {
+    const int64_t rows = std::min(rows_b, n1 - row0);
+    a.row0 = row0; a.items = rows * nsplit;
+    const int64_t waves = std::min(resident, round_up(a.items, 4));
+    for (int s0 = s_begin; s0 < s_end; s0 += sg) {
+      a.s0 = s0; a.ns = std::min(sg, s_end - s0);
+      ProfScope ps(ctx, PROF_MISC, ctx->stream);
+      hipLaunchKernelGGL(kern, dim3((unsigned)(waves / 4)), dim3(256), lds_p, ctx->stream, a);
+      hipLaunchKernelGGL(cigx_finish_kernel<T>, dim3((unsigned)rows, (unsigned)a.ns), dim3(256), lds_q, ctx->stream, a.x1, p,
+                         static_cast<const T*>(gdiag_d), dq, part, a.nsplit, (int)HWP, row0, a.items, s0, cc,
+                         static_cast<T*>(gmean_d), static_cast<T*>(gvar_d));
+      SMN_CHECK_LAUNCH(ctx);
+    }
+  }
+  SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SMN_OK;
+}
+
 }  // namespace
+
+extern "C" int smn_kernel_cnn_input_grad_cross(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
+                                               double last_w_std, const void* x1_d, int64_t n1, const void* x2_d, int64_t n2,
+                                               int64_t H, int64_t W, int64_t C, const void* alpha_d, int64_t c, const void* gbar_d,
+                                               int64_t ldg, const void* gdiag_d, void* gmean_d, void* gvar_d) {
+  if (!ctx) return SMN_EINVAL;
+  SMN_ENTER(ctx);
+  const char* who = "smn_kernel_cnn_input_grad_cross";
+  if (!x1_d || !x2_d) return smn_fail(ctx, SMN_EINVAL, "%s: x1_d or x2_d is NULL", who);
+  if (!gmean_d && !gvar_d) return smn_fail(ctx, SMN_EINVAL, "%s: gmean_d and gvar_d are both NULL", who);
+  if (gmean_d && !alpha_d) return smn_fail(ctx, SMN_EINVAL, "%s: gmean_d needs alpha_d", who);
+  if (gvar_d && !gbar_d && !gdiag_d) return smn_fail(ctx, SMN_EINVAL, "%s: gvar_d needs gbar_d or gdiag_d", who);
+  if (n1 < 1 || n2 < 1) return smn_fail(ctx, SMN_EINVAL, "%s: bad sizes (n1 = %lld, n2 = %lld)", who, (long long)n1, (long long)n2);
+  SMN_TRY(conv_check(ctx, who, dtype, act, num_hiddens, n1, H, W, C, kCigMaxHW));
+  SMN_CHECK_LD(ctx, who, ldg, n2);
+  if (c < 0 || (alpha_d && c < 1)) return smn_fail(ctx, SMN_EINVAL, "%s: c = %lld (1 <= c <= 48 with alpha_d)", who, (long long)c);
+  if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: c = %lld: more than 48 mean seeds", who, (long long)c);
+  return by_dtype(dtype, [&](auto e) {
+    return cigx_run<decltype(e)>(ctx, act, num_hiddens, w_std, b_std, last_w_std, x1_d, n1, x2_d, n2, H, W, C, alpha_d, c, gbar_d, ldg,
+                                 gdiag_d, gmean_d, gvar_d);
+  });
+}
 
 extern "C" int smn_kernel_cnn_input_grad(smn_ctx* ctx, int dtype, int act, int num_hiddens, double w_std, double b_std,
                                          double last_w_std, const void* x_d, int64_t n, int64_t H, int64_t W, int64_t C,

@@ -297,7 +297,7 @@ int build_cross(smn_fit* f, BuildCall b, int64_t r, BuildOut* built) {
 }
 
 // What the gradients read beside the factor, made once: L' = J L^T J (rows below it cleared), alpha^T = (L^-T beta)^T by the
-// forward sweep on L' of the reversed beta rows, and X^T.
+// forward sweep on L' of the reversed beta rows, and (fused states only: a matrix-form state keeps no x) X^T.
 int ensure_grad_state(smn_fit* f) {
   if (f->grad_ready) return SMN_OK;
   smn_ctx* ctx = f->ctx;
@@ -306,13 +306,13 @@ int ensure_grad_state(smn_fit* f) {
                xt_bytes = es * (size_t)round_up(f->d, kTile) * (size_t)f->n_pad;
   if (!f->lt) { SMN_HIP(ctx, hipMalloc(&f->lt, lt_bytes)); f->bytes += lt_bytes; }
   if (!f->alpha) { SMN_HIP(ctx, hipMalloc(&f->alpha, al_bytes)); f->bytes += al_bytes; }
-  if (!f->xt) { SMN_HIP(ctx, hipMalloc(&f->xt, xt_bytes)); f->bytes += xt_bytes; }
+  if (f->fused && !f->xt) { SMN_HIP(ctx, hipMalloc(&f->xt, xt_bytes)); f->bytes += xt_bytes; }
   SMN_HIP(ctx, hipMemsetAsync(f->lt, 0, lt_bytes, ctx->stream));
   SMN_TRY(flip_transpose_lower(ctx, f->dtype, f->lt, f->n_pad, f->a, f->lda, f->n_pad));
   SMN_TRY(flip_rows(ctx, f->dtype, f->lt_at(f->n_pad), f->n_pad, f->at(f->beta_row(), 0), f->lda, f->c, f->n_pad));
   SMN_TRY(solve_rows_padded(ctx, f->dtype, f->lt, f->n_pad + kTile, f->n_pad, f->n_pad));
   SMN_TRY(flip_rows(ctx, f->dtype, f->alpha, f->n_pad, f->lt_at(f->n_pad), f->n_pad, f->c, f->n_pad));
-  SMN_TRY(input_grad_transpose(ctx, f->dtype, f->xp(), f->n_pad, f->kp, f->d, f->xt));
+  if (f->fused) SMN_TRY(input_grad_transpose(ctx, f->dtype, f->xp(), f->n_pad, f->kp, f->d, f->xt));
   f->grad_ready = true;
   return SMN_OK;
 }
@@ -734,6 +734,43 @@ extern "C" int smn_fit_apply(smn_fit* fit, const void* k_td_d, int64_t t, int64_
     SMN_TRY(finish_chunk(fit, r, ktt, stride, static_cast<char*>(mean_d) + es * (size_t)(start * fit->c),
                          (var_d && ktt) ? static_cast<char*>(var_d) + es * (size_t)start : nullptr, cov_d, ldcov));
   }
+  return SMN_OK;
+}
+
+// The solve a state knows how to do, handed out: U = K_td K~^-1 for a cross kernel of the caller's and alpha = K~^-1 Y -- the two
+// sweeps of smn_fit_predict_grad's variance path (V^T = K_td L^-T on L, then U = V^T L^-1 as the forward sweep on L') with
+// K_td copied into the test rows as smn_fit_apply does.  Either kind of state; what the call adds to it is L' and alpha^T.
+extern "C" int smn_fit_weights(smn_fit* fit, const void* k_td_d, int64_t t, int64_t ldk, void* u_d, int64_t ldu, void* alpha_d) {
+  if (!fit || !fit->ctx) return SMN_EINVAL;
+  smn_ctx* ctx = fit->ctx;
+  SMN_ENTER(ctx);
+  const char* who = "smn_fit_weights";
+  if (!u_d && !alpha_d) return smn_fail(ctx, SMN_EINVAL, "%s: u_d and alpha_d are both NULL", who);
+  const int64_t n = fit->n, n_pad = fit->n_pad, c = fit->c;
+  if (u_d) {
+    if (!k_td_d) return smn_fail(ctx, SMN_EINVAL, "%s: u_d needs k_td_d", who);
+    if (t < 1 || t > fit->capacity)
+      return smn_fail(ctx, SMN_EINVAL, "%s: t = %lld outside [1, capacity = %lld]", who, (long long)t, (long long)fit->capacity);
+    SMN_CHECK_LD(ctx, who, ldk, n);
+    SMN_CHECK_LD(ctx, who, ldu, n);
+  }
+  if (fit->info != 0) {
+    if (u_d) SMN_TRY(fill_nan(fit, u_d, t, n, ldu));
+    return fill_nan(fit, alpha_d, n, c, c);
+  }
+  SMN_TRY(ensure_grad_state(fit));
+  const size_t es = fit->es();
+  if (u_d) {
+    const int64_t rp = round_up(t, kTile);
+    SMN_TRY(clear_tail_rows(fit, t));
+    SMN_TRY(copy_matrix(ctx, fit->dtype, fit->at(n_pad, 0), fit->lda, k_td_d, ldk, t, n, 0));
+    SMN_TRY(solve_rows_padded(ctx, fit->dtype, fit->a, n_pad + rp, n_pad, fit->lda));
+    SMN_TRY(flip_rows(ctx, fit->dtype, fit->lt_at(n_pad), n_pad, fit->at(n_pad, 0), fit->lda, rp, n_pad));
+    SMN_TRY(solve_rows_padded(ctx, fit->dtype, fit->lt, n_pad + rp, n_pad, n_pad));
+    // columns [0, n) of the row put back in order: the reversed row's last n entries
+    SMN_TRY(flip_rows(ctx, fit->dtype, u_d, ldu, fit->lt_at(n_pad) + es * (size_t)(n_pad - n), n_pad, t, n));
+  }
+  if (alpha_d) SMN_TRY(transpose_matrix(ctx, fit->dtype, alpha_d, c, fit->alpha, n_pad, c, n));
   return SMN_OK;
 }
 

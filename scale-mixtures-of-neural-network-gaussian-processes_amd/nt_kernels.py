@@ -249,6 +249,40 @@ class CnnKernelFn:
                      self.w_std, self.b_std, self.last_w_std, a.ptr, n, h, w, c, out.ptr)
         return out
 
+    def _check_input_grad(self, h, w):
+        """What the reverse pass of the conv kernel covers: get_cnn_kernel and images of at most 1024 pixels."""
+        if self.entry != "smn_kernel_cnn":
+            raise NotImplementedError("input_grad exists for get_cnn_kernel only: the pooled kernel and the conv ResNet have no "
+                                      "input derivative here")
+        if int(h) * int(w) > 1024:
+            raise NotImplementedError("input_grad needs images of at most 1024 pixels, got %d x %d" % (h, w))
+
+    def input_grad(self, x1, x2, gbar):
+        """gx [n1,H,W,C] = sum_j gbar[r, j] dK(x1_r, x2_j)/dx1_r as a device array (smn_kernel_cnn_input_grad_cross with the
+        seed as its variance seed and no diagonal term): the kernel differentiated in its first argument, contracted with
+        the seed gbar [n1, n2]; mirrors KernelFn.input_grad.  x2 must be given: the form in which both arguments move is
+        the seeded one of SVSP (smn_kernel_cnn_input_grad).  get_cnn_kernel only, images of at most 1024 pixels."""
+        if x2 is None:
+            raise NotImplementedError("input_grad needs x2: the symmetric form, in which both arguments move, is not implemented")
+        shape = tuple(x1.shape) if isinstance(x1, DeviceArray) else np.shape(x1)
+        if len(shape) != 4:
+            raise ValueError("conv kernel expects x of shape [N,H,W,C]")
+        self._check_input_grad(shape[1], shape[2])           # refused before a context is made
+        ctx = self.ctx or (x1.ctx if isinstance(x1, DeviceArray) else default_context())
+        a = as_device(x1, ctx)
+        b = as_device(x2, ctx, dtype=a.dtype)
+        if b.shape[1:] != a.shape[1:]:
+            raise ValueError("x1 and x2 image shapes differ")
+        g = as_device(gbar, ctx, dtype=a.dtype)
+        n1, h, w, c = a.shape
+        n2 = b.shape[0]
+        if tuple(g.shape) != (n1, n2):
+            raise ValueError("gbar must be [n1, n2] = %s, got %s" % ((n1, n2), g.shape))
+        out = ctx.empty((n1, h, w, c), a.dtype)
+        ctx.call("smn_kernel_cnn_input_grad_cross", a.dcode, self.act, self.num_hiddens, self.w_std, self.b_std, self.last_w_std,
+                 a.ptr, n1, b.ptr, n2, h, w, c, None, 0, g.ptr, n2, None, None, out.ptr)
+        return out
+
 
 def get_cnn_pool_kernel(num_hiddens, num_class=1, act="relu", w_std=1., b_std=0., last_w_std=1.):
     """get_cnn_kernel with stax.GlobalAvgPool() in place of stax.Flatten() (the pooling experiments/nt_kernels.py:75 leaves

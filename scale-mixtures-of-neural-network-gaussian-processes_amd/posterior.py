@@ -462,11 +462,22 @@ class FittedPosterior:
         arrays (None for the one not asked for); any T.  Units are those of `predict`: normalised targets, per unit of the
         input features as they are handed in, so in target units d mean is y_std * dmean and d var is y_std^2 * dvar.  Under
         the Student-t likelihood the predictive scale^2 is shape * var with predictive_params()'s shape, so its gradient is
-        shape * dvar.  Fused posteriors only (MLP / dense-ResNet kernel functions); the first call adds the transposed factor,
-        alpha and X^T to the device state (`nbytes` grows)."""
+        shape * dvar.  Fused posteriors (MLP / dense-ResNet kernel functions); the first call adds the transposed factor,
+        alpha and X^T to the device state (`nbytes` grows).
+
+        A matrix-form posterior over get_cnn_kernel returns saliency maps, (dmean [T,C,H,W,Cin], dvar [T,H,W,Cin]), for
+        images of at most 1024 pixels: per chunk of `capacity` rows kernel_fn(x_chunk, x_train), smn_fit_weights for
+        U = K_td K~^-1 and one smn_kernel_cnn_input_grad_cross call with the seeds alpha = K~^-1 Y (fetched once per call),
+        gbar = -2 U and gdiag = 1 -- one forward and one reverse sweep per (test, training) pair for all C + 1 seeds.  The
+        partner lists are cut by the chunk's size, so a row's last bits may depend on the rows it shares a chunk with.
+        Every other matrix-form posterior (the pooled kernel, the conv ResNet, foreign callables) has no input derivative."""
         if not self.fused:
-            raise NotImplementedError("predict_grad needs an MLP / dense-ResNet kernel function: the conv kernels and foreign "
-                                      "callables (matrix-form posteriors) have no input derivative here")
+            fn = getattr(self, "kernel_fn", None)
+            if not (isinstance(fn, CnnKernelFn) and fn.entry == "smn_kernel_cnn"):
+                raise NotImplementedError("predict_grad needs an MLP / dense-ResNet kernel function or get_cnn_kernel: the "
+                                          "pooled kernel, the conv ResNet and foreign callables (matrix-form posteriors) have "
+                                          "no input derivative here")
+            return self._predict_grad_cnn(x, mean, var)
         if self._handle is None:
             raise ValueError("this FittedPosterior is closed")
         if not (mean or var):
@@ -489,6 +500,53 @@ class FittedPosterior:
             for g, rows in ((dmean, t * c), (dvar, t)):
                 if g is not None:
                     ctx.call("smn_scale_columns", g.dcode, g.ptr, rows, d, d, sv, g.ptr, d)
+        nbytes = C.c_size_t()
+        ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
+        self.nbytes = int(nbytes.value)
+        return dmean, dvar
+
+    def _predict_grad_cnn(self, x, mean, var):
+        """predict_grad of a matrix-form posterior over get_cnn_kernel (see there)."""
+        if self._handle is None:
+            raise ValueError("this FittedPosterior is closed")
+        if not (mean or var):
+            raise ValueError("predict_grad: ask for mean, var or both")
+        if self.mode != "nngp":
+            raise NotImplementedError("the conv kernels are NNGP-only")
+        fn, ctx, c = self.kernel_fn, self.ctx, self.num_outputs
+        shape = tuple(int(s) for s in getattr(x, "shape", np.shape(x)))
+        tail = tuple(int(s) for s in self._x_train.shape[1:])
+        if len(shape) != 4 or shape[1:] != tail:
+            raise ValueError("x has rows of shape %s, the training data %s" % (shape[1:], tail))
+        if shape[0] < 1:
+            raise ValueError("predict_grad needs at least one test point")
+        t, h, w, cin = shape
+        fn._check_input_grad(h, w)                           # above 1024 pixels: NotImplementedError before any device call
+        xt = as_device(x, ctx, dtype=self.dtype)
+        x_train = as_device(self.x_train, ctx, dtype=self.dtype)
+        n, code = self.num_data, _lib.dtype_code(self.dtype)
+        dmean = ctx.empty((t, c, h, w, cin), self.dtype) if mean else None
+        dvar = ctx.empty((t, h, w, cin), self.dtype) if var else None
+        alpha = None
+        if mean:
+            alpha = ctx.empty((n, c), self.dtype)
+            ctx.call_on("smn_fit_weights", self._handle, None, 0, n, None, n, alpha.ptr)
+        if var:
+            ones = ctx.to_device(np.ones(min(self.capacity, t), dtype=self.dtype))
+            minus2 = np.full(n, -2.0).ctypes.data_as(C.POINTER(C.c_double))
+        per_row = h * w * cin
+        for start, rows in chunks(t, self.capacity):
+            xc = _rows(xt, start, rows)
+            u = None
+            if var:
+                k_td = self._kernel(xc, x_train)
+                u = ctx.empty((rows, n), self.dtype)
+                ctx.call_on("smn_fit_weights", self._handle, k_td.ptr, rows, n, u.ptr, n, None)
+                ctx.call("smn_scale_columns", code, u.ptr, rows, n, n, minus2, u.ptr, n)       # gbar = -2 U
+            ctx.call("smn_kernel_cnn_input_grad_cross", code, fn.act, fn.num_hiddens, fn.w_std, fn.b_std, fn.last_w_std,
+                     xc.ptr, rows, x_train.ptr, n, h, w, cin, None if alpha is None else alpha.ptr, c,
+                     None if u is None else u.ptr, n, ones.ptr if var else None,
+                     None if dmean is None else _at(dmean, start * c * per_row), None if dvar is None else _at(dvar, start * per_row))
         nbytes = C.c_size_t()
         ctx.call_on("smn_fit_info", self._handle, None, None, None, C.byref(nbytes))
         self.nbytes = int(nbytes.value)
