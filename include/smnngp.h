@@ -476,6 +476,11 @@ int smn_mixture_nll(smn_ctx* ctx, int dtype, int nprob, int64_t t, const void* m
  * smn_lml_grad_terms: the contraction alone.  k0_d [n,n] = X X^T / d and q_d [n] its diagonal (smn_gram),
  *   neg_kinv_d [n,n] = -K~^-1 and alpha_d [n] as smn_predict returns them for K_td = I, K_tt = 0
  *   (covariance = -K~^-1, mean = alpha).  coef = 1 (Gaussian) or (df+n)/((df + quad/scale) scale) (Student-t).
+ *   neg_kinv_d is read in its lower triangle and, whole, in the 64 x 64 blocks on the diagonal (entries above the diagonal
+ *   inside those blocks carry weight 0 and must be finite); no tile strictly above the block diagonal is touched.
+ *   b_std == 0 exactly (MLP / dense ResNet, as the conv entries below): every returned value is finite and terms_h[1] is 0 -- an
+ *   all-zero input row has zero variance at every layer, where the ReLU map is not differentiable; such a row contributes
+ *   nothing to terms_h[0..2], and its G_ii still counts in terms_h[3].  This holds for every dense gradient entry below.
  * smn_spr_loss_grad: everything from X and y (MLP / dense ResNet kernels): also returns quad = y^T K~^-1 y,
  *   logdet K~ and info, from which the host forms the log-pdf and the derivatives w.r.t. (a, b).
  *   On a non-PD matrix info > 0 and the terms are NaN. */

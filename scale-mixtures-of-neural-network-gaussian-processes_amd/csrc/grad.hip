@@ -123,14 +123,19 @@ __device__ __forceinline__ void grad_tables_row(const double* __restrict__ q0, i
     t[0] = (R)q;
     t[n] = (R)dw;
     t[2 * n] = (R)db;
+    // a row of zero variance (an all-zero input row under b_std == 0) under ReLU: the map is not differentiable there.  ra = 0
+    // beside rb = 0 gives the tile code c = 0, sp = 0 and zero variance-side factors without a branch in its loop (1 / sqrt(0)
+    // would give it 0 * inf), and the row's own chain stays at phi(q, q, q) = q / 2 = 0 with slope 1/2 instead of act_d's 0 / 0
+    const bool dead = ACT == ACT_RELU && q == 0.0;
     if (ACT == ACT_RELU) {
-      t[3 * n] = (R)(1.0 / sqrt(q));
+      t[3 * n] = dead ? R(0) : (R)(1.0 / sqrt(q));
       t[4 * n] = (R)sqrt(q);
     } else {
       t[3 * n] = (R)(1.0 / sqrt(1.0 + 2.0 * q));
       t[4 * n] = (R)(1.0 / (1.0 + 2.0 * q));
     }
-    const ActD r = act_d<ACT>(q, q, q);           // on the diagonal A = q_i = q_j
+    ActD r{0.0, 0.5, 0.0, 0.0};
+    if (!dead) r = act_d<ACT>(q, q, q);           // on the diagonal A = q_i = q_j
     const double dq = r.dA + r.d1 + r.d2;
     double o = r.o, ow = dq * dw, ob = dq * db;
     if (NET == NET_RESNET && s != nsets - 1) {    // K <- [Dense o act](K) + K
