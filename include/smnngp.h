@@ -936,6 +936,37 @@ int smn_lml_from_shards(smn_ctx* ctx, int dtype, int64_t n, const void* y_d, dou
                         double* logpdf_h, double* quad_h, double* logdet_h, int* info_h);
 int smn_debug_delay(smn_ctx* ctx, int stream_id, int64_t usec);
 
+/* ---- greedy pivoted Cholesky: a rank-M factor K ~ L L^T and M inducing points, without the N x N matrix (csrc/pchol.hip) ----
+ * State: L_d [n, ldl] of `dtype`, row-major, column j written at step j; resid_d [n] in fp64, r_i = K_ii - sum_t L_it^2.  One
+ * step with pivot p and its kernel row k = K(x_p, X): l_i = (k_i - sum_{t<j} L_it L_pt) / sqrt(r_p), L_ij = l_i rounded to
+ * `dtype`, r_i <- r_i - L_ij^2; the pivot's row gets L_pj = sqrt(r_p) and r_p = 0, a row whose residual is exactly 0 (an earlier
+ * pivot, a zero diagonal) gets L_ij = 0 and stays at 0.  Next pivot: argmax r_i, ties to the LOWEST index; remaining trace:
+ * sum_i max(r_i, 0).  Sums in fp64 in a fixed order (per lane ascending, then a butterfly; partials of 16 rows, then one
+ * reducing workgroup): no floating-point atomics, two calls give the same bits, and the bits depend neither on the grid nor on
+ * the alignment of the operands.  16-byte loads when a base is 16-byte aligned and its leading dimension a multiple of 16 bytes.
+ *   smn_pchol_begin  matrix form: resid_d <- diag_d [n] (of `dtype`) in fp64; *pivot_h, *rmax_h, *trace_h = the first pivot, its
+ *                    residual and the trace.  One synchronisation.
+ *   smn_pchol_step   matrix form: step j with `pivot` and its row krow_d [n] of `dtype` (from any kernel function);
+ *                    *next_pivot_h, *rmax_h, *trace_h = the next pivot, its residual, the remaining trace.  SMN_EINVAL with the
+ *                    state untouched when resid[pivot] is not > 0, when j >= ldl or j >= n.  When to stop is the caller's
+ *                    decision.  Two synchronisations.
+ *   smn_pchol_mlp    fused form for SMN_NET_MLP / SMN_NET_DENSE_RESNET (NNGP; SMN_NET_NTK -> SMN_ENOTSUP): the rows are made in
+ *                    the step kernel from x_d [n, ldx >= d] -- K0 = x_i . x_p / d streamed once per step, then the layer stack in
+ *                    fp64 for both dtypes -- and the initial residual is the closed-form diagonal of smn_kernel_mlp.  Up to
+ *                    max_rank <= n steps (ldl >= max_rank) are queued without a host round trip; the loop stops before step j
+ *                    when trace_j <= tol_rel trace_0 (tol_rel >= 0; 0: never) or when the largest residual is not above
+ *                    4 (j + 1) eps max_i K_ii, eps the unit roundoff of `dtype`: the rounding noise of a residual computed from
+ *                    j stored columns -- the matrix has run out of numerical rank.  The floor does not grow with n.  *rank_h = columns made; pivots_h [max_rank]: [0, rank) written; trace_h [max_rank + 1]:
+ *                    [0, rank] written (the trace before each step and after the last); columns [rank, max_rank) of L_d are
+ *                    zero.  One synchronisation, at the end. */
+int smn_pchol_begin(smn_ctx* ctx, int dtype, int64_t n, const void* diag_d, double* resid_d, int64_t* pivot_h,
+                    double* rmax_h, double* trace_h);
+int smn_pchol_step(smn_ctx* ctx, int dtype, int64_t n, int64_t j, int64_t pivot, const void* krow_d, void* L_d, int64_t ldl,
+                   double* resid_d, int64_t* next_pivot_h, double* rmax_h, double* trace_h);
+int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                  const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank, double tol_rel, void* L_d, int64_t ldl,
+                  double* resid_d, int64_t* pivots_h, double* trace_h, int64_t* rank_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ log-marginal-likelihood / predictive mean+variance):
 
     smnngp.nt_kernels   get_mlp_kernel / get_dense_resnet_kernel / get_cnn_kernel   (experiments/nt_kernels.py)
     smnngp.predict      gradient_descent_mse_ensemble                               (neural_tangents.predict)
+    smnngp.lowrank      pivoted_cholesky / greedy_variance_points: rank-M factors and inducing points without K(X, X)
     smnngp.spectral     eigh_pd / max_learning_rate                                 (jnp.linalg.eigh, neural_tangents.predict)
     smnngp.spax         kernels.NNGPKernel / NTKKernel, likelihoods.*, models.SPR, utils, bijectors, base   (spax/*)
 

@@ -159,6 +159,9 @@ PROTOTYPES = {
     "smn_fit_append_from_kernel": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _pd, _pd, _pi],
     "smn_fit_stats": [_vp, _pi64, _pd, _pd, _pd],
     "smn_fit_remove": [_vp, _pi64, _i64, _pd, _pd],
+    "smn_pchol_begin": [_vp, _i, _i64, _vp, _vp, _pi64, _pd, _pd],
+    "smn_pchol_step": [_vp, _i, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _pi64, _pd, _pd],
+    "smn_pchol_mlp": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _d, _vp, _i64, _vp, _pi64, _pd, _pi64],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing

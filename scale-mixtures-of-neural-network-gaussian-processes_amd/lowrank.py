@@ -1,0 +1,190 @@
+"""Greedy pivoted Cholesky of a kernel matrix that is never formed: K(X, X) ~ L L^T with L [N, M], from the kernel's diagonal
+and M of its rows (csrc/pchol.hip).  The pivots are the conditional-variance choice of M inducing points, L is the Nystroem
+factor of those points, and the trace of what is left out is known after every step, so a rank can be chosen by tolerance.
+
+    res = pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto")
+    res.pivots, res.factor, res.resid, res.trace, res.rank, res.approx(rows, cols)
+    greedy_variance_points(kernel_fn, x, m)  ->  pivots
+
+Routes
+  "fused"   MLP / dense-ResNet kernel functions with NNGP covariance: one call (smn_pchol_mlp) queues every step; the kernel
+            rows are made inside the step kernel from x, which is streamed once per step.
+  "matrix"  the host loop over smn_pchol_begin / smn_pchol_step: the diagonal from the kernel function, one row
+            kernel_fn(x[p:p+1], x) per step.  The conv kernel functions (all three), MLP-family functions under
+            with_cov("ntk"), and any other callable kernel_fn(x1, x2) that also has diag(x).
+  "auto"    the fused route where it exists.
+
+Both stop before step j when trace_j <= tol * trace_0, or when the largest residual is not above 4 (j + 1) eps max_i K_ii (eps: the
+unit roundoff of the storage dtype): the rounding noise of a residual computed from j stored columns -- the matrix has run out
+of numerical rank.  The floor grows with the columns made, not with N.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import DeviceArray, as_device, default_context
+from .nt_kernels import CnnKernelFn, KernelFn
+
+__all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky"]
+
+_DIAG_BLOCK = 256   # rows per symmetric build when an MLP-family diagonal is taken from diagonal blocks (matrix route)
+
+
+class PivotedCholesky:
+    """pivots: np.int64 [rank]; factor: device array [N, rank] in the dtype of x; resid: np.float64 [N], K_ii - sum_t L_it^2;
+    trace: np.float64 [rank + 1], the trace of the residual before each step and after the last; rank: columns made."""
+
+    def __init__(self, pivots, factor, resid, trace, rank):
+        self.pivots, self.factor, self.resid, self.trace, self.rank = pivots, factor, resid, trace, int(rank)
+        self._host = None
+
+    def approx(self, rows=None, cols=None):
+        """(L L^T)[rows][:, cols] on the host in fp64 (None: every row / column); for tests and figures."""
+        if self._host is None:
+            self._host = np.asarray(self.factor.raw_numpy(), dtype=np.float64).reshape(self.factor.shape)
+        a = self._host if rows is None else self._host[np.asarray(rows, dtype=np.int64)]
+        b = self._host if cols is None else self._host[np.asarray(cols, dtype=np.int64)]
+        return a @ b.T
+
+
+def _num_rows(x):
+    shape = tuple(x.shape) if isinstance(x, DeviceArray) else np.shape(x)
+    if len(shape) < 2 or shape[0] < 1:
+        raise ValueError("x must be [N, ...] with N >= 1, got shape %s" % (shape,))
+    return int(shape[0])
+
+
+def _pick_route(kernel_fn, route):
+    if route not in ("auto", "fused", "matrix"):
+        raise ValueError("route must be 'auto', 'fused' or 'matrix', got %r" % (route,))
+    fusable = isinstance(kernel_fn, KernelFn) and kernel_fn.cov == "nngp"
+    if route == "fused" and not fusable:
+        raise NotImplementedError("route='fused' exists for get_mlp_kernel / get_dense_resnet_kernel with NNGP covariance; %s%s goes "
+                                  "through route='matrix'" % (type(kernel_fn).__name__,
+                                                              " under with_cov('ntk')" if isinstance(kernel_fn, KernelFn) else ""))
+    if route == "auto":
+        route = "fused" if fusable else "matrix"
+    if route == "matrix" and not isinstance(kernel_fn, (KernelFn, CnnKernelFn)):
+        if not callable(kernel_fn) or not callable(getattr(kernel_fn, "diag", None)):
+            raise TypeError("route='matrix' needs a callable kernel_fn(x1, x2) that also has diag(x)")
+    return route
+
+
+def _check(kernel_fn, x, max_rank, tol, route):
+    """Everything that can be refused without a device: returns (N, max_rank, tol, route)."""
+    n = _num_rows(x)
+    max_rank = int(max_rank)
+    if max_rank < 1 or max_rank > n:
+        raise ValueError("max_rank must lie in [1, N = %d], got %d" % (n, max_rank))
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    return n, max_rank, tol, _pick_route(kernel_fn, route)
+
+
+def _compact(ctx, factor, rank):
+    """factor [N, max_rank] -> [N, rank] (two device transposes: the library has no strided device copy)."""
+    n, m = factor.shape
+    if rank == m:
+        return factor
+    out = ctx.empty((n, rank), factor.dtype)
+    if rank > 0:
+        t = ctx.empty((rank, n), factor.dtype)
+        ctx.call("smn_transpose", factor.dcode, t.ptr, n, factor.ptr, m, n, rank)
+        ctx.call("smn_transpose", factor.dcode, out.ptr, rank, t.ptr, n, rank, n)
+    return out
+
+
+def _fused(kernel_fn, x, n, max_rank, tol):
+    xs = kernel_fn.scaled(x)
+    ctx = xs.ctx
+    d = xs.shape[1]
+    factor = ctx.empty((n, max_rank), xs.dtype)
+    resid = ctx.empty((n,), np.float64)
+    pivots = np.zeros(max_rank, dtype=np.int64)
+    trace = np.zeros(max_rank + 1, dtype=np.float64)
+    rank = C.c_int64(0)
+    ctx.call("smn_pchol_mlp", xs.dcode, kernel_fn.net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+             kernel_fn.last_w_std, xs.ptr, n, d, d, max_rank, tol, factor.ptr, max_rank, resid.ptr,
+             pivots.ctypes.data_as(C.POINTER(C.c_int64)), trace.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rank))
+    r = int(rank.value)
+    return PivotedCholesky(pivots[:r].copy(), _compact(ctx, factor, r), resid.raw_numpy(), trace[:r + 1].copy(), r)
+
+
+def _row_view(xd, p):
+    """x[p:p+1] of a device array as a view (no copy); keeps the buffer alive."""
+    row_elems = int(np.prod(xd.shape[1:]))
+    v = DeviceArray(xd.ctx, (1,) + tuple(xd.shape[1:]), xd.dtype,
+                    ptr=C.c_void_p(xd.ptr.value + int(p) * row_elems * xd.dtype.itemsize), owner=False)
+    v._base = xd
+    return v
+
+
+def _rows_view(xd, a, b):
+    row_elems = int(np.prod(xd.shape[1:]))
+    v = DeviceArray(xd.ctx, (b - a,) + tuple(xd.shape[1:]), xd.dtype,
+                    ptr=C.c_void_p(xd.ptr.value + int(a) * row_elems * xd.dtype.itemsize), owner=False)
+    v._base = xd
+    return v
+
+
+def _matrix(kernel_fn, x, n, max_rank, tol):
+    native = isinstance(kernel_fn, (KernelFn, CnnKernelFn))
+    ctx = getattr(kernel_fn, "ctx", None) or (x.ctx if isinstance(x, DeviceArray) else default_context())
+    xd = as_device(x, ctx)
+    if isinstance(kernel_fn, KernelFn) and len(xd.shape) != 2:
+        xd = ctx.to_device(xd.numpy().reshape(n, -1))
+    dt = xd.dtype
+    if isinstance(kernel_fn, CnnKernelFn):
+        diag = kernel_fn.diag(xd)
+        row = lambda p: kernel_fn(_row_view(xd, p), xd)
+    elif isinstance(kernel_fn, KernelFn):
+        # the closed-form diagonal, read off the symmetric builds of diagonal blocks: O(N B d), B = _DIAG_BLOCK
+        dh = np.empty(n, dtype=dt)
+        for a in range(0, n, _DIAG_BLOCK):
+            b = min(n, a + _DIAG_BLOCK)
+            dh[a:b] = kernel_fn(_rows_view(xd, a, b), None, get=kernel_fn.cov).diagonal()
+        diag = ctx.to_device(dh)
+        row = lambda p: kernel_fn(_row_view(xd, p), xd, get=kernel_fn.cov)
+    else:
+        diag = as_device(np.asarray(kernel_fn.diag(x)).reshape(-1), ctx, dtype=dt)
+        row = lambda p: as_device(kernel_fn(_row_view(xd, p), xd), ctx, dtype=dt)
+    if tuple(diag.shape) != (n,) or diag.dtype != dt:
+        raise ValueError("diag(x) must be [N] in the dtype of x, got %s %s" % (diag.shape, diag.dtype))
+    factor = ctx.empty((n, max_rank), dt)
+    ctx.call("smn_memset", factor.ptr, 0, factor.nbytes)
+    resid = ctx.empty((n,), np.float64)
+    piv, rmax, tr = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    ctx.call("smn_pchol_begin", xd.dcode, n, diag.ptr, resid.ptr, C.byref(piv), C.byref(rmax), C.byref(tr))
+    floor1 = 4.0 * float(np.finfo(dt).eps) * max(rmax.value, 0.0)      # the floor of step j is (j + 1) times this
+    pivots, trace = [], [tr.value]
+    for j in range(max_rank):
+        if not rmax.value > (j + 1) * floor1 or trace[-1] <= tol * trace[0]:
+            break
+        k = row(piv.value)
+        if not native and (k.size != n):
+            raise ValueError("kernel_fn(x[p:p+1], x) must have N entries, got shape %s" % (k.shape,))
+        p = piv.value
+        ctx.call("smn_pchol_step", xd.dcode, n, j, p, k.ptr, factor.ptr, max_rank, resid.ptr, C.byref(piv), C.byref(rmax),
+                 C.byref(tr))
+        pivots.append(p)
+        trace.append(tr.value)
+    r = len(pivots)
+    return PivotedCholesky(np.asarray(pivots, dtype=np.int64), _compact(ctx, factor, r), resid.raw_numpy(),
+                           np.asarray(trace, dtype=np.float64), r)
+
+
+def pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto"):
+    """The partial Cholesky factorisation of K(x, x) with greedy pivoting (largest residual variance, ties to the lowest
+    index), up to max_rank <= N columns; x a host or a device array.  Input scales of an MLP-family kernel function are
+    applied first.  See the module docstring for the routes and the stopping rule."""
+    n, max_rank, tol, route = _check(kernel_fn, x, max_rank, tol, route)
+    return (_fused if route == "fused" else _matrix)(kernel_fn, x, n, max_rank, tol)
+
+
+def greedy_variance_points(kernel_fn, x, m):
+    """Indices of (up to) m rows of x chosen greedily by largest conditional variance: the pivots of pivoted_cholesky."""
+    return pivoted_cholesky(kernel_fn, x, m).pivots

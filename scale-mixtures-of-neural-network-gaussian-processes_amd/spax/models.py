@@ -666,6 +666,24 @@ class SVSP(Module):
         _lib.dtype_code(self.dtype)                               # float32 / float64 only
         self._kzz_cache = None
 
+    @classmethod
+    def from_greedy(cls, prior, kernel, x_pool, num_inducing, *, num_latent_gps: int = 1, eps: float = 1e-6, dtype=np.float64):
+        """An SVSP whose inducing images are the `num_inducing` images of x_pool [N,H,W,C] that carry the kernel at its
+        current hyper-parameters: the pivots of the greedy pivoted Cholesky of K(x_pool, x_pool) (lowrank.py; largest
+        conditional variance first, the pool's N x N matrix is never formed).  Selection is global, without per-class quotas.
+        ValueError, before any device call, for num_inducing outside [1, N]; ValueError when the pool runs out of numerical
+        rank before num_inducing points are found."""
+        from ..lowrank import _check, pivoted_cholesky
+        kernel_fn = kernel.get_kernel_fn()
+        _check(kernel_fn, x_pool, num_inducing, 0.0, "auto")
+        pool = x_pool if isinstance(x_pool, DeviceArray) else np.asarray(x_pool, dtype=np.dtype(dtype))
+        res = pivoted_cholesky(kernel_fn, pool, num_inducing)
+        if res.rank < int(num_inducing):
+            raise ValueError("x_pool has numerical rank %d under this kernel: fewer than num_inducing = %d distinct points"
+                             % (res.rank, int(num_inducing)))
+        host = pool.numpy() if isinstance(pool, DeviceArray) else pool
+        return cls(prior, kernel, host[res.pivots], num_latent_gps=num_latent_gps, eps=eps, dtype=dtype)
+
     def loss(self, key, x_batch, y_batch, num_train, num_samples, aux=False):
         raise NotImplementedError("SVSP.loss is a value for an autodiff framework to differentiate; this engine returns the "
                                   "negative ELBO together with its analytic gradient: SVSP.loss_and_grad")
