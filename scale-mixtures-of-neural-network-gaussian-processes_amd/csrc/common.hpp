@@ -209,3 +209,15 @@ template <class F>
 auto by_dtype(int dtype, F&& f) {
   return dtype == SMN_F64 ? f(double{}) : f(float{});
 }
+
+// The 16-byte vector of T for streaming kernels, as a compiler vector (gemm_nt.hpp's f32x4 / f64x2): an array of these stays in
+// registers, one of float4 / double2 went to scratch (fit_remove.hip).
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
+template <>
+struct Vec16<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
+
+// sizes of the pieces carved from one workspace allocation: every piece starts on a 256-byte boundary
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }

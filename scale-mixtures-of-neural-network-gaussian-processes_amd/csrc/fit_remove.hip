@@ -60,14 +60,6 @@ constexpr int kRW = kRB + kRK;     // columns of a step
 constexpr int kRLD = kRW + 1;      // LDS row stride in doubles (odd: a column walk over rows spreads over the banks)
 constexpr size_t kPanelLds = sizeof(double) * ((size_t)(kRB + kRW) * kRLD + kRB);
 
-// 16 bytes of T as a compiler vector (gemm_nt.hpp): an array of these stays in registers, one of float4 / double2 went to scratch
-template <typename T>
-struct RVec;
-template <>
-struct RVec<float> { using type = f32x4; static constexpr int N = 4; };
-template <>
-struct RVec<double> { using type = f64x2; static constexpr int N = 2; };
-
 // w [i, j] = L[src[i], w0 + j] (0 above the diagonal) for i < m, w [mb + k, j] = beta[k, w0 + j] for k < c; j < ncols.
 // grid.y strides over the m + c rows.
 template <typename T>
@@ -105,8 +97,8 @@ __global__ void remove_scatter_kernel(const T* __restrict__ w, int64_t ldw, T* _
 // overwritten, and no two threads share an address.
 template <typename T>
 __global__ void remove_compact_left_kernel(T* a, int64_t lda, const int64_t* __restrict__ src, int64_t w0, int64_t i0, int64_t m) {
-  using V = typename RVec<T>::type;
-  const int64_t col = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * RVec<T>::N;
+  using V = typename Vec16<T>::type;
+  const int64_t col = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * Vec16<T>::N;
   if (col >= w0) return;
   int64_t i = i0;
   for (; i + 8 <= m; i += 8) {
@@ -312,7 +304,7 @@ int remove_pass(smn_fit* f, const std::vector<int64_t>& gone, std::vector<int64_
   // the kept rows' columns left of the window, then the window and the beta rows
   const int64_t i0 = gone[0] - w0;
   if (w0 > 0) {
-    const int64_t groups = w0 / RVec<T>::N;
+    const int64_t groups = w0 / Vec16<T>::N;
     hipLaunchKernelGGL(remove_compact_left_kernel<T>, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, st, a, f->lda, src_d, w0, i0, m);
     SMN_CHECK_LAUNCH(ctx);
   }

@@ -5,25 +5,16 @@
 //     dK_rj / dx1_r = (F_1 x2_j + 2 F_2 x1_r) / d,      F_1 = dF/du,  F_2 = dF/dv
 // and for a seed G [n1, n2]
 //     gx[r, :] = sum_j G_rj dK_rj/dx1_r = ((G o F_1) X2 + 2 rowsum(G o F_2) o x1) / d.
-// F_1 and F_2 come from forward mode through the layer stack -- the chain grad.hip carries for (w^2, b^2) with other seeds:
-// k_u = 1, k_v = 0, dq_r/dv = p_r (a per-row table), every column-side tangent 0.  With act_r2's quantities (act_tangent.hpp:
-// phi, D = phi_A, phi_1, D_A, D_1; row = first argument) and t in {u, v}:
-//     Dense:       A = w2 k + b2,  A_t = w2 k_t;   NTK: T = A + w2 Theta,  T_t = A_t + w2 Theta_t
-//     activation:  k <- phi(A),  k_u <- D A_u,  k_v <- D A_v + phi_1 p_r
-//                  NTK: Theta <- T D,  Theta_u <- T_u D + T D_A A_u,  Theta_v <- T_v D + T (D_A A_v + D_1 p_r)
-//     last Dense:  K = lw2 k,  Theta_out = lw2 (k + Theta)
-// The dense ResNet applies the same rules in the order Dense; L x {S <- Dense(act(S)) + S}; act; Dense, the Theta slots holding T
-// between blocks (as in grad.hip).  Singular points follow act_r2: ReLU with (1 - c)(1 + c) <= 0 after clamping (x1_r equal to
-// x2_j) has D_A = D_1 = 0; a zero-variance row (ReLU, q = 0) gets ra = rb = 0 from the table kernel, i.e. c = 0, the value the
-// stax.Relu transform takes where sqrt(q_i q_j) = 0, and no variance-side term.  Every output stays finite there.
+// F_1 and F_2 come from forward mode through the layer stack: the chain of input_tangent.hpp (its rules, their derivation and
+// the guards at the singular points are there) with the row-side variance tangent alone, every column-side tangent being 0.
 //
 // Kernels.
 //   ig_tables_kernel   per row and activation layer, fp64 arithmetic stored in the chain's type: q, p = dq/dq0, ra, rb; and per
 //                      row the derivative of the closed-form diagonal, dK_rr/dq0 (NNGP) or dTheta_rr/dq0 (NTK).
 //   ig_tile_kernel     THE HOT KERNEL.  One workgroup per 128 x 128 tile of (x1 rows) x (x2 rows): K0 on the MFMA tile engine
-//                      (gemm_nt.hpp; never stored), the tangent chain in the epilogue in the storage type's arithmetic, four
-//                      entries of one row at a time (the chain's live state is 4 x 3 values, NTK 4 x 6, beside the tile's 64
-//                      accumulators).  Plain form: F_1 and F_2 [rows1, rows2] to workspace.  Seeded form: G o F_1 instead of F_1
+//                      (gemm_nt.hpp; never stored), the tangent chain (input_tangent.hpp, NV = 1) in the epilogue in the storage
+//                      type's arithmetic, four entries of one row at a time (the chain's live state is 4 x 3 values, NTK 4 x 6,
+//                      beside the tile's 64 accumulators).  Plain form: F_1 and F_2 [rows1, rows2] to workspace.  Seeded form: G o F_1 instead of F_1
 //                      and, instead of F_2, the tile's fp64 row sums of G o F_2 (lanes of a row by the xor tree, the two
 //                      waves of a row in wave order), one slot per (tile column, row).
 //   ig_rowsum_kernel   the tile columns' partial sums added in tile order: no floating-point atomics anywhere, two calls give
@@ -31,22 +22,22 @@
 //   ig_seed_kernel     streaming, 16-byte accesses: W = F_1 o seed and s_r = sum_j F_2[r, j] seed[r, j] in fp64 (the read-out
 //                      kernel's order, fit.hip) for a seed that is one vector for all rows (alpha_k) or a matrix (U).
 //   ig_contract_kernel (G o F_1) X2 on the tile engine as the NT product W [rows1, rows2] x X2T [d, rows2]^T, the epilogue
-//                      adding the row term:  out[r, e] = ca acc + (cs s_r + cd dd_r) x1[r, e].
+//                      adding the row term:  out[r, e] = ca acc + (cs s_r + cd dd_r) x1[r, e]  (the dd term optional: the
+//                      predictive variance has it).  THE contraction of input_grad_sym.hip too (x2 = x1), whose FEAT form adds,
+//                      per (tile row, feature), the fp64 sum of out o x1 (per thread in accumulator order, then the eight
+//                      threads of a column in a fixed order); storing out is optional there.
 // Routes.  Every form of the hot kernel is fused (Gram tile + chain in one launch) and free of scratch, with one exception: the
 // SEEDED f64 NTK forms are not built -- the largest of them (dense ResNet, ReLU) came out of the compiler with its 64 accumulators
 // in a 544-byte stack object -- and smn_kernel_mlp_input_grad takes those through the plain fused form and ig_seed_kernel on a
-// padded copy of the seed instead.  Compiler figures: profiles/r21_input_grad.txt.
+// padded copy of the seed instead.  Compiler figures: profiles/r31_input_tangent.txt (r21_input_grad.txt: when the kernel was written).
 #include <algorithm>
-#include <type_traits>
 
-#include "act_tangent.hpp"
 #include "gemm_nt.hpp"
+#include "input_tangent.hpp"
 #include "internal.hpp"
 #include "layer_prog.hpp"
 
 namespace {
-
-constexpr int kIgFields = 4;   // per activation layer and row: q, p = dq/dq0, ra, rb
 
 template <int NET, int ACT, typename R>
 __global__ void ig_tables_kernel(const double* __restrict__ q0, int64_t n, int nsets, double w2, double b2, double lw2, int ntk,
@@ -68,7 +59,7 @@ __global__ void ig_tables_kernel(const double* __restrict__ q0, int64_t n, int n
       th = q + w2 * th;
       tht = qt + w2 * tht;
     }
-    R* t = tab + (int64_t)s * kIgFields * n + i;
+    R* t = tab + (int64_t)s * kTabFields * n + i;
     t[0] = (R)q;
     t[n] = (R)qt;
     double o, oq, dd, ddq;   // the activation on the diagonal: phi(q, q, q), its slope, D and its slope
@@ -139,8 +130,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, siz
   double* red = reinterpret_cast<double*>(smem + sizeof(T) * (size_t)nsets * 5 * kTile);   // [2][128]
   for (int idx = tid; idx < nsets * kTile; idx += 256) {
     const int s = idx / kTile, r = idx % kTile;
-    const T* t1 = a.tab1 + (int64_t)s * kIgFields * a.ldt1 + row0 + r;
-    const T* t2 = a.tab2 + (int64_t)s * kIgFields * a.ldt2 + col0 + r;
+    const T* t1 = a.tab1 + (int64_t)s * kTabFields * a.ldt1 + row0 + r;
+    const T* t2 = a.tab2 + (int64_t)s * kTabFields * a.ldt2 + col0 + r;
     srow[(s * 3 + 0) * kTile + r] = t1[a.ldt1];
     srow[(s * 3 + 1) * kTile + r] = t1[2 * a.ldt1];
     srow[(s * 3 + 2) * kTile + r] = t1[3 * a.ldt1];
@@ -151,7 +142,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, siz
 
   constexpr int NT = Tile::NT;
   constexpr int NG = (sizeof(T) == 8 && NTK) ? 2 : NT;   // entries of a row carried together (six f64 values each: two)
-  const T w2 = a.w2, b2 = a.b2, lw2 = a.lw2;
+  using Chain = InputTangent<T, NET, ACT, NTK, 1>;
+  const Chain chain{a.w2, a.b2, a.lw2};
   int lcs[NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n) lcs[n] = wc * Tile::WN + n * M::TN + M::acc_col(lane);
@@ -164,62 +156,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, siz
       double rs = 0.0;
 #pragma unroll
      for (int n0 = 0; n0 < NT; n0 += NG) {
-      T k[NG], ku[NG], kv[NG], th[NG], thu[NG], thv[NG];
+      typename Chain::State st[NG];
 #pragma unroll
-      for (int n = 0; n < NG; ++n) {
-        k[n] = t.acc[m][n0 + n][i] * a.inv_d;
-        ku[n] = T(1);
-        kv[n] = th[n] = thu[n] = thv[n] = T(0);
-        if (NET == NET_RESNET) {   // the Dense in front of the first block: A, and T = A (Theta = 0)
-          k[n] = fma(w2, k[n], b2);
-          ku[n] = w2;
-          th[n] = k[n];
-          thu[n] = w2;
-        }
-      }
+      for (int n = 0; n < NG; ++n) chain.init(st[n], t.acc[m][n0 + n][i] * a.inv_d);
       for (int s = 0; s < nsets; ++s) {
-        const T rp = srow[(s * 3 + 0) * kTile + lr], rra = srow[(s * 3 + 1) * kTile + lr], rrb = srow[(s * 3 + 2) * kTile + lr];
+        const T rp[1] = {srow[(s * 3 + 0) * kTile + lr]};
+        const T rra = srow[(s * 3 + 1) * kTile + lr], rrb = srow[(s * 3 + 2) * kTile + lr];
 #pragma unroll
-        for (int n = 0; n < NG; ++n) {
-          const T cra = scol[(s * 2 + 0) * kTile + lcs[n0 + n]], crb = scol[(s * 2 + 1) * kTile + lcs[n0 + n]];
-          T aa = k[n], au = ku[n], av = kv[n], tt = th[n], tu = thu[n], tv = thv[n];
-          if (NET == NET_MLP) {
-            au = w2 * au;
-            av = w2 * av;
-            aa = fma(w2, aa, b2);
-            if (NTK) {
-              tt = fma(w2, tt, aa);
-              tu = fma(w2, tu, au);
-              tv = fma(w2, tv, av);
-            }
-          }
-          const ActR2<T> q = act_r2<ACT, T>(aa, rra, rrb, cra, crb, false);
-          T o = q.o, ou = q.dA * au, ov = fma(q.dA, av, q.d1 * rp);
-          T to = T(0), tou = T(0), tov = T(0);
-          if (NTK) {
-            const T du = q.hA * au, dv = fma(q.hA, av, q.h1 * rp);
-            to = tt * q.dA;
-            tou = fma(tu, q.dA, tt * du);
-            tov = fma(tv, q.dA, tt * dv);
-          }
-          if (NET == NET_RESNET && s != nsets - 1) {   // S <- Dense(act(S)) + S
-            const T a2 = fma(w2, o, b2), a2u = w2 * ou, a2v = w2 * ov;
-            o = aa + a2; ou = au + a2u; ov = av + a2v;
-            if (NTK) {
-              to = tt + fma(w2, to, a2);
-              tou = tu + fma(w2, tou, a2u);
-              tov = tv + fma(w2, tov, a2v);
-            }
-          }
-          k[n] = o; ku[n] = ou; kv[n] = ov; th[n] = to; thu[n] = tou; thv[n] = tov;
-        }
+        for (int n = 0; n < NG; ++n)
+          chain.step(st[n], s == nsets - 1, rra, rrb, scol[(s * 2 + 0) * kTile + lcs[n0 + n]],
+                     scol[(s * 2 + 1) * kTile + lcs[n0 + n]], rp);
       }
-      // the last Dense: K = lw2 k, Theta_out = lw2 (k + Theta); a ResNet's last set has left (k, Theta) too
 #pragma unroll
       for (int n = 0; n < NG; ++n) {
         const int64_t col = col0 + lcs[n0 + n];
-        const T f1 = lw2 * (NTK ? ku[n] + thu[n] : ku[n]);
-        const T f2 = lw2 * (NTK ? kv[n] + thv[n] : kv[n]);
+        const T f1 = chain.f1(st[n]), f2 = chain.f2(st[n], 0);
         if (SEEDED) {
           const T g = (row < a.n1 && col < a.n2) ? a.g[row * a.ldg + col] : T(0);
           a.f1[row * a.ldf + col] = g * f1;
@@ -250,13 +201,6 @@ __global__ void ig_rowsum_kernel(const double* __restrict__ partial, int64_t row
   s[r] = v;
 }
 
-template <typename T>
-struct IgVec;
-template <>
-struct IgVec<float> { using type = float4; static constexpr int N = 4; };
-template <>
-struct IgVec<double> { using type = double2; static constexpr int N = 2; };
-
 // One workgroup (four waves) per row r:  w[r, j] = f1[r, j] seed_rj,  s[r] = sum_j f2[r, j] seed_rj  (j < cols, a multiple of
 // 128; seed_rj = seed[r * lds + j], lds = 0: one vector for every row).  fp64 sums per lane in column order, the xor tree over a
 // wave, the four waves in wave order: the order depends on cols alone.
@@ -264,8 +208,8 @@ template <typename T>
 __global__ void __launch_bounds__(256) ig_seed_kernel(const T* __restrict__ f1, const T* __restrict__ f2, int64_t ldf, int64_t cols,
                                                       const T* __restrict__ seed, int64_t lds, T* __restrict__ w, int64_t ldw,
                                                       double* __restrict__ s) {
-  using V = typename IgVec<T>::type;
-  constexpr int VN = IgVec<T>::N;
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
   __shared__ double red[4];
   const int64_t row = blockIdx.x;
   const T* a1 = f1 + row * ldf;
@@ -313,40 +257,49 @@ struct IgcArgs {
   const T* x1; int64_t kp;       // the padded x1 (row term)
   const double* s; const T* dd;  // row sums; diagonal derivative (or null)
   double ca, cs, cd;
-  T* out; int64_t ldo;
+  T* out; int64_t ldo;           // (FEAT: or null)
+  double* fpart; int64_t dpad;   // FEAT: [rows1 / 128][dpad]
   int64_t n1, d;
 };
 
-template <typename T>
+template <typename T, bool FEAT>
 __global__ void __launch_bounds__(256) ig_contract_kernel(IgcArgs<T> a) {
   using Tile = MainTile<T>;
+  using M = typename Tile::M;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int64_t row0 = (int64_t)blockIdx.y * kTile, e0 = (int64_t)blockIdx.x * kTile;
   Tile t;
   t.zero();
   t.mainloop(a.w + row0 * a.ldw, a.ldw, a.x2t + e0 * a.ldt, a.ldt, a.K, smem);
+  double fs[Tile::NT];   // FEAT: per column of the thread, the sum of out o x1 over its rows
+#pragma unroll
+  for (int n = 0; n < Tile::NT; ++n) fs[n] = 0.0;
   t.for_each([&](int m, int n, int i, int lr, int lc) {
     const int64_t r = row0 + lr, e = e0 + lc;
     if (r < a.n1 && e < a.d) {
+      const double x = (double)a.x1[r * a.kp + e];
       const double rc = a.cs * a.s[r] + (a.dd ? a.cd * (double)a.dd[r] : 0.0);
-      a.out[r * a.ldo + e] = (T)(a.ca * (double)t.acc[m][n][i] + rc * (double)a.x1[r * a.kp + e]);
+      const T o = (T)(a.ca * (double)t.acc[m][n][i] + rc * x);
+      if (!FEAT || a.out) a.out[r * a.ldo + e] = o;
+      if (FEAT) fs[n] += (double)o * x;
     }
   });
+  if (FEAT) {   // (the mainloop ends with a barrier: its LDS is free)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    double* red = reinterpret_cast<double*>(smem);   // [2 wave rows][4 row groups of a wave][128 columns]
+#pragma unroll
+    for (int n = 0; n < Tile::NT; ++n)
+      red[(wr * 4 + (lane >> 4)) * kTile + wc * Tile::WN + n * M::TN + M::acc_col(lane)] = fs[n];
+    __syncthreads();
+    if (threadIdx.x < kTile) {
+      double v = 0.0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v += red[q * kTile + threadIdx.x];
+      a.fpart[(int64_t)blockIdx.y * a.dpad + e0 + threadIdx.x] = v;
+    }
+  }
 }
-
-template <typename F>
-int ig_with_form(int net, int act, bool ntk, F&& f) {
-  using std::integral_constant;
-  auto with_ntk = [&](auto NET, auto ACT) {
-    return ntk ? f(NET, ACT, std::true_type{}) : f(NET, ACT, std::false_type{});
-  };
-  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_RELU>{});
-  if (net == SMN_NET_MLP) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_ERF>{});
-  if (act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_RELU>{});
-  return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_ERF>{});
-}
-
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 template <typename T>
 int ig_factors_t(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* gbar, int64_t ldg) {
@@ -365,7 +318,7 @@ int ig_factors_t(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, cons
   a.partial = w.partial;
   a.map = TileMap::make(o.rows1 / kTile, o.rows2 / kTile, 0);
   const size_t lds = ig_tile_lds<T>(nsets);
-  return ig_with_form(o.spec.net, o.spec.act, o.ntk, [&](auto NET, auto ACT, auto NTK) -> int {
+  return with_net_form(o.spec.net, o.spec.act, o.ntk, [&](auto NET, auto ACT, auto NTK) -> int {
     constexpr int net = decltype(NET)::value, act = decltype(ACT)::value;
     constexpr bool ntk = decltype(NTK)::value;
     const dim3 gt1((unsigned)((o.rows1 + 255) / 256)), gt2((unsigned)((o.rows2 + 255) / 256));
@@ -403,13 +356,25 @@ bool input_grad_seeded_fused(int dtype, bool ntk) { return !(dtype == SMN_F64 &&
 
 int input_grad_nsets(const BuildSpec& spec) { return spec.net == SMN_NET_MLP ? spec.num_hiddens : spec.num_hiddens + 1; }
 
+int input_grad_check(smn_ctx* ctx, const char* who, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                     double last_w_std, BuildSpec* spec, bool* ntk) {
+  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "%s: bad dtype %d", who, dtype);
+  SMN_TRY(split_net(ctx, &net, ntk));
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "%s: Unsupported act %d", who, act);
+  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: num_hiddens = %d", who, num_hiddens);
+  *spec = BuildSpec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
+  if (input_grad_nsets(*spec) > kMaxSets)
+    return smn_fail(ctx, SMN_ENOTSUP, "%s: num_hiddens too large (max %d activation layers)", who, kMaxSets);
+  return SMN_OK;
+}
+
 InputGradWs input_grad_ws_carve(void* base, int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded) {
   const size_t es = dtype_size(dtype), ns = (size_t)(nsets > 0 ? nsets : 1), mat = es * (size_t)rows1 * (size_t)rows2;
   char* p = static_cast<char*>(base);
   auto take = [&](size_t bytes) { void* r = p; p += al256(bytes); return r; };
   InputGradWs w{};
-  w.tab1 = take(es * ns * kIgFields * (size_t)rows1);
-  w.tab2 = take(es * ns * kIgFields * (size_t)rows2);
+  w.tab1 = take(es * ns * kTabFields * (size_t)rows1);
+  w.tab2 = take(es * ns * kTabFields * (size_t)rows2);
   w.ddiag = take(es * (size_t)rows1);
   w.s = static_cast<double*>(take(sizeof(double) * (size_t)rows1));
   w.w = take(mat);
@@ -437,7 +402,7 @@ int input_grad_tables(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const doubl
   const double w2 = spec.w_std * spec.w_std, b2 = spec.b_std * spec.b_std, lw2 = spec.last_w_std * spec.last_w_std;
   by_dtype(spec.dtype, [&](auto e) {
     using T = decltype(e);
-    ig_with_form(spec.net, spec.act, ntk, [&](auto NET, auto ACT, auto) -> int {
+    with_net_form(spec.net, spec.act, ntk, [&](auto NET, auto ACT, auto) -> int {
       hipLaunchKernelGGL((ig_tables_kernel<decltype(NET)::value, decltype(ACT)::value, T>), dim3((unsigned)((rows + 255) / 256)),
                          dim3(256), 0, ctx->stream, q64, rows, nsets, w2, b2, lw2, ntk ? 1 : 0, static_cast<T*>(tab_d),
                          static_cast<T*>(ddiag_d));
@@ -460,7 +425,7 @@ int input_grad_seed(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, c
 }
 
 int input_grad_contract(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, double ca, double cs, double cd, void* out_d,
-                        int64_t ldo) {
+                        int64_t ldo, double* fpart_d) {
   return by_dtype(o.spec.dtype, [&](auto e) -> int {
     using T = decltype(e);
     IgcArgs<T> a;
@@ -471,13 +436,13 @@ int input_grad_contract(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& 
     a.s = w.s; a.dd = cd != 0.0 ? static_cast<const T*>(w.ddiag) : nullptr;
     a.ca = ca; a.cs = cs; a.cd = cd;
     a.out = static_cast<T*>(out_d); a.ldo = ldo;
+    a.fpart = fpart_d; a.dpad = round_up(o.d, kTile);
     a.n1 = o.n1; a.d = o.d;
-    auto kern = ig_contract_kernel<T>;
+    auto kern = fpart_d ? ig_contract_kernel<T, true> : ig_contract_kernel<T, false>;
     const size_t lds = MainTile<T>::LDS_BYTES;
     SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
     ProfScope ps(ctx, PROF_TRAIL, ctx->stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(round_up(o.d, kTile) / kTile), (unsigned)(o.rows1 / kTile)), dim3(256), lds,
-                       ctx->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.dpad / kTile), (unsigned)(o.rows1 / kTile)), dim3(256), lds, ctx->stream, a);
     SMN_CHECK_LAUNCH(ctx);
     return SMN_OK;
   });
@@ -507,25 +472,19 @@ extern "C" int smn_kernel_mlp_input_grad(smn_ctx* ctx, int dtype, int net, int a
   if (!ctx) return SMN_EINVAL;
   SMN_ENTER(ctx);
   const char* who = "smn_kernel_mlp_input_grad";
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "%s: bad dtype %d", who, dtype);
+  InputGradOps o{};
+  SMN_TRY(input_grad_check(ctx, who, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, &o.spec, &o.ntk));
   if (!x2_d)
     return smn_fail(ctx, SMN_EINVAL, "%s: x2_d is NULL: the form in which both arguments move (x2 == x1) is not implemented", who);
   if (!x1_d || !gbar_d || !gx_d) return smn_fail(ctx, SMN_EINVAL, "%s: x1_d, gbar_d or gx_d is NULL", who);
   if (n1 <= 0 || n2 <= 0 || d <= 0)
     return smn_fail(ctx, SMN_EINVAL, "%s: empty operand (n1=%lld n2=%lld d=%lld)", who, (long long)n1, (long long)n2, (long long)d);
-  bool ntk = false;
-  SMN_TRY(split_net(ctx, &net, &ntk));
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "%s: Unsupported act %d", who, act);
-  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: num_hiddens = %d", who, num_hiddens);
   SMN_CHECK_LD(ctx, who, ldx1, d);
   SMN_CHECK_LD(ctx, who, ldx2, d);
   SMN_CHECK_LD(ctx, who, ldg, n2);
   SMN_CHECK_LD(ctx, who, ldgx, d);
-  InputGradOps o{};
-  o.spec = BuildSpec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
-  o.ntk = ntk;
+  const bool ntk = o.ntk;
   const int nsets = input_grad_nsets(o.spec);
-  if (nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "%s: num_hiddens too large (max %d activation layers)", who, kMaxSets);
   const size_t es = dtype_size(dtype);
   o.kp = k_pad(dtype, d); o.d = d;
   o.n1 = n1; o.rows1 = round_up(n1, kTile);

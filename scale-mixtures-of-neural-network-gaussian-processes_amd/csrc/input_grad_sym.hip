@@ -9,9 +9,9 @@
 //     r_n    = sum_{m != n} G_nm F_2[n, m]
 //     gx_n   = dLambda/dx~_n = (sum_m W_nm x~_m + (2 r_n + G_nn ddiag_n) x~_n) / d
 //     feat_j = sum_n gx[n, j] x~[n, j]              (dLambda/ds_j = feat_j / s_j for x~ = s o x;  dLambda/dx_n = s o gx_n)
-// F_1, F_2 by the forward-mode chain of input_grad.hip (same rules, same guards at the singular points) with ONE more tangent:
-// an entry of the lower triangle serves (n, m) and (m, n) at once, so beside the row-side variance tangent (seed p_n = dq_n/dv_n)
-// it carries the column-side one (seed p_m; act_r2's d2 / h2 in place of d1 / h1).
+// F_1, F_2 by the forward-mode chain of input_tangent.hpp (the rules and the guards at the singular points are there) with BOTH
+// variance-side tangents (NV = 2): an entry of the lower triangle serves (n, m) and (m, n) at once, so beside the row-side
+// tangent (seed p_n = dq_n/dv_n) it carries the column-side one (seed p_m).
 //
 // Kernels.
 //   igs_pass_kernel      THE HOT KERNEL.  Elementwise over the 64 x 64 tiles of the lower triangle of the kept K0 = X~ X~^T / d
@@ -23,26 +23,23 @@
 //                        thread in row order, the four waves in wave order) into slot tr + 1 of the column.  A row of tile row t
 //                        owns the slots 0..t (row side) and t + 1..T (column side): every slot is written exactly once.
 //   igs_rowsum_kernel    s_n = the slots in order + 1/2 G_nn ddiag_n.  No floating-point atomics: two calls give the same bits.
-//   igs_contract_kernel  out = ca (W X~) + cs s_n x~_n on the tile engine (input_grad.hip's contraction), with an epilogue for
-//                        feat: per (tile row, feature) the fp64 sum of out o x~ (per thread in accumulator order, then the eight
-//                        threads of a column in a fixed order); storing out is optional.
+//   (input_grad.hip)     ig_contract_kernel through input_grad_contract: out = ca (W X~) + cs s_n x~_n on the tile engine, its
+//                        FEAT form leaving per (tile row, feature) the fp64 sum of out o x~; storing out is optional.
 //   igs_colsum_kernel    feat_j = the tile rows' partial sums in tile-row order.
 //   igs_scale_kernel     out[r, j] = x[r, j] s[j]: streaming, 16-byte accesses where the leading dimensions allow.
-// Every form of the pass is free of scratch (compiler figures: profiles/r26_ard.txt): the f64 NTK forms carry 4 rows at a time,
-// f32 NTK and f64 NNGP 8, f32 NNGP 16.
+// Every form of the pass is free of scratch (compiler figures: profiles/r31_input_tangent.txt): the f64 NTK forms carry 4 rows at
+// a time, f32 NTK and f64 NNGP 8, f32 NNGP 16.
 #include <algorithm>
-#include <type_traits>
 #include <vector>
 
-#include "act_tangent.hpp"
 #include "gemm_nt.hpp"
+#include "input_tangent.hpp"
 #include "internal.hpp"
 #include "layer_prog.hpp"
 
 namespace {
 
-constexpr int ST = 64;          // tile edge of the pass
-constexpr int kSymFields = 4;   // input_grad_tables: q, p = dq/dq0, ra, rb per activation layer and row
+constexpr int ST = 64;   // tile edge of the pass
 
 template <typename T>
 struct SymArgs {
@@ -70,67 +67,28 @@ __global__ void __launch_bounds__(256) igs_pass_kernel(SymArgs<T> a) {
   const int lc = tid % ST;
   const int w = __builtin_amdgcn_readfirstlane(tid / ST);
   const int64_t j = col0 + lc, jc = j < n ? j : n - 1;
-  const T w2 = a.w2, b2 = a.b2, lw2 = a.lw2, coef = a.coef;
+  using Chain = InputTangent<T, NET, ACT, NTK, 2>;
+  const Chain chain{a.w2, a.b2, a.lw2};
+  const T coef = a.coef;
   double cs = 0.0;   // the column's sum of G o F_2 (column side) over the thread's rows
 #pragma unroll 1
   for (int p = 0; p < NPASS; ++p) {
     const int lr0 = w + 4 * NR * p;
-    T k[NR], ku[NR], kv[NR], kc[NR], th[NR], thu[NR], thv[NR], thc[NR];
+    typename Chain::State st[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       const int64_t i = row0 + lr0 + 4 * r, ic = i < n ? i : n - 1;
       const int64_t hi = ic > jc ? ic : jc, lo = ic > jc ? jc : ic;
-      k[r] = a.k0[hi * a.ld0 + lo];
-      ku[r] = T(1);
-      kv[r] = kc[r] = th[r] = thu[r] = thv[r] = thc[r] = T(0);
-      if (NET == NET_RESNET) {   // the Dense in front of the first block: A, and T = A (Theta = 0)
-        k[r] = fma(w2, k[r], b2);
-        ku[r] = w2;
-        th[r] = k[r];
-        thu[r] = w2;
-      }
+      chain.init(st[r], a.k0[hi * a.ld0 + lo]);
     }
     for (int s = 0; s < a.nsets; ++s) {
-      const T* ts = a.tab + (int64_t)s * kSymFields * rows;
+      const T* ts = a.tab + (int64_t)s * kTabFields * rows;
       const T cp = ts[rows + j], cra = ts[2 * rows + j], crb = ts[3 * rows + j];
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         const int64_t i = row0 + lr0 + 4 * r;   // wave-uniform
-        const T rp = ts[rows + i], rra = ts[2 * rows + i], rrb = ts[3 * rows + i];
-        T aa = k[r], au = ku[r], av = kv[r], ac = kc[r], tt = th[r], tu = thu[r], tv = thv[r], tcn = thc[r];
-        if (NET == NET_MLP) {
-          au = w2 * au;
-          av = w2 * av;
-          ac = w2 * ac;
-          aa = fma(w2, aa, b2);
-          if (NTK) {
-            tt = fma(w2, tt, aa);
-            tu = fma(w2, tu, au);
-            tv = fma(w2, tv, av);
-            tcn = fma(w2, tcn, ac);
-          }
-        }
-        const ActR2<T> q = act_r2<ACT, T>(aa, rra, rrb, cra, crb, false);
-        T o = q.o, ou = q.dA * au, ov = fma(q.dA, av, q.d1 * rp), oc = fma(q.dA, ac, q.d2 * cp);
-        T to = T(0), tou = T(0), tov = T(0), toc = T(0);
-        if (NTK) {
-          const T du = q.hA * au, dv = fma(q.hA, av, q.h1 * rp), dc = fma(q.hA, ac, q.h2 * cp);
-          to = tt * q.dA;
-          tou = fma(tu, q.dA, tt * du);
-          tov = fma(tv, q.dA, tt * dv);
-          toc = fma(tcn, q.dA, tt * dc);
-        }
-        if (NET == NET_RESNET && s != a.nsets - 1) {   // S <- Dense(act(S)) + S
-          const T a2 = fma(w2, o, b2), a2u = w2 * ou, a2v = w2 * ov, a2c = w2 * oc;
-          o = aa + a2; ou = au + a2u; ov = av + a2v; oc = ac + a2c;
-          if (NTK) {
-            to = tt + fma(w2, to, a2);
-            tou = tu + fma(w2, tou, a2u);
-            tov = tv + fma(w2, tov, a2v);
-            toc = tcn + fma(w2, toc, a2c);
-          }
-        }
-        k[r] = o; ku[r] = ou; kv[r] = ov; kc[r] = oc; th[r] = to; thu[r] = tou; thv[r] = tov; thc[r] = toc;
+        const T pp[2] = {ts[rows + i], cp};
+        chain.step(st[r], s == a.nsets - 1, ts[2 * rows + i], ts[3 * rows + i], cra, crb, pp);
       }
     }
     // the seed, formed behind the layer loop: C (-K~^-1)_ij + coef sum_c A_ic A_jc (k is dead: its slots take it)
@@ -138,7 +96,7 @@ __global__ void __launch_bounds__(256) igs_pass_kernel(SymArgs<T> a) {
     for (int r = 0; r < NR; ++r) {
       const int64_t i = row0 + lr0 + 4 * r, ic = i < n ? i : n - 1;
       const int64_t hi = ic > jc ? ic : jc, lo = ic > jc ? jc : ic;
-      k[r] = T(a.nc) * a.nkinv[hi * a.ldki + lo];
+      st[r].k = T(a.nc) * a.nkinv[hi * a.ldki + lo];
     }
     const T* aj = a.alpha + jc * a.nc;
     for (int c = 0; c < a.nc; ++c) {
@@ -146,19 +104,16 @@ __global__ void __launch_bounds__(256) igs_pass_kernel(SymArgs<T> a) {
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         const int64_t i = row0 + lr0 + 4 * r, ic = i < n ? i : n - 1;   // wave-uniform
-        k[r] = fma(coef * a.alpha[ic * a.nc + c], ajc, k[r]);
+        st[r].k = fma(coef * a.alpha[ic * a.nc + c], ajc, st[r].k);
       }
     }
-    // the last Dense: K = lw2 k, Theta_out = lw2 (k + Theta)
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       const int li = lr0 + 4 * r;
       const int64_t i = row0 + li;
       const bool valid = i < n && j < i;   // the strict lower triangle (j < i < n)
-      const T g = k[r];
-      const T f1 = lw2 * (NTK ? ku[r] + thu[r] : ku[r]);
-      const T f2r = lw2 * (NTK ? kv[r] + thv[r] : kv[r]);
-      const T f2c = lw2 * (NTK ? kc[r] + thc[r] : kc[r]);
+      const T g = st[r].k;
+      const T f1 = chain.f1(st[r]), f2r = chain.f2(st[r], 0), f2c = chain.f2(st[r], 1);
       tile[li][lc] = valid ? g * f1 : T(0);
       double rs = valid ? (double)(g * f2r) : 0.0;
       cs += valid ? (double)(g * f2c) : 0.0;
@@ -203,63 +158,6 @@ __global__ void igs_rowsum_kernel(const double* __restrict__ partial, int64_t ro
   s[r] = v;
 }
 
-template <typename T>
-struct SymcArgs {
-  const T* w; int64_t ldw;       // [rows, rows]
-  const T* xt; int64_t ldt;      // [dpad, rows]: the padded x~ transposed
-  int K;
-  const T* xp; int64_t kp;       // the padded x~ (row term)
-  const double* s;
-  double ca, cs;
-  T* out; int64_t ldo;           // or null
-  double* fpart; int64_t dpad;   // FEAT: [rows / 128][dpad]
-  int64_t n, d;
-};
-
-template <typename T, bool FEAT>
-__global__ void __launch_bounds__(256) igs_contract_kernel(SymcArgs<T> a) {
-  using Tile = MainTile<T>;
-  using M = typename Tile::M;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int64_t row0 = (int64_t)blockIdx.y * kTile, e0 = (int64_t)blockIdx.x * kTile;
-  Tile t;
-  t.zero();
-  t.mainloop(a.w + row0 * a.ldw, a.ldw, a.xt + e0 * a.ldt, a.ldt, a.K, smem);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  double fs[Tile::NT];
-#pragma unroll
-  for (int nn = 0; nn < Tile::NT; ++nn) fs[nn] = 0.0;
-#pragma unroll
-  for (int m = 0; m < Tile::MT; ++m)
-#pragma unroll
-    for (int nn = 0; nn < Tile::NT; ++nn)
-#pragma unroll
-      for (int i = 0; i < M::ACC; ++i) {
-        const int64_t r = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
-        const int64_t e = e0 + wc * Tile::WN + nn * M::TN + M::acc_col(lane);
-        if (r < a.n && e < a.d) {
-          const double x = (double)a.xp[r * a.kp + e];
-          const T o = (T)(a.ca * (double)t.acc[m][nn][i] + (a.cs * a.s[r]) * x);
-          if (a.out) a.out[r * a.ldo + e] = o;
-          if (FEAT) fs[nn] += (double)o * x;
-        }
-      }
-  if (FEAT) {   // (the mainloop ends with a barrier: its LDS is free)
-    double* red = reinterpret_cast<double*>(smem);   // [2 wave rows][4 row groups of a wave][128 columns]
-#pragma unroll
-    for (int nn = 0; nn < Tile::NT; ++nn)
-      red[(wr * 4 + (lane >> 4)) * kTile + wc * Tile::WN + nn * M::TN + M::acc_col(lane)] = fs[nn];
-    __syncthreads();
-    if (tid < kTile) {
-      double v = 0.0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v += red[q * kTile + tid];
-      a.fpart[(int64_t)blockIdx.y * a.dpad + e0 + tid] = v;
-    }
-  }
-}
-
 __global__ void igs_colsum_kernel(const double* __restrict__ fpart, int64_t dpad, int tiles, int64_t d, double* __restrict__ feat) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= d) return;
@@ -268,19 +166,12 @@ __global__ void igs_colsum_kernel(const double* __restrict__ fpart, int64_t dpad
   feat[e] = v;
 }
 
-template <typename T>
-struct SymVec;
-template <>
-struct SymVec<float> { using type = float4; static constexpr int N = 4; };
-template <>
-struct SymVec<double> { using type = double2; static constexpr int N = 2; };
-
 // one thread per 16-byte chunk of a row (grid.x over the chunks, grid.y strides the rows)
 template <typename T>
 __global__ void __launch_bounds__(256) igs_scale_kernel(const T* x, int64_t ldx, int64_t n, int64_t d, const T* __restrict__ s, T* out,
                                                         int64_t ldo, int vec) {
-  using V = typename SymVec<T>::type;
-  constexpr int VN = SymVec<T>::N;
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
   const int64_t k = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VN;
   if (k >= d) return;
   if (vec && k + VN <= d) {
@@ -301,20 +192,6 @@ __global__ void __launch_bounds__(256) igs_scale_kernel(const T* x, int64_t ldx,
   }
 }
 
-template <typename F>
-int igs_with_form(int net, int act, bool ntk, F&& f) {
-  using std::integral_constant;
-  auto with_ntk = [&](auto NET, auto ACT) {
-    return ntk ? f(NET, ACT, std::true_type{}) : f(NET, ACT, std::false_type{});
-  };
-  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_RELU>{});
-  if (net == SMN_NET_MLP) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_ERF>{});
-  if (act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_RELU>{});
-  return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_ERF>{});
-}
-
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 // One call's scratch in workspace slot 4 (beside what the gradient pipeline takes: one more rows^2 matrix, W, and the transposed
 // inputs), and the padded inputs with their fp64 row variances in slot 0 (the layout and size of the Gram build's own copy).
 struct SymWs {
@@ -332,7 +209,7 @@ SymWs sym_ws(int dtype, int nsets, int64_t n, int64_t d) {
   p.nslots = (int)(p.rows / ST) + 1;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t r = off; off += al256(bytes); return r; };
-  p.tab = take(es * ns * kSymFields * (size_t)p.rows);
+  p.tab = take(es * ns * kTabFields * (size_t)p.rows);
   p.ddiag = take(es * (size_t)p.rows);
   p.s = take(sizeof(double) * (size_t)p.rows);
   p.partial = take(sizeof(double) * (size_t)p.nslots * (size_t)p.rows);
@@ -384,7 +261,7 @@ int sym_run_t(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const void* x_d, in
   const int64_t t64 = p.rows / ST, ntiles = t64 * (t64 + 1) / 2;
   {
     ProfScope ps(ctx, PROF_MISC, ctx->stream);
-    igs_with_form(spec.net, spec.act, ntk, [&](auto NET, auto ACT, auto NTK) -> int {
+    with_net_form(spec.net, spec.act, ntk, [&](auto NET, auto ACT, auto NTK) -> int {
       hipLaunchKernelGGL((igs_pass_kernel<T, decltype(NET)::value, decltype(ACT)::value, decltype(NTK)::value>),
                          dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, a);
       return SMN_OK;
@@ -394,31 +271,15 @@ int sym_run_t(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const void* x_d, in
   hipLaunchKernelGGL(igs_rowsum_kernel<T>, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, ctx->stream, partial, p.rows,
                      p.nslots, n, a.nkinv, ldinv, a.alpha, (int)c, a.coef, ddiag, s);
   SMN_CHECK_LAUNCH(ctx);
-  SymcArgs<T> g;
-  g.w = wm; g.ldw = p.rows;
-  g.xt = xt; g.ldt = p.rows;
-  g.K = (int)p.rows;
-  g.xp = xp; g.kp = p.kp;
-  g.s = s;
-  g.ca = 1.0 / (double)d; g.cs = 2.0 / (double)d;
-  g.out = static_cast<T*>(gx_d); g.ldo = ldgx;
-  g.fpart = fpart; g.dpad = p.dpad;
-  g.n = n; g.d = d;
-  const size_t lds = MainTile<T>::LDS_BYTES;
-  const dim3 grid((unsigned)(p.dpad / kTile), (unsigned)(p.rows / kTile));
-  {
-    ProfScope ps(ctx, PROF_TRAIL, ctx->stream);
-    if (feat_h) {
-      auto kern = igs_contract_kernel<T, true>;
-      SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, g);
-    } else {
-      auto kern = igs_contract_kernel<T, false>;
-      SMN_TRY(smn_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, g);
-    }
-  }
-  SMN_CHECK_LAUNCH(ctx);
+  // input_grad.hip's contraction with x2 = x1 = x~: gx = (W X~ + 2 s o x~) / d, no diagonal term (s holds it)
+  InputGradOps o{};
+  o.spec = spec;
+  o.x1p = xp; o.n1 = n; o.rows1 = p.rows;
+  o.x2t = xt; o.rows2 = p.rows;
+  o.kp = p.kp; o.d = d;
+  InputGradWs ws{};
+  ws.w = wm; ws.s = s;
+  SMN_TRY(input_grad_contract(ctx, o, ws, 1.0 / (double)d, 2.0 / (double)d, 0.0, gx_d, ldgx, feat_h ? fpart : nullptr));
   if (!feat_h) return SMN_OK;
   hipLaunchKernelGGL(igs_colsum_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, ctx->stream, fpart, p.dpad,
                      (int)(p.rows / kTile), d, featd);
@@ -428,24 +289,18 @@ int sym_run_t(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const void* x_d, in
   return SMN_OK;
 }
 
-// The argument checks the two entries share (smn_kernel_mlp_input_grad's); leaves the architecture in spec->net.
+// The argument checks the two entries share: input_grad_check (which leaves the architecture in spec->net), then their operands.
 int sym_check(smn_ctx* ctx, const char* who, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
               double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t c, const void* gx_d, int64_t ldgx,
               const double* feat_h, BuildSpec* spec, bool* ntk) {
-  if (dtype != SMN_F32 && dtype != SMN_F64) return smn_fail(ctx, SMN_EINVAL, "%s: bad dtype %d", who, dtype);
+  SMN_TRY(input_grad_check(ctx, who, dtype, net, act, num_hiddens, w_std, b_std, last_w_std, spec, ntk));
   if (!x_d) return smn_fail(ctx, SMN_EINVAL, "%s: x_d is NULL", who);
   if (!gx_d && !feat_h) return smn_fail(ctx, SMN_EINVAL, "%s: gx_d and feat_h are both NULL", who);
   if (n <= 0 || d <= 0 || c < 1)
     return smn_fail(ctx, SMN_EINVAL, "%s: empty operand (n=%lld d=%lld c=%lld)", who, (long long)n, (long long)d, (long long)c);
   if (c > 48) return smn_fail(ctx, SMN_ENOTSUP, "%s: more than 48 output columns", who);
-  SMN_TRY(split_net(ctx, &net, ntk));
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "%s: Unsupported act %d", who, act);
-  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: num_hiddens = %d", who, num_hiddens);
   SMN_CHECK_LD(ctx, who, ldx, d);
   if (gx_d) SMN_CHECK_LD(ctx, who, ldgx, d);
-  *spec = BuildSpec{dtype, net, act, num_hiddens, w_std, b_std, last_w_std};
-  if (input_grad_nsets(*spec) > kMaxSets)
-    return smn_fail(ctx, SMN_ENOTSUP, "%s: num_hiddens too large (max %d activation layers)", who, kMaxSets);
   return SMN_OK;
 }
 
@@ -463,7 +318,7 @@ extern "C" int smn_scale_columns(smn_ctx* ctx, int dtype, const void* x_d, int64
   SMN_CHECK_LD(ctx, who, ldo, d);
   return by_dtype(dtype, [&](auto e) -> int {
     using T = decltype(e);
-    constexpr int VN = SymVec<T>::N;
+    constexpr int VN = Vec16<T>::N;
     void* sv = nullptr;
     SMN_TRY(smn_workspace(ctx, 4, sizeof(T) * (size_t)d, &sv));
     std::vector<T> stage((size_t)d);

@@ -271,7 +271,12 @@ struct InputGradWs {
   void* tab1; void* tab2; void* ddiag; double* s; void* w; void* f1; void* f2; double* partial;
   size_t bytes;   // of the whole layout
 };
+constexpr int kTabFields = 4;   // the table layout input_grad_tables writes, per activation layer and row: q, p = dq/dq0, ra, rb
 int input_grad_nsets(const BuildSpec& spec);   // activation layers of the stack
+// The argument checks every input-gradient entry shares: dtype, net (its SMN_NET_NTK flag split off into *ntk), act, num_hiddens
+// and the number of activation layers.  Leaves the architecture alone in spec->net.
+int input_grad_check(smn_ctx* ctx, const char* who, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                     double last_w_std, BuildSpec* spec, bool* ntk);
 bool input_grad_seeded_fused(int dtype, bool ntk);   // false: no fused seeded kernel for this form (plain form + input_grad_seed)
 size_t input_grad_ws_bytes(int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded);
 InputGradWs input_grad_ws_carve(void* base, int dtype, int nsets, int64_t rows1, int64_t rows2, bool seeded);
@@ -282,9 +287,12 @@ int input_grad_factors(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w
 int input_grad_tables(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const double* q64, int64_t rows, void* tab_d, void* ddiag_d);
 // ws.w = F_1 o seed, ws.s = rowsum(F_2 o seed); seed [rows1, rows2] with row stride lds, or one row for all (lds = 0)
 int input_grad_seed(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, const void* seed_d, int64_t lds);
-// out[r, e] = ca (ws.w X2)[r, e] + (cs ws.s[r] + cd ws.ddiag[r]) x1[r, e]   (r < n1, e < d)
+// out[r, e] = ca (ws.w X2)[r, e] + (cs ws.s[r] + cd ws.ddiag[r]) x1[r, e]   (r < n1, e < d; cd == 0: ws.ddiag is not read).
+// fpart_d != nullptr: fpart_d [rows1 / 128][round_up(d, 128)] takes, per 128-row tile and e, the fp64 sum of out o x1 over the
+// tile's rows (input_grad_sym.hip adds the tiles up in order), and out_d may be null.  Reads o.spec.dtype, x1p, x2t, n1, rows1,
+// rows2, kp, d and ws.w, ws.s, ws.ddiag.
 int input_grad_contract(smn_ctx* ctx, const InputGradOps& o, const InputGradWs& w, double ca, double cs, double cd, void* out_d,
-                        int64_t ldo);
+                        int64_t ldo, double* fpart_d = nullptr);
 // xt_d [round_up(d, 128), rows] = the padded xp [rows, kp] transposed, zero rows behind d
 int input_grad_transpose(smn_ctx* ctx, int dtype, const void* xp, int64_t rows, int64_t kp, int64_t d, void* xt_d);
 // dst[r, cols - 1 - j] = src[r, j]

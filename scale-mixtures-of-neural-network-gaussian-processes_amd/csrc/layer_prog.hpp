@@ -23,11 +23,28 @@
 // depths do move (profiles/r04_recursion_table.txt).  asin is steep at |c| -> 1, so entries of near-duplicate rows differ
 // from the generic path by up to 1e-4 in f32 -- both are equally far from the fp64 value there.
 #pragma once
+#include <type_traits>
+
+#include "../../include/smnngp.h"
 #include "nngp_math.hpp"
 
 enum { NET_MLP = 0, NET_RESNET = 1, NET_NONE = 2 };
 enum { ACT_RELU = 0, ACT_ERF = 1 };
 constexpr int kMaxSets = 16;
+
+// THE dispatch on a validated (architecture, activation, NNGP | NTK): f is a generic lambda called with the three as
+// integral constants (NET_*, ACT_*, bool), which names kernel<..., decltype(NET)::value, ...>.
+template <typename F>
+int with_net_form(int net, int act, bool ntk, F&& f) {
+  using std::integral_constant;
+  auto with_ntk = [&](auto NET, auto ACT) {
+    return ntk ? f(NET, ACT, std::true_type{}) : f(NET, ACT, std::false_type{});
+  };
+  if (net == SMN_NET_MLP && act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_RELU>{});
+  if (net == SMN_NET_MLP) return with_ntk(integral_constant<int, NET_MLP>{}, integral_constant<int, ACT_ERF>{});
+  if (act == SMN_ACT_RELU) return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_RELU>{});
+  return with_ntk(integral_constant<int, NET_RESNET>{}, integral_constant<int, ACT_ERF>{});
+}
 
 struct LayerProg {  // plain-old-data kernel argument
   int net, act, nsets;

@@ -151,6 +151,28 @@ def test_seeded_entry_equals_the_rules(L, ctx, kind, act, get, layers, dtype, n,
     assert np.array_equal(_bits(feat), _bits(only_feat)), "gx_d = NULL changes feat"
 
 
+# Every (net, act, covariance, dtype) form of the pass at one small shape: n = 129 (three 64-row tiles: both slot sides, and a
+# padded 128-tile in the contraction), d = 7, c = 3, two hidden layers (the ResNet takes its residual step and its last set).
+# Held to the file's FP32_RATIO as it stands; the fp32 ratios measured over these forms reach 2.47 (feat, resnet erf nngp;
+# profiles/r31_input_tangent.txt), the same before and after the chain moved into csrc/input_tangent.hpp (the bits are equal).
+ALL_FORMS = [(kind, act, get, dtype) for kind in ("mlp", "resnet") for act in ("relu", "erf") for get in ("nngp", "ntk")
+             for dtype in (np.float32, np.float64)]
+
+
+@pytest.mark.parametrize("kind,act,get,dtype", ALL_FORMS)
+def test_every_form_of_the_seeded_entry_equals_the_rules(L, ctx, kind, act, get, dtype):
+    f32 = dtype == np.float32
+    x, ninv, alpha, coef = sym_data(kind, act, get, 2, 129, 7, 3, f32)
+    gx, feat = _sym_call(L, ctx, kind, act, get, 2, dtype, x, ninv, alpha, coef)
+    gx64, feat64 = sym_reference(kind, act, get, 2, 129, 7, 3, f32, False)
+    gx32, feat32 = sym_reference(kind, act, get, 2, 129, 7, 3, f32, True) if f32 else (None, None)
+    what = "form %s %s %s %s" % (kind, act, get, np.dtype(dtype).name)
+    _check(what + " gx", gx, gx64, gx32, dtype)
+    _check(what + " feat", feat, feat64, feat32, dtype)
+    again = _sym_call(L, ctx, kind, act, get, 2, dtype, x, ninv, alpha, coef)
+    assert np.array_equal(_bits(gx), _bits(again[0])) and np.array_equal(_bits(feat), _bits(again[1])), "two calls differ in bits"
+
+
 # ----------------------------------------------------------------------------- 2. singular points
 @pytest.mark.parametrize("kind,get", [("mlp", "nngp"), ("resnet", "ntk"), ("mlp", "ntk"), ("resnet", "nngp")])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

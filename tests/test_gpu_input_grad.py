@@ -109,6 +109,24 @@ def test_kernel_input_grad_equals_the_rules(L, ctx, kind, act, get, layers, dtyp
     assert np.array_equal(got.view(np.uint8), again.view(np.uint8)), "two calls differ in bits"
 
 
+# Every (net, act, covariance, dtype) form of the hot kernel at one small shape: n1 = 5, n2 = 130 (two column tiles: the
+# tile-order row sums, padding on both sides), d = 7, two hidden layers (the ResNet takes its residual step and its last set).
+# The fp32 ratios measured over these forms reach 1.24 (profiles/r31_input_tangent.txt).
+ALL_FORMS = [(kind, act, get, dtype) for kind in ("mlp", "resnet") for act in ("relu", "erf") for get in ("nngp", "ntk")
+             for dtype in (np.float32, np.float64)]
+
+
+@pytest.mark.parametrize("kind,act,get,dtype", ALL_FORMS)
+def test_every_form_of_the_entry_equals_the_rules(L, ctx, kind, act, get, dtype):
+    x1, x2, g = entry_data(5, 130, 7, dtype == np.float32)
+    got = _entry_call(L, ctx, kind, act, get, 2, dtype, x1, x2, g)
+    ref64 = R.input_grad(kind, x1, x2, g, get, **_hyp(2, act))
+    ref32 = R.input_grad(kind, x1, x2, g, get, dtype=np.float32, **_hyp(2, act)) if dtype == np.float32 else None
+    _check("form %s %s %s %s" % (kind, act, get, np.dtype(dtype).name), got, ref64, ref32, dtype)
+    again = _entry_call(L, ctx, kind, act, get, 2, dtype, x1, x2, g)
+    assert np.array_equal(got.view(np.uint8), again.view(np.uint8)), "two calls differ in bits"
+
+
 def test_kernel_fn_input_grad_defaults_to_the_covariance_mode(ctx):
     from smnngp import nt_kernels
     x1, x2, g = entry_data(5, 130, 7, False)
