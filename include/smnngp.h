@@ -967,6 +967,46 @@ int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, do
                   const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank, double tol_rel, void* L_d, int64_t ldl,
                   double* resid_d, int64_t* pivots_h, double* trace_h, int64_t* rank_h);
 
+/* ---- regression on the pivoted-Cholesky factor: GP / Student-t models at O(n m^2) work and O(n m) memory (csrc/lowrank.hip) ----
+ * With L_d [n, ldl >= m] of `dtype` from smn_pchol_* and d_i = fitc max(resid_i, 0) + lambda, the model covariance is
+ * K^ = L L^T + diag(d): FITC on the greedy inducing points (fitc = 1) or SoR / DTC (fitc = 0).  Woodbury, W = diag(1 / d):
+ *   G = L^T W L,  B = L^T W Y,  s_k = sum_i w_i y_ik^2,  A = I + G = C C^T,  beta = A^-1 B,
+ *   quad_k = y_k^T K^^-1 y_k = s_k - |C^-1 B_k|^2,   logdet = log|K^| = log|A| + sum_i log d_i.
+ * Everything of size m x m is fp64 for both dtypes.  1 <= m <= SMN_LOWRANK_MAX_RANK, else SMN_ENOTSUP naming the limit.
+ * SMN_EINVAL, before anything is allocated or launched: a NULL pointer where one is needed, n, m or t below 1, c below its
+ * minimum (above 48: SMN_ENOTSUP), a leading dimension below the extent it strides, lambda not a positive finite number, fitc
+ * neither 0 nor 1.  SMN_ENOTSUP also for an n whose splits do not fit a launch (about 2^31 / (block pairs) splits).
+ *   smn_lowrank_gram     G_d [m, ldg >= m] (the whole matrix, the upper half mirrored from the lower bit for bit), B_d [m, c] and
+ *                        s_d [c], all fp64, from L_d, the weights w_d [n] (fp64; NULL: every weight 1) and y_d [n, ldy >= c] of
+ *                        `dtype`; 0 <= c <= 48, c = 0: G alone (y_d, B_d, s_d not touched).  The rows are cut into splits of
+ *                        SMN_LOWRANK_SPLIT rows; G accumulates each split on the MFMA of `dtype` (f32: the weight rounded to f32,
+ *                        w l rounded, then the MFMA), B and s in fp64; the splits are then added in fp64 in ascending order.  No
+ *                        floating-point atomics: two calls give the same bits, and the bits depend neither on ldl nor on the
+ *                        alignment of L_d (16-byte loads when the base is 16-byte aligned and ldl a multiple of 16 bytes, element
+ *                        loads into the same registers otherwise).  Workspace, kept by the context:
+ *                        ceil(n / SMN_LOWRANK_SPLIT) blocks of the lower half of G in `dtype`.  No synchronisation.
+ *   smn_lowrank_fit      the quantities above from L_d, resid_d [n] (fp64, smn_pchol's residual diagonal; NULL: zeros), lambda > 0,
+ *                        fitc in {0, 1} and y_d [n, ldy >= c], 1 <= c <= 48.  A is factored by smn_cholesky in fp64.  quad_h [c],
+ *                        *logdet_h; C_d [m, m] (lower, zeros above) and beta_d [m, c], both fp64, stay on the device for
+ *                        smn_lowrank_readout.  *info_h: 0, or the failing pivot of A (1-based): quad_h, *logdet_h, C_d and beta_d
+ *                        are then NaN and the return is SMN_OK, as smn_lml does.  Synchronises.
+ *   smn_lowrank_readout  predictions at t test points from kzt_d [m, ldk >= t] = K(Z, x*) (Z: the pivots' inputs) and
+ *                        ktt_d [t] = K(x*, x*), both of `dtype`; R_d [m, ldr >= m] = L[pivots, :] in fp64 (lower triangular,
+ *                        K(Z, Z) = R R^T), C_d and beta_d [m, c] from smn_lowrank_fit.  phi = R^-1 K(Z, x*), mean = phi^T beta,
+ *                        var = k** - |phi|^2 + |C^-1 phi|^2 (the DTC / FITC predictive of the latent function), computed in fp64
+ *                        and written as mean_d [t, c], var_d [t] of `dtype`.  Every sum has a fixed order that does not depend on t:
+ *                        a point predicted alone carries the bits it has inside a larger chunk.  No synchronisation. */
+#define SMN_LOWRANK_MAX_RANK 4096
+#define SMN_LOWRANK_SPLIT 512
+int smn_lowrank_gram(smn_ctx* ctx, int dtype, const void* L_d, int64_t n, int64_t m, int64_t ldl, const double* w_d,
+                     const void* y_d, int64_t c, int64_t ldy, double* G_d, int64_t ldg, double* B_d, double* s_d);
+int smn_lowrank_fit(smn_ctx* ctx, int dtype, const void* L_d, int64_t n, int64_t m, int64_t ldl, const double* resid_d,
+                    double lambda, int fitc, const void* y_d, int64_t c, int64_t ldy, double* C_d, double* beta_d, double* quad_h,
+                    double* logdet_h, int* info_h);
+int smn_lowrank_readout(smn_ctx* ctx, int dtype, const void* kzt_d, int64_t ldk, const void* ktt_d, int64_t t, int64_t m,
+                        const double* R_d, int64_t ldr, const double* C_d, const double* beta_d, int64_t c, void* mean_d,
+                        void* var_d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ ACT = {"relu": 0, "erf": 1}
 GET_NNGP, GET_NTK = 1, 2
 FILL_FULL, FILL_LOWER = 0, 1
 NET_MLP, NET_DENSE_RESNET = 0, 1
+LOWRANK_MAX_RANK, LOWRANK_SPLIT = 4096, 512   # SMN_LOWRANK_MAX_RANK, SMN_LOWRANK_SPLIT (include/smnngp.h)
 NET_NTK = 0x100   # SMN_NET_NTK: OR-ed into `net`, the model entries then work on Theta instead of K (include/smnngp.h)
 
 
@@ -162,6 +163,9 @@ PROTOTYPES = {
     "smn_pchol_begin": [_vp, _i, _i64, _vp, _vp, _pi64, _pd, _pd],
     "smn_pchol_step": [_vp, _i, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _pi64, _pd, _pd],
     "smn_pchol_mlp": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _i64, _d, _vp, _i64, _vp, _pi64, _pd, _pi64],
+    "smn_lowrank_gram": [_vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "smn_lowrank_fit": [_vp, _i, _vp, _i64, _i64, _i64, _vp, _d, _i, _vp, _i64, _i64, _vp, _vp, _pd, _pd, _pi],
+    "smn_lowrank_readout": [_vp, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing

@@ -5,6 +5,8 @@ factor of those points, and the trace of what is left out is known after every s
     res = pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto")
     res.pivots, res.factor, res.resid, res.trace, res.rank, res.approx(rows, cols)
     greedy_variance_points(kernel_fn, x, m)  ->  pivots
+    fit = woodbury_fit(res, y, lam, fitc)        regression on the factor (csrc/lowrank.hip): fit.quad, fit.logdet, fit.info,
+    fit.readout(kzt, ktt) -> mean, var           K^ = L L^T + diag(fitc max(resid, 0) + lam) by the Woodbury identity
 
 Routes
   "fused"   MLP / dense-ResNet kernel functions with NNGP covariance: one call (smn_pchol_mlp) queues every step; the kernel
@@ -28,7 +30,8 @@ from . import _lib
 from ._lib import DeviceArray, as_device, default_context
 from .nt_kernels import CnnKernelFn, KernelFn
 
-__all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky"]
+__all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky", "woodbury_fit", "WoodburyFit", "kernel_diag",
+           "kernel_cross"]
 
 _DIAG_BLOCK = 256   # rows per symmetric build when an MLP-family diagonal is taken from diagonal blocks (matrix route)
 
@@ -131,6 +134,32 @@ def _rows_view(xd, a, b):
     return v
 
 
+def kernel_diag(kernel_fn, xd, x=None):
+    """K(x_i, x_i) [N] as a device array in the dtype of xd, without the other pairs.  The conv kernel functions have their own
+    diag; an MLP-family diagonal is read off the symmetric builds of diagonal blocks, O(N B d) with B = _DIAG_BLOCK; any other
+    callable is asked for diag(x) (x: the array as the caller handed it in, xd by default)."""
+    ctx, n, dt = xd.ctx, xd.shape[0], xd.dtype
+    if isinstance(kernel_fn, CnnKernelFn):
+        return kernel_fn.diag(xd)
+    if isinstance(kernel_fn, KernelFn):
+        dh = np.empty(n, dtype=dt)
+        for a in range(0, n, _DIAG_BLOCK):
+            b = min(n, a + _DIAG_BLOCK)
+            dh[a:b] = kernel_fn(_rows_view(xd, a, b), None, get=kernel_fn.cov).diagonal()
+        return ctx.to_device(dh)
+    return as_device(np.asarray(kernel_fn.diag(xd if x is None else x)).reshape(-1), ctx, dtype=dt)
+
+
+def kernel_cross(kernel_fn, a, b):
+    """K(a, b) [na, nb] as a plain device array in the dtype of a: the covariance mode of an MLP-family kernel function, the
+    NNGP kernel of a conv one, whatever any other callable returns."""
+    if isinstance(kernel_fn, KernelFn):
+        return kernel_fn(a, b, get=kernel_fn.cov)
+    if isinstance(kernel_fn, CnnKernelFn):
+        return kernel_fn(a, b)
+    return as_device(kernel_fn(a, b), a.ctx, dtype=a.dtype)
+
+
 def _matrix(kernel_fn, x, n, max_rank, tol):
     native = isinstance(kernel_fn, (KernelFn, CnnKernelFn))
     ctx = getattr(kernel_fn, "ctx", None) or (x.ctx if isinstance(x, DeviceArray) else default_context())
@@ -138,19 +167,12 @@ def _matrix(kernel_fn, x, n, max_rank, tol):
     if isinstance(kernel_fn, KernelFn) and len(xd.shape) != 2:
         xd = ctx.to_device(xd.numpy().reshape(n, -1))
     dt = xd.dtype
+    diag = kernel_diag(kernel_fn, xd, x)
     if isinstance(kernel_fn, CnnKernelFn):
-        diag = kernel_fn.diag(xd)
         row = lambda p: kernel_fn(_row_view(xd, p), xd)
     elif isinstance(kernel_fn, KernelFn):
-        # the closed-form diagonal, read off the symmetric builds of diagonal blocks: O(N B d), B = _DIAG_BLOCK
-        dh = np.empty(n, dtype=dt)
-        for a in range(0, n, _DIAG_BLOCK):
-            b = min(n, a + _DIAG_BLOCK)
-            dh[a:b] = kernel_fn(_rows_view(xd, a, b), None, get=kernel_fn.cov).diagonal()
-        diag = ctx.to_device(dh)
         row = lambda p: kernel_fn(_row_view(xd, p), xd, get=kernel_fn.cov)
     else:
-        diag = as_device(np.asarray(kernel_fn.diag(x)).reshape(-1), ctx, dtype=dt)
         row = lambda p: as_device(kernel_fn(_row_view(xd, p), xd), ctx, dtype=dt)
     if tuple(diag.shape) != (n,) or diag.dtype != dt:
         raise ValueError("diag(x) must be [N] in the dtype of x, got %s %s" % (diag.shape, diag.dtype))
@@ -188,3 +210,73 @@ def pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto"):
 def greedy_variance_points(kernel_fn, x, m):
     """Indices of (up to) m rows of x chosen greedily by largest conditional variance: the pivots of pivoted_cholesky."""
     return pivoted_cholesky(kernel_fn, x, m).pivots
+
+
+class WoodburyFit:
+    """What smn_lowrank_fit leaves: quad [c] = y_k^T K^^-1 y_k, logdet = log|K^|, info (0, or the failing pivot of I + G; quad
+    and logdet are then NaN), and on the device the fp64 factor C of I + L^T W L, beta = (I + G)^-1 L^T W Y and R = L[pivots, :]."""
+
+    def __init__(self, res, lam, fitc, quad, logdet, info, c_fac, beta, r_fac):
+        self.res, self.lam, self.fitc = res, float(lam), bool(fitc)
+        self.quad, self.logdet, self.info = quad, float(logdet), int(info)
+        self.c_fac, self.beta, self.r_fac = c_fac, beta, r_fac
+
+    def readout(self, kzt, ktt):
+        """(mean [t, c], var [t]) device arrays in the factor's dtype from kzt [rank, t] = K(Z, x*), Z = x[res.pivots], and
+        ktt [t] = K(x*, x*): smn_lowrank_readout.  A point carries the same bits alone or inside a larger chunk."""
+        f = self.res.factor
+        ctx, m = f.ctx, self.res.rank
+        kzt, ktt = as_device(kzt, ctx, dtype=f.dtype), as_device(ktt, ctx, dtype=f.dtype)
+        if len(kzt.shape) != 2 or kzt.shape[0] != m or tuple(ktt.shape) != (kzt.shape[1],):
+            raise ValueError("kzt must be [rank = %d, t] and ktt [t], got %s and %s" % (m, kzt.shape, ktt.shape))
+        t, c = kzt.shape[1], self.beta.shape[1]
+        mean, var = ctx.empty((t, c), f.dtype), ctx.empty((t,), f.dtype)
+        ctx.call("smn_lowrank_readout", f.dcode, kzt.ptr, t, ktt.ptr, t, m, self.r_fac.ptr, m, self.c_fac.ptr, self.beta.ptr, c,
+                 mean.ptr, var.ptr)
+        return mean, var
+
+
+def _check_fit(res, y, lam, fitc):
+    """Everything woodbury_fit can refuse without a device: returns (y [n, c] float64, lam)."""
+    if not isinstance(res, PivotedCholesky):
+        raise TypeError("res must be a PivotedCholesky (pivoted_cholesky's result), got %s" % type(res).__name__)
+    if res.rank < 1:
+        raise ValueError("the factor has rank 0: nothing to regress on")
+    if res.rank > _lib.LOWRANK_MAX_RANK:
+        raise NotImplementedError("rank %d is above the limit of %d columns (SMN_LOWRANK_MAX_RANK)" % (res.rank, _lib.LOWRANK_MAX_RANK))
+    n = int(res.factor.shape[0])
+    y = np.asarray(y, dtype=np.float64)
+    y = y.reshape(n, 1) if y.ndim == 1 and y.shape[0] == n else y
+    if y.ndim != 2 or y.shape[0] != n or not 1 <= y.shape[1] <= 48:
+        raise ValueError("y must be [N = %d] or [N, C] with 1 <= C <= 48, got shape %s" % (n, np.shape(y)))
+    lam = float(lam)
+    if not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError("lam must be a positive finite number, got %r" % (lam,))
+    if fitc not in (0, 1, False, True):
+        raise ValueError("fitc must be a bool, got %r" % (fitc,))
+    return y, lam
+
+
+def woodbury_fit(res, y, lam, fitc=True):
+    """The regression quantities of K^ = L L^T + diag(d), d_i = fitc max(resid_i, 0) + lam, for a PivotedCholesky `res` and
+    targets y [N] or [N, C <= 48]: a WoodburyFit.  fitc=True is the FITC approximation on the greedy inducing points, False is
+    SoR / DTC.  O(N rank^2) work and O(N rank) memory; the rank x rank side runs in fp64 for both dtypes.  An fp32 factor
+    under fitc with a small lam loses digits in quad: the pivot rows have resid = 0, hence weight 1 / lam, and
+    s - |C^-1 B|^2 cancels (2.8e-2 relative at lam = 1e-6; README, "Low-rank regression")."""
+    y, lam = _check_fit(res, y, lam, fitc)
+    f = res.factor
+    ctx, (n, m), c = f.ctx, f.shape, y.shape[1]
+    yd = ctx.to_device(np.ascontiguousarray(y, dtype=f.dtype))
+    resid = ctx.to_device(np.ascontiguousarray(res.resid, dtype=np.float64)) if fitc else None
+    c_fac, beta = ctx.empty((m, m), np.float64), ctx.empty((m, c), np.float64)
+    quad = np.zeros(c, dtype=np.float64)
+    logdet, info = C.c_double(0.0), C.c_int(0)
+    ctx.call("smn_lowrank_fit", f.dcode, f.ptr, n, m, m, None if resid is None else resid.ptr, lam, 1 if fitc else 0, yd.ptr, c, c,
+             c_fac.ptr, beta.ptr, quad.ctypes.data_as(C.POINTER(C.c_double)), C.byref(logdet), C.byref(info))
+    if getattr(res, "_r_fac", None) is None:     # R = L[pivots, :] in fp64: rank row copies, once per factor
+        r = np.empty((m, m), dtype=f.dtype)
+        isz = f.dtype.itemsize
+        for j, p in enumerate(res.pivots):
+            ctx.call("smn_memcpy_d2h", r[j].ctypes.data_as(C.c_void_p), C.c_void_p(f.ptr.value + int(p) * m * isz), m * isz)
+        res._r_fac = ctx.to_device(np.tril(r).astype(np.float64))
+    return WoodburyFit(res, lam, fitc, quad, logdet.value, info.value, c_fac, beta, res._r_fac)

@@ -1,7 +1,8 @@
 """spax — host-side mirror of the hot-path surface of the reference library of the same name.
 
 Sub-modules (import them by name, as the reference's experiments do):
-    spax.models       SPR, MultiSPR (C outputs over one kernel matrix), SVSP (evaluation: test_acc_nll / evaluate)
+    spax.models       SPR, LowRankSPR (SPR on a rank-M pivoted-Cholesky factor), MultiSPR (C outputs over one kernel matrix),
+                      SVSP (evaluation: test_acc_nll / evaluate)
     spax.kernels      NNGPKernel, NTKKernel (the same models on the tangent kernel of the MLP / dense-ResNet architectures)
     spax.likelihoods  GaussianLikelihood, StudentTLikelihood
     spax.priors       GaussianPrior, InverseGammaPrior (sample_f_iid; the training-side methods raise)

@@ -18,7 +18,7 @@ from .likelihoods import _norm_logpdf, _t_logpdf
 from .priors import split_key
 from .utils import jitter
 
-__all__ = ["SPR", "MultiSPR", "SVSP", "grad_route", "multi_grad_route", "lml_value_and_grads"]
+__all__ = ["SPR", "LowRankSPR", "MultiSPR", "SVSP", "grad_route", "multi_grad_route", "lml_value_and_grads"]
 
 
 def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
@@ -484,6 +484,165 @@ class SPR(_ExactGP):
         )
         ll = np.mean(log_prob)
         return -ll
+
+
+class LowRankSPR(Module):
+    """SPR on a rank-M approximation of the kernel matrix: K(X, X) ~ L L^T from the greedy pivoted Cholesky
+    (lowrank.pivoted_cholesky), never the N x N matrix.  The model covariance is
+
+        K^ = L L^T + diag(resid)   correction="fitc": the FITC approximation on the M greedy inducing points
+        K^ = L L^T                 correction="none": SoR / DTC
+
+    and the log-marginal likelihood and the predictions of K^ + lam I come from the Woodbury identity on the device
+    (lowrank.woodbury_fit, csrc/lowrank.hip): O(N M^2) work, O(N M) memory, the M x M side in fp64.  Same trainables and names
+    as SPR (kernel.w_std / b_std / last_w_std, eps, the likelihood's a / b), so train.build_train_step(method="auto") trains it
+    by central differences and checkpoints carry over.
+
+    loss()        lam = eps, absolute, and SPR.loss's Gaussian / multivariate-t heads, over N.
+    predict(x)    (mean [T, 1], var [T]) of the latent function in normalised units under lam = eps trace(K) / N, the relative
+                  ridge of SPR.predict; the test set streams through in chunks, nothing of size N x N or T x T is formed.
+    test_nll      SPR.test_nll's per-point heads on those marginals.  DEVIATION for the Student-t head: its quadratic form is
+                  the one of that same fit, y^T (scale (K^ + lam I))^-1 y = quad / scale.  The reference (and SPR) take it from
+                  a separate matrix scale K + 1e-6 I; under a rank-M K^ that matrix divides the part of y outside the span of
+                  L by 1e-6, which is an artefact of the approximation and not a statement about the data.
+
+    rank: columns asked for (1 <= rank <= N, at most 4096); tol: stop early when the residual trace falls to tol trace(K).
+    Every kernel function pivoted_cholesky accepts works.  The factor is kept while the hyper-parameters do not change.
+    An fp32 model under "fitc" loses digits in loss() as eps shrinks (pivot rows weigh 1 / eps: 1.3e-6 relative at
+    eps >= 1e-2, 6.5e-5 at 1e-4, 2.8e-2 at 1e-6): use fp64 data or correction="none" there.  loss_and_grad, the leave-one-out
+    entries, posterior(), sample_posterior and input scales are not implemented."""
+
+    def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, rank, correction="fitc", eps: float = 1e-6,
+                 tol: float = 0.0):
+        super().__init__()
+        from .. import lowrank                       # (lowrank imports nothing from spax: no cycle, but keep start-up light)
+        shape = tuple(x_data.shape) if hasattr(x_data, "shape") else np.shape(x_data)
+        if len(shape) < 2 or shape[0] < 1:
+            raise ValueError("x_data must be [N, ...] with N >= 1, got shape %s" % (shape,))
+        if isinstance(rank, bool) or int(rank) != rank:
+            raise ValueError("rank must be an integer, got %r" % (rank,))
+        if not 1 <= int(rank) <= min(shape[0], _lib.LOWRANK_MAX_RANK):
+            raise ValueError("rank must lie in [1, min(N = %d, %d)], got %d" % (shape[0], _lib.LOWRANK_MAX_RANK, rank))
+        if correction not in ("fitc", "none"):
+            raise ValueError("correction must be 'fitc' or 'none', got %r" % (correction,))
+        if not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0, got %r" % (tol,))
+        if getattr(kernel, "input_scales", None) is not None:
+            raise NotImplementedError("LowRankSPR does not support input scales")
+        if not hasattr(likelihood, "lml_params"):
+            raise NotImplementedError("LowRankSPR needs a Gaussian or Student-t likelihood")
+        y = np.asarray(y_data, dtype=np.float64).reshape(-1)
+        if y.shape[0] != shape[0]:
+            raise ValueError("y_data has %d entries for N = %d inputs" % (y.shape[0], shape[0]))
+        self._lowrank = lowrank
+        self.kernel, self.likelihood = kernel, likelihood
+        self.rank, self.correction, self.tol = int(rank), correction, float(tol)
+        self.x_data = as_device(x_data)
+        self.y_host = y
+        self.y_mean, self.y_std = float(np.asarray(y_mean)), float(np.asarray(y_std))
+        self.num_data = self.x_data.shape[0]
+        self.eps = ConstraintTrainVar(eps, constraint=positive())
+        self._factor_cache = None                    # (key, PivotedCholesky, {lam: WoodburyFit})
+
+    # ---- what is not there, refused before any device call
+    def _missing(self, what):
+        raise NotImplementedError("LowRankSPR has no %s: the exact models (SPR) do" % what)
+
+    def loss_and_grad(self):
+        self._missing("analytic gradient (train.build_train_step(method='auto') falls back to central differences)")
+
+    def loo_loss(self):
+        self._missing("leave-one-out objective")
+
+    def loo_predict(self):
+        self._missing("leave-one-out predictions")
+
+    def loo_loss_and_grad(self):
+        self._missing("leave-one-out gradient")
+
+    def posterior(self, *args, **kwargs):
+        self._missing("fitted posterior")
+
+    def sample_posterior(self, *args, **kwargs):
+        self._missing("joint posterior draws")
+
+    # ---- the factor and the fits on it, kept by hyper-parameter content
+    def _factor(self):
+        kernel_fn = self.kernel.get_kernel_fn()
+        params = getattr(kernel_fn, "params", None)
+        key = None if params is None else (type(kernel_fn).__name__, getattr(kernel_fn, "entry", None),
+                                           getattr(kernel_fn, "cov", None), tuple(params))
+        hit = self._factor_cache
+        if hit is None or key is None or hit[0] != key:
+            res = self._lowrank.pivoted_cholesky(kernel_fn, self.x_data, self.rank, tol=self.tol)
+            hit = self._factor_cache = (key, res, {})
+        return kernel_fn, hit[1], hit[2]
+
+    def _fit(self, relative):
+        """The WoodburyFit under lam = eps (loss) or eps trace(K) / N (predict, test_nll)."""
+        kernel_fn, res, fits = self._factor()
+        eps = self.eps.safe_value
+        lam = eps * float(res.trace[0]) / self.num_data if relative else eps
+        if lam not in fits:
+            fits.clear() if len(fits) > 4 else None
+            fits[lam] = self._lowrank.woodbury_fit(res, self.y_host, lam, self.correction == "fitc")
+        return kernel_fn, res, fits[lam]
+
+    def loss(self):
+        _, _, fit = self._fit(False)
+        if fit.info != 0:
+            return float("nan")
+        df, scale = self.likelihood.lml_params()
+        student = df > 0.0
+        lp, _ = lml_value_and_grads((0.0,) * 4, float(fit.quad[0]), fit.logdet, self.num_data, df, scale,
+                                    self.likelihood.a.safe_value if student else None,
+                                    self.likelihood.b.safe_value if student else None)
+        return -lp / self.num_data
+
+    def _predict(self, x, chunk):
+        kernel_fn, res, fit = self._fit(True)
+        ctx, dt = self.x_data.ctx, self.x_data.dtype
+        xt = np.asarray(x.numpy() if isinstance(x, DeviceArray) else x)
+        if xt.shape[1:] != tuple(self.x_data.shape[1:]):
+            raise ValueError("x has shape %s, the training inputs %s" % (xt.shape, tuple(self.x_data.shape)))
+        t = xt.shape[0]
+        mean, var = np.full((t, 1), np.nan, dtype=dt), np.full(t, np.nan, dtype=dt)
+        if fit.info != 0 or t == 0:
+            return fit, mean, var
+        if getattr(res, "_z", None) is None:         # the inducing inputs Z = x[pivots]: rank rows, gathered once per factor
+            res._z = ctx.to_device(np.ascontiguousarray(self.x_data.numpy()[res.pivots]))
+        for a in range(0, t, chunk):
+            xc = ctx.to_device(np.ascontiguousarray(xt[a:a + chunk], dtype=dt))
+            kzt = self._lowrank.kernel_cross(kernel_fn, res._z, xc)
+            ktt = self._lowrank.kernel_diag(kernel_fn, xc)
+            m, v = fit.readout(kzt, ktt)
+            mean[a:a + chunk], var[a:a + chunk] = m.raw_numpy(), v.raw_numpy()
+        return fit, mean, var
+
+    def predict(self, x, cov="diag", chunk=2048):
+        """(mean [T, 1], var [T]) as host arrays in the model's dtype and in normalised units: the DTC / FITC predictive of the
+        latent function at x, `chunk` test points at a time (a point's bits do not depend on the chunking).  Only the
+        diagonal exists: a T x T covariance would defeat the purpose.  NaN when I + L^T W L does not factor."""
+        if cov != "diag":
+            raise NotImplementedError("LowRankSPR.predict has cov='diag' only")
+        if int(chunk) < 1:
+            raise ValueError("chunk must be at least 1")
+        _, mean, var = self._predict(x, int(chunk))
+        return mean, var
+
+    def test_nll(self, x, y, chunk=2048):
+        fit, mean, var = self._predict(x, int(chunk))
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        mu = mean.astype(np.float64).reshape(-1) * self.y_std + self.y_mean
+        v = var.astype(np.float64) * self.y_std ** 2
+        df, scale = self.likelihood.lml_params()
+        if df > 0.0:                                  # likelihoods.py:52-65 with the quadratic form of this fit (class docstring)
+            cond_df = df + self.num_data
+            sigma = np.sqrt((df + float(fit.quad[0]) / scale) / cond_df * scale * v)
+            log_prob = _t_logpdf(y * self.y_std + self.y_mean, cond_df, mu, sigma)
+        else:
+            log_prob = _norm_logpdf(y * self.y_std + self.y_mean, mu, np.sqrt(v))
+        return -np.mean(log_prob)
 
 
 def multi_grad_route(kernel_fn, likelihood):
