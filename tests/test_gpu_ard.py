@@ -14,7 +14,9 @@ Shapes of the entry cases: n in {1, 5, 129, 257} (the pass works on 64 x 64 tile
 tiles: one partial tile; several tile rows with off-diagonal tiles, so row-side and column-side partial sums both have more than
 one slot), d in {1, 7, 65, 130} (130: two feature tiles in the contraction), c in {1, 3}, 0 / 1 / 3 layers, sparse over net x act x
 covariance x dtype; every matrix operand inside a guarded window with a leading dimension above its extent, and the strict upper
-triangle of -K~^-1 NaN (the lower triangle is what is read)."""
+triangle of -K~^-1 NaN (the lower triangle is what is read).  The singular cases below assert finiteness for every form and values
+for NNGP only; test_gpu_input_probes.py holds smn_kernel_mlp_input_grad_sym pair by pair (every slot of the 64 x 64 pass, both
+stores, both slot sides) to a long-double reference, the NTK forms at near-duplicate, duplicate and anti-parallel rows included."""
 import ctypes as C
 import functools
 

@@ -2,7 +2,10 @@
 KernelFn.input_grad and FittedPosterior.predict_grad, against the fp64 rules of tests/_input_grad_rules.py.
 
 Metric: _tol.relerr_norm per output array (sums over N, outputs of solves).  Inputs are standard normal rows rounded to the
-dtype under test (no near-duplicates; the singular cases are separate), hyper-parameters (1.3, 0.4, 0.9).
+dtype under test (no near-duplicates; the singular cases below assert finiteness for every form and values for NNGP only),
+hyper-parameters (1.3, 0.4, 0.9).  What a norm over a whole gx cannot see -- one wrong pair, F_2 beside F_1, near-duplicate,
+duplicate and anti-parallel rows, where the NTK forms are held to the guarded rules' values -- is in test_gpu_input_probes.py,
+which holds both kernel entries pair by pair to a long-double reference.
 
   fp64   relerr_norm <= 1e-8, the project's fp64 kernel tolerance (tests/_tol.py).
   fp32   the yardstick is the rules evaluated in float32 against float64 on the same inputs; the device's error is held to
