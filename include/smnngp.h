@@ -966,6 +966,15 @@ int smn_pchol_step(smn_ctx* ctx, int dtype, int64_t n, int64_t j, int64_t pivot,
 int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
                   const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank, double tol_rel, void* L_d, int64_t ldl,
                   double* resid_d, int64_t* pivots_h, double* trace_h, int64_t* rank_h);
+/* smn_pchol_mlp_at: smn_pchol_mlp at PRESCRIBED pivots: step j is taken at pivots_h[j] (host, m entries in [0, n), else
+ * SMN_EINVAL; 1 <= m <= n, ldl >= m) instead of the arg-max.  The same step kernel is queued, with no host round trip and one
+ * synchronisation at the end; the pivot's residual is read behind step j - 1 and in front of step j.  The loop stops before
+ * step j when resid[pivots_h[j]] is not above the floor 4 (j + 1) eps max_i K_ii (an index listed twice, or a duplicate of an
+ * earlier pivot's row, therefore ends the factor there) or on tol_rel, as above.  At the pivots smn_pchol_mlp returned, with the
+ * same hyper-parameters, L_d, resid_d and trace_h carry that call's bits.  trace_h [m + 1], *rank_h as above. */
+int smn_pchol_mlp_at(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const int64_t* pivots_h, int64_t m, double tol_rel,
+                     void* L_d, int64_t ldl, double* resid_d, double* trace_h, int64_t* rank_h);
 
 /* ---- regression on the pivoted-Cholesky factor: GP / Student-t models at O(n m^2) work and O(n m) memory (csrc/lowrank.hip) ----
  * With L_d [n, ldl >= m] of `dtype` from smn_pchol_* and d_i = fitc max(resid_i, 0) + lambda, the model covariance is
@@ -1006,6 +1015,27 @@ int smn_lowrank_fit(smn_ctx* ctx, int dtype, const void* L_d, int64_t n, int64_t
 int smn_lowrank_readout(smn_ctx* ctx, int dtype, const void* kzt_d, int64_t ldk, const void* ktt_d, int64_t t, int64_t m,
                         const double* R_d, int64_t ldr, const double* C_d, const double* beta_d, int64_t c, void* mean_d,
                         void* var_d);
+
+/* smn_lowrank_grad (csrc/lowrank_grad.hip): the analytic hyper-parameter gradient of the low-rank model's log-marginal likelihood
+ * at FIXED pivots.  With K^ = Q + diag(mu o (k - q)) + lambda I, Q = K_nP K_PP^-1 K_Pn = L L^T, mu_i = fitc [resid_i > 0] and
+ * G = coef alpha alpha^T - c K^^-1 (the convention of smn_lml_grad_terms: d logpdf / d theta = terms / 2),
+ *   terms_h[0..2] = sum_ij G_ij dK^_ij / d(w_std, b_std, last_w_std),   terms_h[3] = tr G  (d / d lambda).
+ * The pivot SELECTION is not differentiated: the factor must have been built at pivots_h (host, m distinct indices in [0, n)),
+ * e.g. by smn_pchol_mlp_at, and x_d [n, ldx >= d], L_d [n, ldl >= m], resid_d [n] (fp64; may be NULL when fitc = 0), lambda,
+ * fitc, y_d [n, ldy >= c], C_d [m, m], beta_d [m, c] (smn_lowrank_fit's outputs for these inputs) and R_d [m, ldr >= m] =
+ * L[pivots, :] in fp64 must belong together.  net: SMN_NET_MLP or SMN_NET_DENSE_RESNET with NNGP covariance (SMN_NET_NTK:
+ * SMN_ENOTSUP); act relu or erf.  coef = 1 (Gaussian) or (df + n c) / ((df + quad / scale) scale) (Student-t).
+ * O(n m^2 + n m d) work; workspace kept by the context: two [n, m] matrices of `dtype` (X Z^T / d and U) and O(m^2) fp64.  Everything
+ * m x m is fp64 for both dtypes; the per-element tangents run in the arithmetic of `dtype`, every sum that crosses elements in
+ * fp64 in a fixed order: two calls give the same bits, and the bits depend neither on ldl, ldx nor on alignment.  b_std == 0:
+ * as smn_lml_grad_terms.  An f32 factor under fitc with a small lambda loses digits exactly as smn_lowrank_fit's quad does
+ * (pivot rows have weight 1 / lambda and kappa_i = w_i - w_i^2 h_i cancels).  SMN_EINVAL, before anything is allocated or
+ * launched: the cases of the block above, a pivot out of range or listed twice, m > n, d < 1, a coef that is not finite, fitc = 1
+ * without resid_d.  Synchronises. */
+int smn_lowrank_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                     const void* x_d, int64_t n, int64_t ldx, int64_t d, const int64_t* pivots_h, const void* L_d, int64_t m,
+                     int64_t ldl, const double* resid_d, double lambda, int fitc, const void* y_d, int64_t c, int64_t ldy,
+                     const double* C_d, const double* beta_d, const double* R_d, int64_t ldr, double coef, double* terms_h);
 
 #ifdef __cplusplus
 }

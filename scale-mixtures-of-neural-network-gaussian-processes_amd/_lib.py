@@ -166,6 +166,9 @@ PROTOTYPES = {
     "smn_lowrank_gram": [_vp, _i, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
     "smn_lowrank_fit": [_vp, _i, _vp, _i64, _i64, _i64, _vp, _d, _i, _vp, _i64, _i64, _vp, _vp, _pd, _pd, _pi],
     "smn_lowrank_readout": [_vp, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "smn_pchol_mlp_at": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _pi64, _i64, _d, _vp, _i64, _vp, _pd, _pi64],
+    "smn_lowrank_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _pi64, _vp, _i64, _i64, _vp, _d, _i, _vp, _i64,
+                         _i64, _vp, _vp, _vp, _i64, _d, _pd],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing

@@ -26,6 +26,11 @@
 //   j + 1, its residual and the trace where the next step reads them.  No floating-point atomics: two calls give the same
 //   bits, and since a partial is always 16 rows the bits do not depend on the grid either.
 //
+// Prescribed pivots (smn_pchol_mlp_at; the matrix form's host loop simply hands smn_pchol_step the given pivot): the same step
+// kernel is queued; the finish kernel between two steps writes piv[j] = given[j] and rmax[j] = resid[given[j]] in place of the
+// arg-max -- behind step j - 1 and in front of step j, so the pivot's residual is read before its own workgroup overwrites it.
+// The step kernel therefore sees the (p, r_p) it saw in the greedy run that chose these pivots, and leaves that run's bits.
+//
 // Rank: the loop stops before step j when trace_j <= tol_rel trace_0 or when the largest residual is not above
 // 4 (j + 1) eps_T max_i K_ii, eps_T the unit roundoff of the storage type: the size of the rounding error of a residual that was
 // computed from j columns stored in T (the gamma_{j+1} bound of a Cholesky's Schur complement), with a factor 4 of room.  Below
@@ -248,7 +253,9 @@ __global__ void pchol_partial_kernel(const double* __restrict__ resid, int64_t n
 __global__ void __launch_bounds__(256) pchol_finish_kernel(const double* __restrict__ pmax, const double* __restrict__ psum,
                                                            const int64_t* __restrict__ pidx, int64_t P, int jn, PcholCtl* ctl,
                                                            double* __restrict__ trace, double* __restrict__ rmax,
-                                                           int64_t* __restrict__ piv, double floor_scale) {
+                                                           int64_t* __restrict__ piv, double floor_scale,
+                                                           const int64_t* __restrict__ fixed, int nfixed,
+                                                           const double* __restrict__ resid) {
   __shared__ double sm[256], ss[256];
   __shared__ int64_t si[256];
   if (ctl->stop >= 0) return;
@@ -274,10 +281,15 @@ __global__ void __launch_bounds__(256) pchol_finish_kernel(const double* __restr
     __syncthreads();
   }
   if (t == 0) {
-    trace[jn] = ss[0]; rmax[jn] = sm[0]; piv[jn] = si[0];
+    // prescribed pivots (smn_pchol_mlp_at): step jn is taken at fixed[jn], whose residual is read here -- behind step jn - 1 and
+    // in front of step jn, whose own workgroup overwrites it; the floor and the trace are those of the greedy loop
+    const bool given = fixed != nullptr && jn < nfixed;
+    const int64_t pj = given ? fixed[jn] : si[0];
+    const double rj = given ? resid[pj] : sm[0];
+    trace[jn] = ss[0]; rmax[jn] = rj; piv[jn] = pj;
     if (jn == 0) ctl->dmax = fmax(sm[0], 0.0);
     const double floor = floor_scale * (double)(jn + 1) * ctl->dmax;
-    if (jn < ctl->max_rank && (!(sm[0] > floor) || ss[0] <= ctl->tol_rel * trace[0])) ctl->stop = jn;
+    if (jn < ctl->max_rank && (!(rj > floor) || ss[0] <= ctl->tol_rel * trace[0])) ctl->stop = jn;
   }
 }
 
@@ -337,14 +349,16 @@ __global__ void pchol_tables_kernel(const double* __restrict__ q0, int64_t n, La
 // ------------------------------------------------------------------ host side
 struct PcholWs {
   PcholCtl* ctl; double* trace; double* rmax; int64_t* piv; double* pmax; double* psum; int64_t* pidx; double* q; double* tab;
+  int64_t* fixed;   // prescribed pivots [max_rank + 1] (smn_pchol_mlp_at), else nullptr
   int64_t P;
 };
 
-int pchol_ws(smn_ctx* ctx, int64_t n, int64_t max_rank, int nsets, bool fused, PcholWs* w) {
+int pchol_ws(smn_ctx* ctx, int64_t n, int64_t max_rank, int nsets, bool fused, PcholWs* w, bool fixed = false) {
   const int64_t P = (n + kRowsPerWg - 1) / kRowsPerWg;
   const size_t m1 = (size_t)max_rank + 1;
   size_t words = 8 + 3 * m1 + 3 * (size_t)P;           // 8-byte words: ctl (padded to 64 bytes), trace, rmax, piv, the partials
   if (fused) words += (size_t)n * (size_t)(1 + 2 * nsets);
+  if (fixed) words += m1;
   void* base = nullptr;
   SMN_TRY(smn_workspace(ctx, 0, 8 * words, &base));
   double* b = static_cast<double*>(base);
@@ -357,6 +371,8 @@ int pchol_ws(smn_ctx* ctx, int64_t n, int64_t max_rank, int nsets, bool fused, P
   w->pidx = reinterpret_cast<int64_t*>(b); b += P;
   w->q = fused ? b : nullptr;
   w->tab = fused ? b + n : nullptr;
+  if (fused) b += (size_t)n * (size_t)(1 + 2 * nsets);
+  w->fixed = fixed ? reinterpret_cast<int64_t*>(b) : nullptr;
   w->P = P;
   return SMN_OK;
 }
@@ -365,9 +381,9 @@ bool aligned16(const void* p, int64_t ld, size_t es) { return reinterpret_cast<u
 
 double unit_roundoff(int dtype) { return dtype == SMN_F64 ? DBL_EPSILON : (double)FLT_EPSILON; }
 
-int launch_finish(smn_ctx* ctx, const PcholWs& w, int jn, double floor_scale) {
+int launch_finish(smn_ctx* ctx, const PcholWs& w, int jn, double floor_scale, int nfixed = 0, const double* resid = nullptr) {
   hipLaunchKernelGGL(pchol_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, w.pmax, w.psum, w.pidx, w.P, jn, w.ctl, w.trace,
-                     w.rmax, w.piv, floor_scale);
+                     w.rmax, w.piv, floor_scale, static_cast<const int64_t*>(nfixed > 0 ? w.fixed : nullptr), nfixed, resid);
   SMN_CHECK_LAUNCH(ctx);
   return SMN_OK;
 }
@@ -472,31 +488,41 @@ extern "C" int smn_pchol_step(smn_ctx* ctx, int dtype, int64_t n, int64_t j, int
   return read_back(ctx, w, 0, next_pivot_h, rmax_h, trace_h);
 }
 
-extern "C" int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
-                             double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank,
-                             double tol_rel, void* L_d, int64_t ldl, double* resid_d, int64_t* pivots_h, double* trace_h,
-                             int64_t* rank_h) {
+namespace {
+
+// The fused loop behind smn_pchol_mlp (given_h == nullptr: greedy, the pivots come back in pivots_h) and smn_pchol_mlp_at
+// (given_h [max_rank]: step j is taken at given_h[j]).
+int pchol_mlp_run(smn_ctx* ctx, const char* who, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                  double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank, double tol_rel,
+                  void* L_d, int64_t ldl, double* resid_d, int64_t* pivots_h, const int64_t* given_h, double* trace_h,
+                  int64_t* rank_h) {
   if (!ctx) return SMN_EINVAL;
-  SMN_TRY(check_pchol(ctx, "smn_pchol_mlp", dtype, n));
-  if (!x_d || !L_d || !resid_d || !pivots_h || !trace_h || !rank_h) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: NULL pointer");
-  if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: d = %lld", (long long)d);
+  SMN_TRY(check_pchol(ctx, who, dtype, n));
+  if (!x_d || !L_d || !resid_d || (!pivots_h && !given_h) || !trace_h || !rank_h) return smn_fail(ctx, SMN_EINVAL, "%s: NULL pointer", who);
+  if (d <= 0) return smn_fail(ctx, SMN_EINVAL, "%s: d = %lld", who, (long long)d);
   if (max_rank < 1 || max_rank > n || max_rank >= (int64_t)INT_MAX)
-    return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: max_rank = %lld outside [1, n = %lld]", (long long)max_rank, (long long)n);
-  if (!(tol_rel >= 0.0)) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: tol_rel = %g is negative", tol_rel);
-  SMN_CHECK_LD(ctx, "smn_pchol_mlp", ldx, d);
-  SMN_CHECK_LD(ctx, "smn_pchol_mlp", ldl, max_rank);
-  SMN_TRY(no_ntk_net(ctx, "smn_pchol_mlp", net));
-  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: unknown net %d", net);
-  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: Unsupported act %d", act);
-  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: num_hiddens < 0");
+    return smn_fail(ctx, SMN_EINVAL, "%s: max_rank = %lld outside [1, n = %lld]", who, (long long)max_rank, (long long)n);
+  if (!(tol_rel >= 0.0)) return smn_fail(ctx, SMN_EINVAL, "%s: tol_rel = %g is negative", who, tol_rel);
+  SMN_CHECK_LD(ctx, who, ldx, d);
+  SMN_CHECK_LD(ctx, who, ldl, max_rank);
+  if (given_h)
+    for (int64_t t = 0; t < max_rank; ++t)
+      if (given_h[t] < 0 || given_h[t] >= n)
+        return smn_fail(ctx, SMN_EINVAL, "%s: pivots_h[%lld] = %lld outside [0, n = %lld)", who, (long long)t, (long long)given_h[t], (long long)n);
+  SMN_TRY(no_ntk_net(ctx, who, net));
+  if (net != SMN_NET_MLP && net != SMN_NET_DENSE_RESNET) return smn_fail(ctx, SMN_EINVAL, "%s: unknown net %d", who, net);
+  if (act != SMN_ACT_RELU && act != SMN_ACT_ERF) return smn_fail(ctx, SMN_EINVAL, "%s: Unsupported act %d", who, act);
+  if (num_hiddens < 0) return smn_fail(ctx, SMN_EINVAL, "%s: num_hiddens < 0", who);
   LayerProg prog;
   prog.net = net; prog.act = act; prog.fast = 0;
   prog.nsets = net == SMN_NET_MLP ? num_hiddens : num_hiddens + 1;
-  if (prog.nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "smn_pchol_mlp: num_hiddens too large (max %d activation layers)", kMaxSets);
+  if (prog.nsets > kMaxSets) return smn_fail(ctx, SMN_ENOTSUP, "%s: num_hiddens too large (max %d activation layers)", who, kMaxSets);
   prog.w2 = w_std * w_std; prog.b2 = b_std * b_std; prog.lw2 = last_w_std * last_w_std;
   SMN_ENTER(ctx);
   PcholWs w;
-  SMN_TRY(pchol_ws(ctx, n, max_rank, prog.nsets, true, &w));
+  SMN_TRY(pchol_ws(ctx, n, max_rank, prog.nsets, true, &w, given_h != nullptr));
+  const int nfixed = given_h ? (int)max_rank : 0;
+  if (given_h) SMN_HIP(ctx, hipMemcpyAsync(w.fixed, given_h, 8 * (size_t)max_rank, hipMemcpyHostToDevice, ctx->stream));
   SMN_TRY(init_ctl(ctx, w, (int)max_rank, tol_rel));
   const double inv_d = 1.0 / (double)d;
   const double floor_scale = 4.0 * unit_roundoff(dtype);
@@ -511,7 +537,7 @@ extern "C" int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_
     hipLaunchKernelGGL(pchol_partial_kernel, dim3((unsigned)((w.P + 255) / 256)), dim3(256), 0, ctx->stream, resid_d, n, w.pmax,
                        w.psum, w.pidx);
     SMN_CHECK_LAUNCH(ctx);
-    SMN_TRY(launch_finish(ctx, w, 0, floor_scale));
+    SMN_TRY(launch_finish(ctx, w, 0, floor_scale, nfixed, resid_d));
     StepArgs<T> a{};
     a.x = static_cast<const T*>(x_d); a.n = n; a.ldx = ldx; a.d = d; a.inv_d = inv_d;
     a.x_vec = aligned16(x_d, ldx, sizeof(T)) ? 1 : 0;
@@ -522,7 +548,7 @@ extern "C" int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_
     for (int64_t j = 0; j < max_rank; ++j) {
       a.j = (int)j;
       SMN_TRY(launch_step_fused<T>(ctx, a, w.P));
-      SMN_TRY(launch_finish(ctx, w, (int)j + 1, floor_scale));
+      SMN_TRY(launch_finish(ctx, w, (int)j + 1, floor_scale, nfixed, resid_d));
     }
     return (int)SMN_OK;
   }));
@@ -534,8 +560,28 @@ extern "C" int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_
   SMN_HIP(ctx, hipMemcpyAsync(pv.data(), w.piv, 8 * pv.size(), hipMemcpyDeviceToHost, ctx->stream));
   SMN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int64_t rank = h.stop >= 0 ? h.stop : max_rank;
-  for (int64_t t = 0; t < rank; ++t) pivots_h[t] = pv[(size_t)t];
+  for (int64_t t = 0; pivots_h && t < rank; ++t) pivots_h[t] = pv[(size_t)t];
   for (int64_t t = 0; t <= rank; ++t) trace_h[t] = tr[(size_t)t];
   *rank_h = rank;
   return SMN_OK;
+}
+
+}  // namespace
+
+extern "C" int smn_pchol_mlp(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                             double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, int64_t max_rank,
+                             double tol_rel, void* L_d, int64_t ldl, double* resid_d, int64_t* pivots_h, double* trace_h,
+                             int64_t* rank_h) {
+  if (ctx && !pivots_h) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp: NULL pointer");
+  return pchol_mlp_run(ctx, "smn_pchol_mlp", dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, max_rank, tol_rel,
+                       L_d, ldl, resid_d, pivots_h, nullptr, trace_h, rank_h);
+}
+
+extern "C" int smn_pchol_mlp_at(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                                double last_w_std, const void* x_d, int64_t n, int64_t ldx, int64_t d, const int64_t* pivots_h,
+                                int64_t m, double tol_rel, void* L_d, int64_t ldl, double* resid_d, double* trace_h,
+                                int64_t* rank_h) {
+  if (ctx && !pivots_h) return smn_fail(ctx, SMN_EINVAL, "smn_pchol_mlp_at: NULL pointer");
+  return pchol_mlp_run(ctx, "smn_pchol_mlp_at", dtype, net, act, num_hiddens, w_std, b_std, last_w_std, x_d, n, ldx, d, m, tol_rel, L_d,
+                       ldl, resid_d, nullptr, pivots_h, trace_h, rank_h);
 }

@@ -2,11 +2,16 @@
 and M of its rows (csrc/pchol.hip).  The pivots are the conditional-variance choice of M inducing points, L is the Nystroem
 factor of those points, and the trace of what is left out is known after every step, so a rank can be chosen by tolerance.
 
-    res = pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto")
+    res = pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto", pivots=None)
     res.pivots, res.factor, res.resid, res.trace, res.rank, res.approx(rows, cols)
     greedy_variance_points(kernel_fn, x, m)  ->  pivots
     fit = woodbury_fit(res, y, lam, fitc)        regression on the factor (csrc/lowrank.hip): fit.quad, fit.logdet, fit.info,
     fit.readout(kzt, ktt) -> mean, var           K^ = L L^T + diag(fitc max(resid, 0) + lam) by the Woodbury identity
+    terms = woodbury_grad(fit, kernel_fn, x, coef)   sum G dK^/d(w_std, b_std, last_w_std, lam) at FIXED pivots (csrc/lowrank_grad.hip)
+
+pivots=<distinct indices>: step j is taken at pivots[j] instead of the arg-max (both routes).  The loop still stops before step j
+when resid[pivots[j]] is not above the floor below, so a later pivot that duplicates an earlier pivot's row ends the factor there.
+A factor built at the pivots a greedy call returned, at the same hyper-parameters, carries that call's bits.
 
 Routes
   "fused"   MLP / dense-ResNet kernel functions with NNGP covariance: one call (smn_pchol_mlp) queues every step; the kernel
@@ -30,8 +35,8 @@ from . import _lib
 from ._lib import DeviceArray, as_device, default_context
 from .nt_kernels import CnnKernelFn, KernelFn
 
-__all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky", "woodbury_fit", "WoodburyFit", "kernel_diag",
-           "kernel_cross"]
+__all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky", "woodbury_fit", "WoodburyFit", "woodbury_grad",
+           "kernel_diag", "kernel_cross"]
 
 _DIAG_BLOCK = 256   # rows per symmetric build when an MLP-family diagonal is taken from diagonal blocks (matrix route)
 
@@ -76,16 +81,37 @@ def _pick_route(kernel_fn, route):
     return route
 
 
-def _check(kernel_fn, x, max_rank, tol, route):
-    """Everything that can be refused without a device: returns (N, max_rank, tol, route)."""
+def _check_pivots(pivots, n):
+    """pivots as np.int64 [m]: distinct indices in [0, n)."""
+    p = np.asarray(pivots)
+    if p.ndim != 1 or p.shape[0] < 1 or not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("pivots must be a non-empty 1-D integer array, got shape %s dtype %s" % (p.shape, p.dtype))
+    p = np.ascontiguousarray(p, dtype=np.int64)
+    if p.min() < 0 or p.max() >= n:
+        raise ValueError("pivots must lie in [0, N = %d)" % n)
+    if np.unique(p).shape[0] != p.shape[0]:
+        raise ValueError("pivots must be distinct")
+    return p
+
+
+def _check(kernel_fn, x, max_rank, tol, route, pivots=None):
+    """Everything that can be refused without a device: returns (N, max_rank, tol, route[, pivots])."""
     n = _num_rows(x)
+    if pivots is not None:
+        pivots = _check_pivots(pivots, n)
+        if max_rank is not None and int(max_rank) != pivots.shape[0]:
+            raise ValueError("max_rank = %d does not equal len(pivots) = %d" % (int(max_rank), pivots.shape[0]))
+        max_rank = pivots.shape[0]
+    elif max_rank is None:
+        raise ValueError("max_rank is needed when no pivots are given")
     max_rank = int(max_rank)
     if max_rank < 1 or max_rank > n:
         raise ValueError("max_rank must lie in [1, N = %d], got %d" % (n, max_rank))
     tol = float(tol)
     if not tol >= 0.0:
         raise ValueError("tol must be >= 0, got %r" % (tol,))
-    return n, max_rank, tol, _pick_route(kernel_fn, route)
+    route = _pick_route(kernel_fn, route)
+    return (n, max_rank, tol, route) if pivots is None else (n, max_rank, tol, route, pivots)
 
 
 def _compact(ctx, factor, rank):
@@ -101,7 +127,7 @@ def _compact(ctx, factor, rank):
     return out
 
 
-def _fused(kernel_fn, x, n, max_rank, tol):
+def _fused(kernel_fn, x, n, max_rank, tol, given=None):
     xs = kernel_fn.scaled(x)
     ctx = xs.ctx
     d = xs.shape[1]
@@ -110,9 +136,15 @@ def _fused(kernel_fn, x, n, max_rank, tol):
     pivots = np.zeros(max_rank, dtype=np.int64)
     trace = np.zeros(max_rank + 1, dtype=np.float64)
     rank = C.c_int64(0)
-    ctx.call("smn_pchol_mlp", xs.dcode, kernel_fn.net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
-             kernel_fn.last_w_std, xs.ptr, n, d, d, max_rank, tol, factor.ptr, max_rank, resid.ptr,
-             pivots.ctypes.data_as(C.POINTER(C.c_int64)), trace.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rank))
+    if given is None:
+        ctx.call("smn_pchol_mlp", xs.dcode, kernel_fn.net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+                 kernel_fn.last_w_std, xs.ptr, n, d, d, max_rank, tol, factor.ptr, max_rank, resid.ptr,
+                 pivots.ctypes.data_as(C.POINTER(C.c_int64)), trace.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rank))
+    else:
+        pivots = given
+        ctx.call("smn_pchol_mlp_at", xs.dcode, kernel_fn.net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+                 kernel_fn.last_w_std, xs.ptr, n, d, d, pivots.ctypes.data_as(C.POINTER(C.c_int64)), max_rank, tol, factor.ptr,
+                 max_rank, resid.ptr, trace.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rank))
     r = int(rank.value)
     return PivotedCholesky(pivots[:r].copy(), _compact(ctx, factor, r), resid.raw_numpy(), trace[:r + 1].copy(), r)
 
@@ -160,7 +192,7 @@ def kernel_cross(kernel_fn, a, b):
     return as_device(kernel_fn(a, b), a.ctx, dtype=a.dtype)
 
 
-def _matrix(kernel_fn, x, n, max_rank, tol):
+def _matrix(kernel_fn, x, n, max_rank, tol, given=None):
     native = isinstance(kernel_fn, (KernelFn, CnnKernelFn))
     ctx = getattr(kernel_fn, "ctx", None) or (x.ctx if isinstance(x, DeviceArray) else default_context())
     xd = as_device(x, ctx)
@@ -183,7 +215,12 @@ def _matrix(kernel_fn, x, n, max_rank, tol):
     ctx.call("smn_pchol_begin", xd.dcode, n, diag.ptr, resid.ptr, C.byref(piv), C.byref(rmax), C.byref(tr))
     floor1 = 4.0 * float(np.finfo(dt).eps) * max(rmax.value, 0.0)      # the floor of step j is (j + 1) times this
     pivots, trace = [], [tr.value]
+    rp = C.c_double(0.0)
     for j in range(max_rank):
+        if given is not None:                        # the prescribed pivot and its residual stand in for the arg-max
+            piv.value = int(given[j])
+            ctx.call("smn_memcpy_d2h", C.byref(rp), C.c_void_p(resid.ptr.value + 8 * piv.value), 8)
+            rmax.value = rp.value
         if not rmax.value > (j + 1) * floor1 or trace[-1] <= tol * trace[0]:
             break
         k = row(piv.value)
@@ -199,12 +236,16 @@ def _matrix(kernel_fn, x, n, max_rank, tol):
                            np.asarray(trace, dtype=np.float64), r)
 
 
-def pivoted_cholesky(kernel_fn, x, max_rank, tol=0.0, route="auto"):
+def pivoted_cholesky(kernel_fn, x, max_rank=None, tol=0.0, route="auto", pivots=None):
     """The partial Cholesky factorisation of K(x, x) with greedy pivoting (largest residual variance, ties to the lowest
     index), up to max_rank <= N columns; x a host or a device array.  Input scales of an MLP-family kernel function are
-    applied first.  See the module docstring for the routes and the stopping rule."""
-    n, max_rank, tol, route = _check(kernel_fn, x, max_rank, tol, route)
-    return (_fused if route == "fused" else _matrix)(kernel_fn, x, n, max_rank, tol)
+    applied first.  pivots: an integer array of distinct indices in [0, N) to take, in order, instead of the greedy choice
+    (max_rank may then be omitted, or must equal len(pivots)).  See the module docstring for the routes and the stopping rule."""
+    if pivots is None:
+        n, max_rank, tol, route = _check(kernel_fn, x, max_rank, tol, route)
+        return (_fused if route == "fused" else _matrix)(kernel_fn, x, n, max_rank, tol)
+    n, max_rank, tol, route, pivots = _check(kernel_fn, x, max_rank, tol, route, pivots)
+    return (_fused if route == "fused" else _matrix)(kernel_fn, x, n, max_rank, tol, pivots)
 
 
 def greedy_variance_points(kernel_fn, x, m):
@@ -216,8 +257,8 @@ class WoodburyFit:
     """What smn_lowrank_fit leaves: quad [c] = y_k^T K^^-1 y_k, logdet = log|K^|, info (0, or the failing pivot of I + G; quad
     and logdet are then NaN), and on the device the fp64 factor C of I + L^T W L, beta = (I + G)^-1 L^T W Y and R = L[pivots, :]."""
 
-    def __init__(self, res, lam, fitc, quad, logdet, info, c_fac, beta, r_fac):
-        self.res, self.lam, self.fitc = res, float(lam), bool(fitc)
+    def __init__(self, res, lam, fitc, quad, logdet, info, c_fac, beta, r_fac, y_dev=None):
+        self.res, self.lam, self.fitc, self.y_dev = res, float(lam), bool(fitc), y_dev   # y_dev: the targets as the fit read them
         self.quad, self.logdet, self.info = quad, float(logdet), int(info)
         self.c_fac, self.beta, self.r_fac = c_fac, beta, r_fac
 
@@ -279,4 +320,49 @@ def woodbury_fit(res, y, lam, fitc=True):
         for j, p in enumerate(res.pivots):
             ctx.call("smn_memcpy_d2h", r[j].ctypes.data_as(C.c_void_p), C.c_void_p(f.ptr.value + int(p) * m * isz), m * isz)
         res._r_fac = ctx.to_device(np.tril(r).astype(np.float64))
-    return WoodburyFit(res, lam, fitc, quad, logdet.value, info.value, c_fac, beta, res._r_fac)
+    return WoodburyFit(res, lam, fitc, quad, logdet.value, info.value, c_fac, beta, res._r_fac, yd)
+
+
+def _check_grad(fit, kernel_fn, x, coef):
+    """Everything woodbury_grad can refuse without a device: returns coef."""
+    if not isinstance(fit, WoodburyFit):
+        raise TypeError("fit must be a WoodburyFit (woodbury_fit's result), got %s" % type(fit).__name__)
+    if isinstance(kernel_fn, KernelFn) and kernel_fn.cov != "nngp":
+        raise NotImplementedError("woodbury_grad has no form for with_cov(%r): SMN_NET_NTK is not supported" % (kernel_fn.cov,))
+    if not isinstance(kernel_fn, KernelFn):
+        raise NotImplementedError("woodbury_grad exists for get_mlp_kernel / get_dense_resnet_kernel with NNGP covariance, not for %s"
+                                  % type(kernel_fn).__name__)
+    if getattr(kernel_fn, "input_scales", None) is not None:
+        raise NotImplementedError("woodbury_grad does not support input scales")
+    n = int(fit.res.factor.shape[0])
+    shape = tuple(x.shape) if isinstance(x, DeviceArray) else np.shape(x)
+    if len(shape) != 2 or shape[0] != n:
+        raise ValueError("x must be [N = %d, d], got shape %s" % (n, shape))
+    coef = float(coef)
+    if not np.isfinite(coef):
+        raise ValueError("coef must be finite, got %r" % (coef,))
+    return coef
+
+
+def woodbury_grad(fit, kernel_fn, x, coef):
+    """terms [4] = sum_ij G_ij dK^_ij / d(w_std, b_std, last_w_std, lam) with G = coef alpha alpha^T - C K^^-1 (the convention of
+    smn_lml_grad_terms: d logpdf / d theta = terms / 2), for a WoodburyFit whose factor was built on x by kernel_fn at the pivots
+    fit.res.pivots.  The pivots are held FIXED: the derivative of the selection is not part of it.  One smn_lowrank_grad call,
+    O(N rank^2 + N rank d) work and O(N rank) memory.  MLP / dense-ResNet kernel functions with NNGP covariance; NaN when the fit
+    failed (fit.info != 0)."""
+    coef = _check_grad(fit, kernel_fn, x, coef)
+    if fit.info != 0:
+        return np.full(4, np.nan)
+    res = fit.res
+    f = res.factor
+    ctx, (n, m) = f.ctx, f.shape
+    xd = as_device(x, ctx, dtype=f.dtype)
+    d, c = xd.shape[1], fit.beta.shape[1]
+    resid = ctx.to_device(np.ascontiguousarray(res.resid, dtype=np.float64)) if fit.fitc else None
+    piv = np.ascontiguousarray(res.pivots, dtype=np.int64)
+    terms = np.zeros(4, dtype=np.float64)
+    ctx.call("smn_lowrank_grad", f.dcode, kernel_fn.net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+             kernel_fn.last_w_std, xd.ptr, n, d, d, piv.ctypes.data_as(C.POINTER(C.c_int64)), f.ptr, m, m,
+             None if resid is None else resid.ptr, fit.lam, 1 if fit.fitc else 0, fit.y_dev.ptr, c, c, fit.c_fac.ptr, fit.beta.ptr,
+             fit.r_fac.ptr, m, coef, terms.ctypes.data_as(C.POINTER(C.c_double)))
+    return terms

@@ -509,8 +509,19 @@ class LowRankSPR(Module):
     rank: columns asked for (1 <= rank <= N, at most 4096); tol: stop early when the residual trace falls to tol trace(K).
     Every kernel function pivoted_cholesky accepts works.  The factor is kept while the hyper-parameters do not change.
     An fp32 model under "fitc" loses digits in loss() as eps shrinks (pivot rows weigh 1 / eps: 1.3e-6 relative at
-    eps >= 1e-2, 6.5e-5 at 1e-4, 2.8e-2 at 1e-6): use fp64 data or correction="none" there.  loss_and_grad, the leave-one-out
-    entries, posterior(), sample_posterior and input scales are not implemented."""
+    eps >= 1e-2, 6.5e-5 at 1e-4, 2.8e-2 at 1e-6): use fp64 data or correction="none" there.  The leave-one-out entries,
+    posterior(), sample_posterior and input scales are not implemented.
+
+    Frozen pivots.  By default every call selects its pivots greedily at the current hyper-parameters, so loss() is only piecewise
+    smooth in them and has no gradient.  freeze_pivots() keeps the inducing set -- the greedy choice at the current values, or
+    an array of indices -- until refresh_pivots() re-selects it or unfreeze_pivots() goes back to greedy: loss, predict and
+    test_nll then build the factor at those pivots (lowrank.pivoted_cholesky(pivots=...)), loss() is smooth, and
+    loss_and_grad() returns it with its analytic gradient in the raw values of w_std, b_std, last_w_std, eps and the Student-t
+    head's a and b (lowrank.woodbury_grad, csrc/lowrank_grad.hip; MLP / dense-ResNet kernels with NNGP covariance), which
+    train.build_train_step(method="auto" | "analytic") then uses.  The gradient is that of the frozen objective: the selection
+    itself is not differentiated.  The fp32 limit of loss() under "fitc" at small eps holds for the gradient too."""
+
+    _frozen_pivots = None                            # class-level default: not frozen (objects made by __new__ included)
 
     def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, rank, correction="fitc", eps: float = 1e-6,
                  tol: float = 0.0):
@@ -548,8 +559,63 @@ class LowRankSPR(Module):
     def _missing(self, what):
         raise NotImplementedError("LowRankSPR has no %s: the exact models (SPR) do" % what)
 
+    # ---- frozen pivots
+    @property
+    def pivots(self):
+        """The frozen pivots (np.int64, a copy) or None."""
+        p = self._frozen_pivots
+        return None if p is None else p.copy()
+
+    def freeze_pivots(self, pivots=None):
+        """Keep the inducing set: the greedy selection at the current hyper-parameters (None), or the given distinct indices.
+        Right after freeze_pivots() loss, predict and test_nll return the bits they returned before it.  Returns self."""
+        if pivots is None:
+            self._frozen_pivots = None
+            pivots = self._factor()[1].pivots
+        else:
+            pivots = self._lowrank._check_pivots(pivots, self.num_data)
+            if pivots.shape[0] > min(self.num_data, _lib.LOWRANK_MAX_RANK):
+                raise ValueError("at most %d pivots, got %d" % (min(self.num_data, _lib.LOWRANK_MAX_RANK), pivots.shape[0]))
+        self._frozen_pivots = np.array(pivots, dtype=np.int64)
+        return self
+
+    def refresh_pivots(self):
+        """Re-select the frozen pivots greedily at the current hyper-parameters.  Returns self."""
+        return self.freeze_pivots(None)
+
+    def unfreeze_pivots(self):
+        """Back to a greedy selection on every call.  Returns self."""
+        self._frozen_pivots = None
+        return self
+
     def loss_and_grad(self):
-        self._missing("analytic gradient (train.build_train_step(method='auto') falls back to central differences)")
+        """(loss, {variable name: d loss / d RAW value}) of the FROZEN model, as SPR.loss_and_grad returns them: the loss is
+        loss()'s value (same bits); the gradient holds the pivots fixed.  NotImplementedError while the pivots are not frozen
+        (the greedy objective has no gradient) and for kernel functions outside the MLP / dense-ResNet NNGP family."""
+        if self._frozen_pivots is None:
+            self._missing("analytic gradient while the pivots are not frozen: call freeze_pivots() first "
+                          "(train.build_train_step(method='auto') falls back to central differences)")
+        kernel_fn = self.kernel.get_kernel_fn()
+        if not (isinstance(kernel_fn, KernelFn) and kernel_fn.cov == "nngp"):
+            raise NotImplementedError("LowRankSPR.loss_and_grad needs an MLP / dense-ResNet KernelFn with NNGP covariance; "
+                                      "use train.value_and_grad_fd")
+        _, _, fit = self._fit(False)
+        if fit.info != 0:
+            nan = float("nan")
+            return nan, {k: nan for k in self.vars()}
+        n = self.num_data
+        df, scale = self.likelihood.lml_params()
+        student = df > 0.0
+        quad = float(fit.quad[0])
+        coef = (df + n) / ((df + quad / scale) * scale) if student else 1.0
+        terms = self._lowrank.woodbury_grad(fit, kernel_fn, self.x_data, coef)
+        lp, dlp = lml_value_and_grads(terms, quad, fit.logdet, n, df, scale,
+                                      self.likelihood.a.safe_value if student else None,
+                                      self.likelihood.b.safe_value if student else None)
+        owners = {"w_std": self.kernel.w_std, "b_std": self.kernel.b_std, "last_w_std": self.kernel.last_w_std, "eps": self.eps}
+        if student:
+            owners.update(a=self.likelihood.a, b=self.likelihood.b)
+        return -lp / n, _raw_grads(self, {key: (owners[key], g) for key, g in dlp.items()}, -n)
 
     def loo_loss(self):
         self._missing("leave-one-out objective")
@@ -570,11 +636,19 @@ class LowRankSPR(Module):
     def _factor(self):
         kernel_fn = self.kernel.get_kernel_fn()
         params = getattr(kernel_fn, "params", None)
+        frozen = self._frozen_pivots
         key = None if params is None else (type(kernel_fn).__name__, getattr(kernel_fn, "entry", None),
-                                           getattr(kernel_fn, "cov", None), tuple(params))
+                                           getattr(kernel_fn, "cov", None), tuple(params),
+                                           None if frozen is None else frozen.tobytes())
         hit = self._factor_cache
+        if hit is not None and key is not None and frozen is not None and hit[0] == key[:4] + (None,) \
+                and np.array_equal(hit[1].pivots, frozen):
+            hit = self._factor_cache = (key, hit[1], hit[2])   # the greedy factor these pivots came from: the same bits, kept
         if hit is None or key is None or hit[0] != key:
-            res = self._lowrank.pivoted_cholesky(kernel_fn, self.x_data, self.rank, tol=self.tol)
+            if frozen is None:
+                res = self._lowrank.pivoted_cholesky(kernel_fn, self.x_data, self.rank, tol=self.tol)
+            else:
+                res = self._lowrank.pivoted_cholesky(kernel_fn, self.x_data, tol=self.tol, pivots=frozen)
             hit = self._factor_cache = (key, res, {})
         return kernel_fn, hit[1], hit[2]
 

@@ -102,7 +102,9 @@ def build_train_step(model, variables=None, optimizer=None, h=1e-4, method="auto
     """train_step(learning_rate) -> loss before the update  (regression/train.py:61-67).
     method: "analytic" (SPR.loss_and_grad), "fd" (central differences) or "auto" (analytic when the model's
     kernel / likelihood support it -- MLP, dense-ResNet and get_cnn_kernel kernels with images of up to 1024 pixels --
-    else finite differences: the conv ResNet, the pooled conv kernel, larger images).
+    else finite differences: the conv ResNet, the pooled conv kernel, larger images).  A LowRankSPR is trained analytically
+    once its pivots are frozen (model.freeze_pivots(); the gradient holds them fixed, refresh_pivots() re-selects them between
+    steps) and by central differences otherwise.
     objective: "lml" (the negative log-marginal likelihood: model.loss / model.loss_and_grad) or "loo" (the negative
     leave-one-out predictive log-probability: model.loo_loss / model.loo_loss_and_grad)."""
     if method not in ("auto", "analytic", "fd"):
