@@ -1037,6 +1037,52 @@ int smn_lowrank_grad(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens,
                      int64_t ldl, const double* resid_d, double lambda, int fitc, const void* y_d, int64_t c, int64_t ldy,
                      const double* C_d, const double* beta_d, const double* R_d, int64_t ldr, double coef, double* terms_h);
 
+/* ---- matrix-free exact GP: the kernel matrix applied to vectors, never stored (csrc/kernel_matmul.hip, csrc/pcg.hip) ----
+ * smn_kernel_mlp_matmul: out_d [n1, ldo >= t] (fp64 for both dtypes) = K(x1, x2) V, V = v_d [n2, ldv >= t] of `dtype`, K the
+ *   kernel of smn_kernel_mlp (SMN_NET_MLP or SMN_NET_DENSE_RESNET, relu or erf; SMN_NET_NTK OR-ed into net: K is Theta).
+ *   x2_d == NULL is the symmetric form: n2 and ldx2 are ignored, V has n1 rows, the diagonal of K is the closed-form exact one,
+ *   and out = K(x1, x1) V + shift V, the shift added in fp64 after the reduction (never folded into a `dtype` diagonal entry).
+ *   In the cross form shift must be 0.  Each 128x128 tile of K is made in registers by the main loop and the epilogue of the
+ *   fused build and multiplied by its 128 rows of V on the MFMA of `dtype`; it never reaches memory.  The contraction is cut into
+ *   splits of SMN_MATMUL_SPLIT rows of V: one split accumulates in the MFMA's precision, the splits are added in fp64 in ascending
+ *   order.  No floating-point atomics: out[i, k] depends on x1, x2, V[:, k] and the hyper-parameters alone -- not on t or the
+ *   other columns, not on ldx*, ldv, ldo or the alignment of any base, not on a grid or an earlier call.  Any t >= 1: one pass
+ *   holds SMN_MATMUL_PASS columns, further columns go in further passes, each of which recomputes the Gram tiles (cost:
+ *   ceil(t / SMN_MATMUL_PASS) builds of the n1 x n2 rectangle; K = K^T is not exploited).  Workspace, kept by the context:
+ *   the padded operands, the per-row tables and the split partials [splits, n1, t] in fp64, all acquired before the first
+ *   launch.  With b_std == 0, zero rows and duplicate rows give finite values, as the build does.  No synchronisation.
+ *   SMN_EINVAL, before anything is allocated or launched: a NULL pointer where one is needed, n1, n2 (cross form), d or t below
+ *   1, a leading dimension below its extent, a bad dtype, net or act, a shift that is not finite or not 0 in the cross form.
+ *   SMN_ENOTSUP: more than 16 activation layers. */
+#define SMN_MATMUL_SPLIT 4096
+#define SMN_MATMUL_PASS 16
+int smn_kernel_mlp_matmul(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std,
+                          double last_w_std, const void* x1_d, int64_t n1, int64_t ldx1, const void* x2_d, int64_t n2,
+                          int64_t ldx2, int64_t d, double shift, const void* v_d, int64_t t, int64_t ldv, double* out_d,
+                          int64_t ldo);
+
+/* smn_pcg_solve: block preconditioned conjugate gradients on (K(x, x) + lambda I) X = B, K applied by smn_kernel_mlp_matmul (same
+ *   net / act / dtype rules), x_d [n, ldx >= d] of `dtype`, b_d [n, ldb >= c] and sol_d [n, lds >= c] fp64, 1 <= c <= 48.
+ *   Preconditioner M = L L^T + lambda I with L_d [n, ldl >= m] of `dtype` from smn_pchol_*, 0 <= m <= min(n, SMN_LOWRANK_MAX_RANK);
+ *   L_d == NULL or m == 0: M = lambda I.  M^-1 r = (r - L (lambda I + L^T L)^-1 L^T r) / lambda; the m x m matrix is formed once per
+ *   call and factored by smn_cholesky in fp64; everything m x m is fp64.
+ *   c independent CG recurrences (each column its own alpha and beta) share one K-apply per iteration; the direction is cast to
+ *   `dtype` for it, every vector (X, R, Z, P) and every inner product is fp64, summed in a fixed order: two calls give the same
+ *   bits.  A column stops when its recurrence residual has |r_k| <= tol |b_k| (its iteration count goes to col_iters_h[k], its
+ *   direction leaves the shared K-apply); a zero b_k gives x_k = 0 at iteration 0; the loop ends when every column has stopped or
+ *   at max_iter.  warm != 0: sol_d is read as the start.  *iters_h: iterations run.  resid_h [c]: the TRUE relative residuals
+ *   |b_k - (K + lambda I) x_k| / |b_k| of the returned solution, from one further K-apply (0 for a zero b_k).  hist_h, if given,
+ *   [(max_iter + 1), c]: the recurrence's relative residual per iteration and column (a stopped column keeps its last value;
+ *   iterations not run are NaN).  *info_h: 0 every column stopped on tol; 1 max_iter was reached (the solution so far is
+ *   returned and finite); 2 breakdown -- p^T K~ p <= 0 or a scalar that is not finite -- and sol_d, resid_h are NaN.  The return
+ *   value is SMN_OK in all three cases, as smn_lml does.  SMN_EINVAL as smn_kernel_mlp_matmul, and for lambda not positive and
+ *   finite, tol outside (0, 1), max_iter < 1, m < 0, m > n, ldl < m, c < 1; SMN_ENOTSUP for c > 48 and m above
+ *   SMN_LOWRANK_MAX_RANK.  Workspace, kept by the context: six [n, c] vectors and the m x m factor.  Synchronises. */
+int smn_pcg_solve(smn_ctx* ctx, int dtype, int net, int act, int num_hiddens, double w_std, double b_std, double last_w_std,
+                  const void* x_d, int64_t n, int64_t ldx, int64_t d, double lambda, const void* L_d, int64_t m, int64_t ldl,
+                  const double* b_d, int64_t c, int64_t ldb, double tol, int max_iter, int warm, double* sol_d, int64_t lds,
+                  int* iters_h, int* col_iters_h, double* resid_h, double* hist_h, int* info_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ GET_NNGP, GET_NTK = 1, 2
 FILL_FULL, FILL_LOWER = 0, 1
 NET_MLP, NET_DENSE_RESNET = 0, 1
 LOWRANK_MAX_RANK, LOWRANK_SPLIT = 4096, 512   # SMN_LOWRANK_MAX_RANK, SMN_LOWRANK_SPLIT (include/smnngp.h)
+MATMUL_SPLIT, MATMUL_PASS, PCG_MAX_COLS = 4096, 16, 48   # SMN_MATMUL_SPLIT, SMN_MATMUL_PASS; right-hand sides of smn_pcg_solve
 NET_NTK = 0x100   # SMN_NET_NTK: OR-ed into `net`, the model entries then work on Theta instead of K (include/smnngp.h)
 
 
@@ -169,6 +170,9 @@ PROTOTYPES = {
     "smn_pchol_mlp_at": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _pi64, _i64, _d, _vp, _i64, _vp, _pd, _pi64],
     "smn_lowrank_grad": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _pi64, _vp, _i64, _i64, _vp, _d, _i, _vp, _i64,
                          _i64, _vp, _vp, _vp, _i64, _d, _pd],
+    "smn_kernel_mlp_matmul": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64],
+    "smn_pcg_solve": [_vp, _i, _i, _i, _i, _d, _d, _d, _vp, _i64, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _d, _i, _i, _vp,
+                      _i64, _pi, _pi, _pd, _pd, _pi],
 }
 for _name, _args in PROTOTYPES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == a symbol the header declares is missing

@@ -35,7 +35,7 @@ struct smn_ctx {
   size_t ev_pool_used = 0;
   std::string err;
   // cached workspace arenas (grown on demand, freed with the context)
-  static constexpr int kSlots = 16;   // 12, 13: the leave-one-out head (loo.hip); 14, 15: eigensolver and smn_predict_gd (eigh.hip)
+  static constexpr int kSlots = 19;   // 12, 13: the leave-one-out head (loo.hip); 14, 15: eigensolver and smn_predict_gd (eigh.hip); 16: kernel_matmul.hip; 17, 18: pcg.hip
   void* ws[kSlots] = {};
   size_t ws_bytes[kSlots] = {};
   // small device scalar block: [0..15] doubles scratch, ints after

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <vector>
 
+#include "build_tile.hpp"
 #include "gemm_nt.hpp"
 #include "internal.hpp"
 #include "layer_prog.hpp"
@@ -143,31 +144,7 @@ __global__ void table_trace_kernel(const T* __restrict__ dg, int64_t n, double* 
 }
 
 // ------------------------------------------------------------------ fused Gram + recursion
-template <typename T>
-struct BuildArgs {
-  const T* x1; const T* x2; int64_t ld1, ld2; int kp;
-  int tiles_n; int tiles_m; int symmetric; int mirror;
-  int lower_skip;             // rectangular grid: drop tiles lying wholly above the global diagonal
-  const T* tab1; const T* tab2; int64_t ldt1, ldt2; const T* dg; const T* dgt;
-  T inv_d; LayerProg prog;
-  int64_t row_off, col_off; int exact_diag;
-  int store_mode; int64_t out_rows, out_cols; int64_t nv0, aug0, nv1;
-  T* out_k; T* out_t; int64_t ldo;
-  int use_map; TileMap map;   // XCD-aware patch order (gemm_nt.hpp)
-  // paired lower-block shard (smn_kernel_mlp_shard): two trapezoids of row tiles, each packed into its own
-  // output with its own leading dimension; operands and tables are the symmetric ones
-  int shard; int sh_b0[2]; int sh_cnt0; T* sh_k[2]; T* sh_t[2]; int64_t sh_ld[2]; int64_t sh_cols[2];
-  // cyclic column-first shard (smn_kernel_mlp_shard_cols, shard == 2): the rank's tile rows are t_j = j P + (j even ? rank :
-  // P-1-rank), every lower tile of them, stored into the rank's chunk piece by piece (a piece = the tile columns
-  // [cy_c[g], cy_c[g+1]) of every tile row from cy_c[g] down, cy_c[g] a multiple of P): slot (j - cy_c[g]/P) of piece g is a
-  // 128 x (width of the piece) strip.  sh_k[0] / sh_t[0] are the chunk bases.
-  int cy_P, cy_rank, cy_T, cy_np; int cy_c[kMaxColPieces + 1]; int64_t cy_off[kMaxColPieces];
-  // batched build (smn_spr_loss_batch / smn_spr_predict_batch): problem blockIdx.y = the same operands under its own layer
-  // program progs[y] (same net, act and depth; its own w, b, last_w), its own table block and its own output matrix
-  const LayerProg* progs; int64_t tab_bs, out_bs; int nbatch;
-  // explicit tile order (split build): tile l = tlist[l] = tr | tc << 16, dealt to the XCDs in equal contiguous shares like the map
-  const int* tlist; int tlist_n;
-};
+// (BuildArgs, the argument block of every build launch, and build_epilogue, the tile epilogue: build_tile.hpp)
 
 // BM = 64 (f32 launches of few tiles: a rank's share of a sharded build, small kernels): two workgroups per 128x128 tile, 64
 // rows each -- at about one tile per CU a launch ends in a tail as long as a tile; halves end in half of it.
@@ -192,7 +169,6 @@ template <typename T, int NET, int ACT, bool NTK, int BM, int GC>
 __device__ __forceinline__ void build_body(const BuildArgs<T>& a, T* __restrict__ g0, bool store_acc) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Tile = TileNT<T, BM, kTile, SMN_STAGES>;
-  using M = typename Tile::M;
   static_assert(BM == kTile || BM == 64, "row tile: 128 or 64");
   int tr, tc, half = 0;
   T* out_k = a.out_k; T* out_t = a.out_t;
@@ -275,7 +251,7 @@ __device__ __forceinline__ void build_body(const BuildArgs<T>& a, T* __restrict_
     return o >= a.nv0 && !(a.nv1 > 0 && o < a.aug0 + a.nv1 && o + kTile > a.aug0);
   };
   const bool dead = a.store_mode == STORE_PAD_IDENTITY && (no_valid(row0) || no_valid(col0));
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   typename Tile::acc_t* gacc = nullptr;
   if (GC != GRAM_NONE)
     gacc = reinterpret_cast<typename Tile::acc_t*>(g0 + ((int64_t)tr * (tr + 1) / 2 + tc) * (kTile * kTile) + half * (BM * kTile)) + tid;
@@ -296,111 +272,37 @@ __device__ __forceinline__ void build_body(const BuildArgs<T>& a, T* __restrict_
       for (int n = 0; n < Tile::NT; ++n) gacc[(m * Tile::NT + n) * 256] = t.acc[m][n];
   }
 
-  const int wr = wave >> 1, wc = wave & 1;
-  ElemProg<T, NET, ACT, NTK> prog(a.prog);
-  const int nsets = a.prog.nsets;
-  // (locals, not writes into `a`: a kernel argument that is written gets a private copy in scratch)
-  const T* tab1 = a.tab1; const T* tab2 = a.tab2; const T* dgp = a.dg; const T* dgtp = a.dgt;
   if (a.progs) {
-    prog = ElemProg<T, NET, ACT, NTK>(a.progs[blockIdx.y]);
-    const int64_t tb = (int64_t)blockIdx.y * a.tab_bs, ob = (int64_t)blockIdx.y * a.out_bs;
-    tab1 += tb; tab2 += tb; dgp += tb; dgtp += tb;
+    const int64_t ob = (int64_t)blockIdx.y * a.out_bs;
     if (out_k) out_k += ob;
     if (out_t) out_t += ob;
   }
-
-  // stage the per-row / per-column layer tables of this tile in LDS (mainloop ended on a barrier)
-  constexpr bool FAST = ElemProg<T, NET, ACT, NTK>::FAST;
-  const int trows = nsets * 2 + (FAST ? 1 : 0);   // FAST: one more row, sigma (kept in the NTK-diagonal slot)
-  T* srow = reinterpret_cast<T*>(smem);
-  T* scol = srow + trows * kTile;
-  for (int idx = tid; idx < trows * kTile; idx += 256) {
-    const int s2 = idx / kTile, r = idx % kTile;
-    const int g2 = s2 < nsets * 2 ? s2 : nsets * 2 + 1;
-    if (r < BM) srow[idx] = tab1[(int64_t)g2 * a.ldt1 + row0 + r];
-    scol[idx] = tab2[(int64_t)g2 * a.ldt2 + col0 + r];
-  }
-  __syncthreads();
-
-  typename Tile::acc_t th[Tile::MT][Tile::NT];
-#pragma unroll
-  for (int m = 0; m < Tile::MT; ++m)
-#pragma unroll
-    for (int n = 0; n < Tile::NT; ++n)
-#pragma unroll
-      for (int i = 0; i < M::ACC; ++i) {
-        T k = t.acc[m][n][i] * a.inv_d;
-        T h = T(0);
-        prog.pre(k, h);
-        t.acc[m][n][i] = k;
-        th[m][n][i] = h;
-      }
-
-  for (int s = 0; s < nsets; ++s) {
-    const T* sr = srow + s * 2 * kTile;
-    const T* sc = scol + s * 2 * kTile;
-    T cr[Tile::NT], cs[Tile::NT];
-#pragma unroll
-    for (int n = 0; n < Tile::NT; ++n) {
-      const int lc = wc * Tile::WN + n * M::TN + M::acc_col(lane);
-      cr[n] = sc[lc];
-      cs[n] = sc[kTile + lc];
-    }
-#pragma unroll
-    for (int m = 0; m < Tile::MT; ++m)
-#pragma unroll
-      for (int i = 0; i < M::ACC; ++i) {
-        const int lr = wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
-        const T ri = sr[lr], si = sr[kTile + lr];
-#pragma unroll
-        for (int n = 0; n < Tile::NT; ++n) {
-          T k = t.acc[m][n][i], h = th[m][n][i];
-          prog.step(s, k, h, ri * cr[n], si * cs[n]);
-          t.acc[m][n][i] = k;
-          th[m][n][i] = h;
-        }
-      }
-  }
-
   const bool do_mirror = a.symmetric && a.mirror && tr != tc;
-#pragma unroll
-  for (int m = 0; m < Tile::MT; ++m)
-#pragma unroll
-    for (int n = 0; n < Tile::NT; ++n)
-#pragma unroll
-      for (int i = 0; i < M::ACC; ++i) {
-        const int64_t gr = row0 + wr * Tile::WM + m * M::TM + M::acc_row(lane, i);
-        const int64_t gc = col0 + wc * Tile::WN + n * M::TN + M::acc_col(lane);
-        T k = t.acc[m][n][i], h = th[m][n][i];
-        T sig = T(0);
-        if (FAST)
-          sig = srow[nsets * 2 * kTile + (int)(gr - row0)] * scol[nsets * 2 * kTile + (int)(gc - col0)];
-        prog.post(k, h, sig);
-        if (a.exact_diag && gr + a.row_off == gc + a.col_off) {
-          k = dgp[gr];
-          if (NTK) h = dgtp[gr];
-        }
-        bool wr_ok;
-        if (a.store_mode == STORE_PAD_IDENTITY) {
-          const bool vr = gr < a.nv0 || (gr >= a.aug0 && gr < a.aug0 + a.nv1);
-          const bool vc = gc < a.nv0 || (gc >= a.aug0 && gc < a.aug0 + a.nv1);
-          if (!(vr && vc)) {
-            k = (gr == gc) ? T(1) : T(0);
-            h = k;
-          }
-          wr_ok = true;
-        } else {
-          wr_ok = gr < a.out_rows && gc < out_cols;
-        }
-        if (wr_ok) {
-          if (out_k) out_k[gr * ldo + gc] = k;
-          if (NTK && out_t) out_t[gr * ldo + gc] = h;
-        }
-        if (do_mirror && gc < a.out_rows && gr < out_cols) {
-          if (out_k) out_k[gc * ldo + gr] = k;
-          if (NTK && out_t) out_t[gc * ldo + gr] = h;
-        }
+  // (locals captured by value: fields of `a` read through the closure are reloaded behind every store)
+  const bool pad_identity = a.store_mode == STORE_PAD_IDENTITY;
+  const int64_t nv0 = a.nv0, aug0 = a.aug0, nv1 = a.nv1, out_rows = a.out_rows;
+  build_epilogue<T, NET, ACT, NTK, BM>(a, t, row0, col0, smem, [=](int, int, int, int64_t gr, int64_t gc, T k, T h) {
+    bool wr_ok;
+    if (pad_identity) {
+      const bool vr = gr < nv0 || (gr >= aug0 && gr < aug0 + nv1);
+      const bool vc = gc < nv0 || (gc >= aug0 && gc < aug0 + nv1);
+      if (!(vr && vc)) {
+        k = (gr == gc) ? T(1) : T(0);
+        h = k;
       }
+      wr_ok = true;
+    } else {
+      wr_ok = gr < out_rows && gc < out_cols;
+    }
+    if (wr_ok) {
+      if (out_k) out_k[gr * ldo + gc] = k;
+      if (NTK && out_t) out_t[gr * ldo + gc] = h;
+    }
+    if (do_mirror && gc < out_rows && gr < out_cols) {
+      if (out_k) out_k[gc * ldo + gr] = k;
+      if (NTK && out_t) out_t[gc * ldo + gr] = h;
+    }
+  });
 }
 
 template <typename T, int NET, int ACT, bool NTK, int BM = kTile>
@@ -1043,6 +945,36 @@ int recursion_batch_t(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const dou
 }
 
 }  // namespace
+
+// The table stage of run_build_t alone, for a launch that is not a build (kernel_matmul.hip): same kernel, same slot, same layout.
+int layer_tables(smn_ctx* ctx, const BuildSpec& spec, bool ntk, const double* q1, int64_t rows1, const double* q2, int64_t rows2,
+                 LayerTables* out) {
+  LayerProg prog;
+  SMN_TRY(make_prog(ctx, spec, &prog));
+  if (prog.net == NET_NONE) return smn_fail(ctx, SMN_EINVAL, "layer_tables: a bare Gram has no tables");
+  return by_dtype(spec.dtype, [&](auto e) {
+    using T = decltype(e);
+    set_fast<T>(&prog, ntk);
+    const int trows = 2 * prog.nsets + 2;
+    const int64_t tlen = rows1 + rows2;
+    void* tabv = nullptr;
+    SMN_TRY(smn_workspace(ctx, 1, sizeof(T) * (size_t)trows * (size_t)tlen, &tabv));
+    T* tab1 = static_cast<T*>(tabv);
+    T* dg1 = tab1 + (int64_t)(2 * prog.nsets) * tlen;
+    T* dgt1 = dg1 + tlen;
+    hipLaunchKernelGGL(diag_tables_kernel<T>, dim3((unsigned)((rows1 + 255) / 256)), dim3(256), 0, ctx->stream, q1, rows1, prog, tab1,
+                       tlen, dg1, dgt1, static_cast<const LayerProg*>(nullptr), (int64_t)0);
+    SMN_CHECK_LAUNCH(ctx);
+    if (rows2 > 0) {
+      hipLaunchKernelGGL(diag_tables_kernel<T>, dim3((unsigned)((rows2 + 255) / 256)), dim3(256), 0, ctx->stream, q2, rows2, prog,
+                         tab1 + rows1, tlen, dg1 + rows1, dgt1 + rows1, static_cast<const LayerProg*>(nullptr), (int64_t)0);
+      SMN_CHECK_LAUNCH(ctx);
+    }
+    out->prog = prog;
+    out->tab1 = tab1; out->tab2 = rows2 > 0 ? tab1 + rows1 : tab1; out->ldt = tlen; out->dg = dg1; out->dgt = dgt1;
+    return (int)SMN_OK;
+  });
+}
 
 int recursion_lower_batch(smn_ctx* ctx, const BuildSpec& spec, int nbatch, const double* w_std, const double* b_std,
                           const double* last_w_std, const void* k0_d, int64_t n, int64_t ldk0, const void* q_d, void* out_d,

@@ -8,6 +8,8 @@ factor of those points, and the trace of what is left out is known after every s
     fit = woodbury_fit(res, y, lam, fitc)        regression on the factor (csrc/lowrank.hip): fit.quad, fit.logdet, fit.info,
     fit.readout(kzt, ktt) -> mean, var           K^ = L L^T + diag(fitc max(resid, 0) + lam) by the Woodbury identity
     terms = woodbury_grad(fit, kernel_fn, x, coef)   sum G dK^/d(w_std, b_std, last_w_std, lam) at FIXED pivots (csrc/lowrank_grad.hip)
+    out = kernel_matmul(kernel_fn, x1, x2, v, shift=0.0)     K(x1, x2) V (+ shift V) without K (csrc/kernel_matmul.hip)
+    sol = pcg_solve(kernel_fn, x, b, lam, precond=res)       (K + lam I) X = B by preconditioned CG (csrc/pcg.hip): a PcgResult
 
 pivots=<distinct indices>: step j is taken at pivots[j] instead of the arg-max (both routes).  The loop still stops before step j
 when resid[pivots[j]] is not above the floor below, so a later pivot that duplicates an earlier pivot's row ends the factor there.
@@ -36,7 +38,7 @@ from ._lib import DeviceArray, as_device, default_context
 from .nt_kernels import CnnKernelFn, KernelFn
 
 __all__ = ["pivoted_cholesky", "greedy_variance_points", "PivotedCholesky", "woodbury_fit", "WoodburyFit", "woodbury_grad",
-           "kernel_diag", "kernel_cross"]
+           "kernel_diag", "kernel_cross", "kernel_matmul", "pcg_solve", "PcgResult"]
 
 _DIAG_BLOCK = 256   # rows per symmetric build when an MLP-family diagonal is taken from diagonal blocks (matrix route)
 
@@ -366,3 +368,132 @@ def woodbury_grad(fit, kernel_fn, x, coef):
              None if resid is None else resid.ptr, fit.lam, 1 if fit.fitc else 0, fit.y_dev.ptr, c, c, fit.c_fac.ptr, fit.beta.ptr,
              fit.r_fac.ptr, m, coef, terms.ctypes.data_as(C.POINTER(C.c_double)))
     return terms
+
+
+def _check_matrix_free(kernel_fn):
+    """kernel_matmul / pcg_solve exist for the MLP family alone; refused before any device call."""
+    if not isinstance(kernel_fn, KernelFn):
+        raise NotImplementedError("the matrix-free product exists for get_mlp_kernel / get_dense_resnet_kernel (NNGP or with_cov('ntk')), "
+                                  "not for %s: a matrix-free conv kernel costs P times more per pair" % type(kernel_fn).__name__)
+
+
+def _shape2(a, what):
+    shape = tuple(a.shape) if isinstance(a, DeviceArray) else np.shape(a)
+    if len(shape) < 2 or shape[0] < 1 or int(np.prod(shape[1:])) < 1:
+        raise ValueError("%s must be [N, d] with N, d >= 1, got shape %s" % (what, shape))
+    return int(shape[0]), int(np.prod(shape[1:]))
+
+
+def _check_matmul(kernel_fn, x1, x2, v, shift):
+    """Everything kernel_matmul can refuse without a device: returns (n1, n2, t, shift)."""
+    _check_matrix_free(kernel_fn)
+    n1, d = _shape2(x1, "x1")
+    n2 = n1
+    if x2 is not None:
+        n2, d2 = _shape2(x2, "x2")
+        if d2 != d:
+            raise ValueError("x1 and x2 feature dimensions differ: %d vs %d" % (d, d2))
+    vs = tuple(v.shape) if isinstance(v, DeviceArray) else np.shape(v)
+    if len(vs) == 1:
+        vs = (vs[0], 1)
+    if len(vs) != 2 or vs[0] != n2 or vs[1] < 1:
+        raise ValueError("v must be [%d] or [%d, t] with t >= 1, got shape %s" % (n2, n2, vs))
+    shift = float(shift)
+    if not np.isfinite(shift):
+        raise ValueError("shift must be finite, got %r" % (shift,))
+    if x2 is not None and shift != 0.0:
+        raise ValueError("shift belongs to the symmetric form (x2=None), got shift = %r with x2 given" % (shift,))
+    return n1, n2, int(vs[1]), shift
+
+
+def kernel_matmul(kernel_fn, x1, x2, v, shift=0.0):
+    """K(x1, x2) V as a device fp64 array [n1, t], K never stored (smn_kernel_mlp_matmul): the covariance mode of an MLP /
+    dense-ResNet kernel function (with_cov("ntk"): Theta), input scales applied first.  x2=None is the symmetric form on the
+    exact diagonal, K(x1, x1) V + shift V with the shift added in fp64.  v [n2] or [n2, t] is taken in the dtype of x1.  Cost:
+    ceil(t / 16) builds of the n1 x n2 rectangle; memory O((n1 + n2) (d + t))."""
+    n1, n2, t, shift = _check_matmul(kernel_fn, x1, x2, v, shift)
+    a = kernel_fn.scaled(x1)
+    ctx = a.ctx
+    b = None if x2 is None or x2 is x1 else kernel_fn.scaled(x2, ctx, dtype=a.dtype)
+    if x2 is x1:
+        n2 = n1
+    vd = as_device(v, ctx, dtype=a.dtype)
+    out = ctx.empty((n1, t), np.float64)
+    net = kernel_fn.params[0]
+    ctx.call("smn_kernel_mlp_matmul", a.dcode, net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+             kernel_fn.last_w_std, a.ptr, n1, a.shape[1], None if b is None else b.ptr, n2, a.shape[1], a.shape[1], shift, vd.ptr, t, t,
+             out.ptr, t)
+    return out
+
+
+class PcgResult:
+    """x: device fp64 [N, C]; iters: iterations run; col_iters: np.int32 [C], the iteration at which each column stopped; resid:
+    np.float64 [C], the TRUE relative residuals |b - (K + lam I) x| / |b| of the returned solution; history: np.float64
+    [iters + 1, C], the recurrence's relative residual per iteration; info: 0 converged, 1 max_iter reached, 2 breakdown (x and
+    resid are NaN); converged: info == 0."""
+
+    def __init__(self, x, iters, col_iters, resid, history, info):
+        self.x, self.iters, self.col_iters, self.resid, self.history, self.info = x, int(iters), col_iters, resid, history, int(info)
+        self.converged = self.info == 0
+
+
+def _check_pcg(kernel_fn, x, b, lam, precond, tol, max_iter, x0):
+    """Everything pcg_solve can refuse without a device: returns (n, b [n, c] float64, lam, tol, max_iter, x0 or None)."""
+    _check_matrix_free(kernel_fn)
+    n, _ = _shape2(x, "x")
+    if precond is not None:
+        if not isinstance(precond, PivotedCholesky):
+            raise TypeError("precond must be a PivotedCholesky (pivoted_cholesky's result) or None, got %s" % type(precond).__name__)
+        if precond.rank > _lib.LOWRANK_MAX_RANK:
+            raise NotImplementedError("rank %d is above the limit of %d columns (SMN_LOWRANK_MAX_RANK)" % (precond.rank, _lib.LOWRANK_MAX_RANK))
+        if precond.rank > 0 and int(precond.factor.shape[0]) != n:
+            raise ValueError("the preconditioner's factor has %d rows, x has %d" % (int(precond.factor.shape[0]), n))
+    if isinstance(b, DeviceArray):
+        b = b.numpy()
+    b = np.asarray(b, dtype=np.float64)
+    b = b.reshape(n, 1) if b.ndim == 1 and b.shape[0] == n else b
+    if b.ndim != 2 or b.shape[0] != n or b.shape[1] < 1:
+        raise ValueError("b must be [N = %d] or [N, C] with C >= 1, got shape %s" % (n, np.shape(b)))
+    if b.shape[1] > _lib.PCG_MAX_COLS:
+        raise NotImplementedError("%d right-hand sides are above the limit of %d per solve" % (b.shape[1], _lib.PCG_MAX_COLS))
+    lam, tol = float(lam), float(tol)
+    if not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError("lam must be a positive finite number, got %r" % (lam,))
+    if not 0.0 < tol < 1.0:
+        raise ValueError("tol must lie in (0, 1), got %r" % (tol,))
+    max_iter = int(max_iter)
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1, got %d" % max_iter)
+    if x0 is not None:
+        if isinstance(x0, DeviceArray):
+            x0 = x0.numpy()
+        x0 = np.asarray(x0, dtype=np.float64).reshape(n, -1)
+        if x0.shape != b.shape:
+            raise ValueError("x0 must have the shape of b %s, got %s" % (b.shape, x0.shape))
+    return n, b, lam, tol, max_iter, x0
+
+
+def pcg_solve(kernel_fn, x, b, lam, precond=None, tol=1e-6, max_iter=1000, x0=None):
+    """(K(x, x) + lam I) X = B by block preconditioned conjugate gradients with K applied matrix-free (smn_pcg_solve): a
+    PcgResult.  b [N] or [N, C <= 48]; precond a PivotedCholesky of the same kernel on x (any route produced it; M = L L^T +
+    lam I) or None (M = lam I); x0 the start (zeros by default).  Each column is its own CG recurrence and stops at
+    |r| <= tol |b|; all vectors and inner products are fp64.  Cost per iteration: one kernel_matmul with the active columns."""
+    n, b, lam, tol, max_iter, x0 = _check_pcg(kernel_fn, x, b, lam, precond, tol, max_iter, x0)
+    xs = kernel_fn.scaled(x)
+    ctx, d, c = xs.ctx, xs.shape[1], b.shape[1]
+    bd = ctx.to_device(np.ascontiguousarray(b))
+    sol = ctx.to_device(np.ascontiguousarray(x0)) if x0 is not None else ctx.empty((n, c), np.float64)
+    f = precond.factor if precond is not None and precond.rank > 0 else None
+    if f is not None and f.dtype != xs.dtype:
+        f = as_device(f, ctx, dtype=xs.dtype)
+    m = 0 if f is None else int(f.shape[1])
+    iters, info = C.c_int(0), C.c_int(0)
+    col_iters = np.zeros(c, dtype=np.int32)
+    resid = np.zeros(c, dtype=np.float64)
+    hist = np.zeros((max_iter + 1, c), dtype=np.float64)
+    net = kernel_fn.params[0]
+    ctx.call("smn_pcg_solve", xs.dcode, net, kernel_fn.act, kernel_fn.num_hiddens, kernel_fn.w_std, kernel_fn.b_std,
+             kernel_fn.last_w_std, xs.ptr, n, d, d, lam, None if f is None else f.ptr, m, max(m, 1), bd.ptr, c, c, tol, max_iter,
+             1 if x0 is not None else 0, sol.ptr, c, C.byref(iters), col_iters.ctypes.data_as(C.POINTER(C.c_int)),
+             resid.ctypes.data_as(C.POINTER(C.c_double)), hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(info))
+    return PcgResult(sol, iters.value, col_iters, resid, hist[:iters.value + 1].copy(), info.value)

@@ -1,7 +1,7 @@
 """spax — host-side mirror of the hot-path surface of the reference library of the same name.
 
 Sub-modules (import them by name, as the reference's experiments do):
-    spax.models       SPR, LowRankSPR (SPR on a rank-M pivoted-Cholesky factor), MultiSPR (C outputs over one kernel matrix),
+    spax.models       SPR, LowRankSPR (SPR on a rank-M pivoted-Cholesky factor), IterativeSPR (the exact posterior by matrix-free PCG), MultiSPR (C outputs over one kernel matrix),
                       SVSP (evaluation: test_acc_nll / evaluate)
     spax.kernels      NNGPKernel, NTKKernel (the same models on the tangent kernel of the MLP / dense-ResNet architectures)
     spax.likelihoods  GaussianLikelihood, StudentTLikelihood

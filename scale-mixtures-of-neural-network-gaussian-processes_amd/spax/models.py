@@ -18,7 +18,7 @@ from .likelihoods import _norm_logpdf, _t_logpdf
 from .priors import split_key
 from .utils import jitter
 
-__all__ = ["SPR", "LowRankSPR", "MultiSPR", "SVSP", "grad_route", "multi_grad_route", "lml_value_and_grads"]
+__all__ = ["SPR", "LowRankSPR", "IterativeSPR", "MultiSPR", "SVSP", "grad_route", "multi_grad_route", "lml_value_and_grads"]
 
 
 def lml_value_and_grads(terms, quad, logdet, n, df, scale, a=None, b=None):
@@ -713,6 +713,174 @@ class LowRankSPR(Module):
         if df > 0.0:                                  # likelihoods.py:52-65 with the quadratic form of this fit (class docstring)
             cond_df = df + self.num_data
             sigma = np.sqrt((df + float(fit.quad[0]) / scale) / cond_df * scale * v)
+            log_prob = _t_logpdf(y * self.y_std + self.y_mean, cond_df, mu, sigma)
+        else:
+            log_prob = _norm_logpdf(y * self.y_std + self.y_mean, mu, np.sqrt(v))
+        return -np.mean(log_prob)
+
+
+class IterativeSPR(Module):
+    """SPR without the N x N matrix: the exact posterior of K(X, X) + lam I by preconditioned conjugate gradients, with K applied
+    matrix-free (lowrank.kernel_matmul / lowrank.pcg_solve, csrc/kernel_matmul.hip and csrc/pcg.hip).  Memory is O(N (d + rank));
+    every solve costs (iterations) x (one build of the N x N rectangle) on the MFMA.  Same trainables and names as SPR
+    (NNGPKernel or NTKKernel over get_mlp_kernel / get_dense_resnet_kernel, eps, the likelihood's a / b), so the values of an SPR
+    or a LowRankSPR -- trained where training is cheap -- carry over: IterativeSPR.from_model(model).
+
+    fit()         solves K~ alpha = y in normalised units under lam = eps trace(K) / N, the relative ridge of SPR.predict (the
+                  trace from lowrank.kernel_diag), preconditioned by M = L L^T + lam I with L = lowrank.pivoted_cholesky(kernel_fn,
+                  x, rank) (the fused route where it exists; rank=0: unpreconditioned).  alpha, the factor and the PcgResult
+                  (model.solve_info) are kept while the hyper-parameters do not change.
+    predict(x)    (mean [T, 1], var [T] or None) in normalised units as host fp64 arrays.  mean = K(x*, X) alpha by the cross form
+                  of kernel_matmul, `chunk` points at a time; K(x*, X) is never stored.  var=True adds var = k** - k*^T K~^-1 k* by
+                  block solves: ONE PCG PER BLOCK of var_block <= 48 test points (right-hand sides K(X, x*_block)), so T points
+                  cost ceil(T / var_block) solves of the size of fit().
+    test_nll      SPR.test_nll's per-point heads on those marginals.  DEVIATION for the Student-t head, as LowRankSPR documents
+                  and for the same reason: its quadratic form is y^T alpha of this solve, y^T (scale K~)^-1 y = quad / scale.
+    A solve that ends with info != 0 makes predict warn with the residual reached; the values are still returned.
+    loss, loss_and_grad, the leave-one-out entries, posterior() and sample_posterior are not implemented: there is no
+    log-determinant here (train on LowRankSPR or SPR)."""
+
+    def __init__(self, kernel, likelihood, x_data, y_data, y_mean, y_std, *, rank=256, eps: float = 1e-6, tol: float = 1e-6,
+                 max_iter: int = 1000):
+        super().__init__()
+        from .. import lowrank
+        shape = tuple(x_data.shape) if hasattr(x_data, "shape") else np.shape(x_data)
+        if len(shape) < 2 or shape[0] < 1:
+            raise ValueError("x_data must be [N, ...] with N >= 1, got shape %s" % (shape,))
+        if isinstance(rank, bool) or int(rank) != rank:
+            raise ValueError("rank must be an integer, got %r" % (rank,))
+        if not 0 <= int(rank) <= _lib.LOWRANK_MAX_RANK:
+            raise ValueError("rank must lie in [0, %d] (0: no preconditioner), got %d" % (_lib.LOWRANK_MAX_RANK, rank))
+        if not 0.0 < float(tol) < 1.0:
+            raise ValueError("tol must lie in (0, 1), got %r" % (tol,))
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError("max_iter must be an integer >= 1, got %r" % (max_iter,))
+        if not hasattr(likelihood, "lml_params"):
+            raise NotImplementedError("IterativeSPR needs a Gaussian or Student-t likelihood")
+        y = np.asarray(y_data, dtype=np.float64).reshape(-1)
+        if y.shape[0] != shape[0]:
+            raise ValueError("y_data has %d entries for N = %d inputs" % (y.shape[0], shape[0]))
+        self._lowrank = lowrank
+        self.kernel, self.likelihood = kernel, likelihood
+        self.rank, self.tol, self.max_iter = min(int(rank), shape[0]), float(tol), int(max_iter)
+        self.x_data = as_device(x_data)
+        self.y_host = y
+        self.y_mean, self.y_std = float(np.asarray(y_mean)), float(np.asarray(y_std))
+        self.num_data = self.x_data.shape[0]
+        self.eps = ConstraintTrainVar(eps, constraint=positive())
+        self.solve_info = None
+        self._fit_cache = None                       # (key, kernel_fn, lam, PivotedCholesky or None, PcgResult, y^T alpha)
+
+    @classmethod
+    def from_model(cls, model, **kw):
+        """The matrix-free model of an SPR or a LowRankSPR: its kernel and likelihood objects (so the trained values carry
+        over), its data and its eps; rank, tol and max_iter from **kw."""
+        for name in ("kernel", "likelihood", "x_data", "y_host", "y_mean", "y_std", "eps"):
+            if not hasattr(model, name):
+                raise TypeError("from_model needs an SPR or a LowRankSPR, got %s" % type(model).__name__)
+        kw.setdefault("eps", model.eps.safe_value)
+        return cls(model.kernel, model.likelihood, model.x_data, model.y_host, model.y_mean, model.y_std, **kw)
+
+    # ---- what is not there, refused before any device call
+    def _missing(self, what):
+        raise NotImplementedError("IterativeSPR has no %s: there is no log-determinant here; LowRankSPR (approximate) and SPR "
+                                  "(exact, N x N) do" % what)
+
+    def loss(self):
+        self._missing("training objective")
+
+    def loss_and_grad(self):
+        self._missing("analytic gradient")
+
+    def loo_loss(self):
+        self._missing("leave-one-out objective")
+
+    def loo_predict(self):
+        self._missing("leave-one-out predictions")
+
+    def loo_loss_and_grad(self):
+        self._missing("leave-one-out gradient")
+
+    def posterior(self, *args, **kwargs):
+        self._missing("fitted posterior")
+
+    def sample_posterior(self, *args, **kwargs):
+        self._missing("joint posterior draws")
+
+    # ---- the solve, kept by hyper-parameter content
+    def _kernel_fn(self):
+        kernel_fn = self.kernel.get_kernel_fn()
+        if not isinstance(kernel_fn, KernelFn):
+            raise NotImplementedError("IterativeSPR exists for get_mlp_kernel / get_dense_resnet_kernel (NNGPKernel or NTKKernel), "
+                                      "not for %s" % type(kernel_fn).__name__)
+        return kernel_fn
+
+    def fit(self):
+        """Solve K~ alpha = y (see the class docstring); returns the PcgResult, also kept as model.solve_info."""
+        kernel_fn = self._kernel_fn()
+        eps = self.eps.safe_value
+        key = (kernel_fn.cov, tuple(kernel_fn.params), _scales_key(kernel_fn), eps, self.rank, self.tol, self.max_iter)
+        hit = self._fit_cache
+        if hit is None or hit[0] != key:
+            lr = self._lowrank
+            trace = float(np.sum(np.asarray(lr.kernel_diag(kernel_fn, self.x_data).raw_numpy(), dtype=np.float64)))
+            lam = eps * trace / self.num_data
+            pre = lr.pivoted_cholesky(kernel_fn, self.x_data, self.rank) if self.rank > 0 else None
+            sol = lr.pcg_solve(kernel_fn, self.x_data, self.y_host, lam, precond=pre, tol=self.tol, max_iter=self.max_iter)
+            quad = float(self.y_host @ sol.x.numpy()[:, 0])
+            hit = self._fit_cache = (key, kernel_fn, lam, pre, sol, quad)
+        self.solve_info = hit[4]
+        return hit[4]
+
+    def _warn(self, sol, what):
+        if sol.info != 0:
+            import warnings
+            warnings.warn("IterativeSPR: %s ended with info = %d after %d iterations (true relative residual %.3e, tol %.1e); the "
+                          "values are returned as they are" % (what, sol.info, sol.iters, float(np.nanmax(sol.resid)), self.tol),
+                          RuntimeWarning, stacklevel=3)
+
+    def predict(self, x, var=False, chunk=2048, var_block=48):
+        """(mean [T, 1], var [T] or None): see the class docstring.  var=True costs one PCG per block of var_block test points."""
+        if int(chunk) < 1:
+            raise ValueError("chunk must be at least 1")
+        if not 1 <= int(var_block) <= _lib.PCG_MAX_COLS:
+            raise ValueError("var_block must lie in [1, %d], got %r" % (_lib.PCG_MAX_COLS, var_block))
+        xt = np.asarray(x.numpy() if isinstance(x, DeviceArray) else x)
+        if xt.ndim < 2 or xt.shape[1:] != tuple(self.x_data.shape[1:]):
+            raise ValueError("x has shape %s, the training inputs %s" % (xt.shape, tuple(self.x_data.shape)))
+        sol = self.fit()
+        self._warn(sol, "the solve of fit()")
+        _, kernel_fn, lam, pre, _, _ = self._fit_cache
+        lr, ctx, dt = self._lowrank, self.x_data.ctx, self.x_data.dtype
+        t = xt.shape[0]
+        mean = np.zeros((t, 1), dtype=np.float64)
+        for a in range(0, t, int(chunk)):
+            xc = ctx.to_device(np.ascontiguousarray(xt[a:a + int(chunk)], dtype=dt))
+            mean[a:a + int(chunk)] = lr.kernel_matmul(kernel_fn, xc, self.x_data, sol.x).numpy()
+        if not var:
+            return mean, None
+        out = np.zeros(t, dtype=np.float64)
+        self.var_info = []
+        for a in range(0, t, int(var_block)):
+            xb = ctx.to_device(np.ascontiguousarray(xt[a:a + int(var_block)], dtype=dt))
+            rhs = np.asarray(lr.kernel_cross(kernel_fn, self.x_data, xb).numpy(), dtype=np.float64)
+            ktt = np.asarray(lr.kernel_diag(kernel_fn, xb).raw_numpy(), dtype=np.float64)
+            blk = lr.pcg_solve(kernel_fn, self.x_data, rhs, lam, precond=pre, tol=self.tol, max_iter=self.max_iter)
+            self._warn(blk, "a variance block solve")
+            self.var_info.append(blk)
+            out[a:a + int(var_block)] = ktt - np.einsum("ij,ij->j", rhs, blk.x.numpy())
+        return mean, out
+
+    def test_nll(self, x, y, chunk=2048, var_block=48):
+        mean, var = self.predict(x, var=True, chunk=chunk, var_block=var_block)
+        quad = self._fit_cache[5]
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        mu = mean.reshape(-1) * self.y_std + self.y_mean
+        v = var * self.y_std ** 2
+        df, scale = self.likelihood.lml_params()
+        if df > 0.0:                                  # likelihoods.py:52-65 with the quadratic form of this solve (class docstring)
+            cond_df = df + self.num_data
+            sigma = np.sqrt((df + quad / scale) / cond_df * scale * v)
             log_prob = _t_logpdf(y * self.y_std + self.y_mean, cond_df, mu, sigma)
         else:
             log_prob = _norm_logpdf(y * self.y_std + self.y_mean, mu, np.sqrt(v))
